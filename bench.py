@@ -18,6 +18,12 @@ applied like src/data.cu:96-133 (the un-reordered number is reported beside it).
 scaling -- the global graph is N x arxiv-shaped, 1-D row-partitioned; every step pulls the halo
 feature rows with one RCCL all-to-all and then runs the same kernel (gnn_computing_amd/dist.py).
 Rank 0 prints ONE JSON line.
+
+N = 1, config A: a plain run sets up, warms up, times the K steps of the headline arm and prints the line (`value`, `ms_per_step`
+and the figures that need no launch of their own).  --full adds everything else the line has carried: the arm without the reorder
+and the MinHash-cluster arm, the oracle check of the whole output, the gather probes and ceilings, the other single-GPU configs
+(`configs`) and the CPU baseline.  --dump-outputs DIR writes what the timed step computed in its last step (a fixed seeded sample
+of the output rows, in the original row numbering) as DIR/<name>.npy: the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -92,12 +98,13 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
-def time_steps(step_fn, steps, warmup, barrier):
+def time_steps(step_fn, steps, warmup, barrier, median=True):
     """W untimed warm-up steps, then exactly K steps between barrier + synchronize on both sides.
     Returns (wall seconds for the K steps, avg device seconds per step from ONE pair of HIP events around the K launches on
     the launch stream, median device seconds per step).  Nothing but the K steps is enqueued inside the timed region: an
     event record between launches is a barrier packet that drains the queue (it cost ~3 us per 80 us step); the per-step
-    median comes from a separate pass with one event pair per launch, after the timed region."""
+    median comes from a separate pass with one event pair per launch, after the timed region (median=False: no such pass, None).
+    The outputs of the K-th timed step are what the step function's buffers hold when this returns."""
     # Host hygiene first (nothing of it is inside the timed region): the GPU boxes run this process in a CPU-quota'd container,
     # where a host thread that has been busy-waiting can be descheduled for 45-55 ms (seen once per few hundred launches,
     # scripts/history/exp_stall_hunt.py: GPU times unaffected); an idle period lets the quota window roll over, and the collector stays
@@ -117,7 +124,7 @@ def time_steps(step_fn, steps, warmup, barrier):
             time_steps._stream = s_
             s_.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s_):
-                r_ = time_steps(step_fn, steps, warmup, barrier)
+                r_ = time_steps(step_fn, steps, warmup, barrier, median)
             torch.cuda.current_stream().wait_stream(s_)
             return r_
         finally:
@@ -145,6 +152,8 @@ def time_steps(step_fn, steps, warmup, barrier):
     if gc_was_on:
         gc.enable()
     dev = ev0.elapsed_time(ev1) * 1e-3 / steps
+    if not median:
+        return wall, dev, None
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     evs[0].record()
     for i in range(steps):
@@ -153,6 +162,26 @@ def time_steps(step_fn, steps, warmup, barrier):
     torch.cuda.synchronize()
     per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e-3 for i in range(steps))
     return wall, dev, per[len(per) // 2]
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: at most this many bytes of sampled output rows (+ their ids), under the 64 MB a dump may take
+
+
+def dump_outputs(dirname, y, rows=None, first_row=0, name="y"):
+    """--dump-outputs DIR: what the timed step left in its output Y [n, F] -- the array a caller of that step receives --, as
+    DIR/<name>.npy (float32), in the graph's ORIGINAL row numbering: `rows` is the locality reorder's permutation (entry i = original row
+    at position i), which is undone.  Y is larger than a dump may be, so a fixed seeded sample of rows is written (sorted, the same rows for
+    the same arguments on every run and every build), with their row ids (+ first_row: a rank's first global row) as DIR/<name>_rows.npy
+    (float64)."""
+    n, F = y.shape
+    count = min(n, 65536, DUMP_BYTES // (4 * F + 8))
+    pick = np.sort(np.random.default_rng(0).choice(n, count, replace=False))
+    at = pick if rows is None else np.argsort(np.asarray(rows))[pick]   # position of original row r after the reorder
+    got = y[torch.from_numpy(at.astype(np.int64)).to(y.device)].to(torch.float32).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), got)
+    np.save(os.path.join(dirname, name + "_rows.npy"), (pick + first_row).astype(np.float64))
+    log("bench.py: wrote %s/%s.npy (%d x %d float32, rows sampled with seed 0) and %s_rows.npy" % (dirname, name, count, F, name))
 
 
 CPU_BASELINE_CHILD = r"""
@@ -231,6 +260,7 @@ def run_single(args, dev):
     rng = np.random.default_rng(123)
     x = rng.standard_normal((V, FEAT), dtype=np.float32)
     val = np.ones(E, np.float32)
+    which = os.environ.get("BENCH_HEADLINE", "reorder")
 
     prep = {}
 
@@ -251,17 +281,27 @@ def run_single(args, dev):
     dx = torch.from_numpy(x).to(dev)
     y = torch.empty((V, FEAT), dtype=torch.float32, device=dev)
     results = {}
+    # A plain run times the headline arm only (BENCH_HEADLINE, default: with the reorder); --full times both arms and everything below.
     # without reorder
-    agg0 = build(ptr, idx)
-    results["no_reorder"] = time_steps(lambda: agg0.run(dx, y, 512, mode), args.steps, args.warmup, lambda: None)
+    if args.full or which == "no_reorder":
+        agg0 = build(ptr, idx)
+        results["no_reorder"] = time_steps(lambda: agg0.run(dx, y, 512, mode), args.steps, args.warmup, lambda: None, args.full)
+        if which == "no_reorder" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, y, None)
     # with the locality reorder applied on load (reference: load_graph(..., "_thres_0.2"), our.py:79)
     # the reorder GENERATOR (what writes a <dset>.reorder_thres_0.2 file; the reference's is the offline script script/cluster2.py) is the
     # library's gnnagg_cluster_reorder_ex; the file is applied by the library's loader (load_with_locality_reorder above).  The
-    # reference's MinHash-64 + LSH(0.2) + capped-64 clustering written in first-member order is timed beside it.
-    nptr, nidx, rows, t_reorder, t_load = load_with_locality_reorder("arxiv", ptr, idx)
-    agg1 = build(nptr, nidx)
-    dx1 = torch.from_numpy(np.ascontiguousarray(x[rows])).to(dev)
-    results["reorder"] = time_steps(lambda: agg1.run(dx1, y, 512, mode), args.steps, args.warmup, lambda: None)
+    # reference's MinHash-64 + LSH(0.2) + capped-64 clustering written in first-member order is timed beside it (--full).
+    t_reorder = t_load = None
+    if args.full or which == "reorder":
+        nptr, nidx, rows, t_reorder, t_load = load_with_locality_reorder("arxiv", ptr, idx)
+        agg1 = build(nptr, nidx)
+        dx1 = torch.from_numpy(np.ascontiguousarray(x[rows])).to(dev)
+        results["reorder"] = time_steps(lambda: agg1.run(dx1, y, 512, mode), args.steps, args.warmup, lambda: None, args.full)
+        if which == "reorder" and args.dump_outputs:
+            dump_outputs(args.dump_outputs, y, rows)
+    if not args.full:
+        return plain_line(args, results[which], V, E, which, mode, prep.get("schedule_prep_s"), t_reorder, t_load)
     y_reorder = y.clone()
     rows_m, _ = gnc.cluster_reorder(ptr, idx, order="first_member")
     mptr, midx, _ = gnc.reorder_csr(ptr, idx, rows_m)
@@ -277,7 +317,6 @@ def run_single(args, dev):
            else orc.gcn_grouped(ps, tg, nidx, val, x[rows], V, seg=seg))
     assert np.array_equal(y.cpu().numpy(), ref), "bench output differs from the oracle"
 
-    which = os.environ.get("BENCH_HEADLINE", "reorder")
     wall, dev_s, med_s = results[which]
     ms = wall / args.steps * 1e3
     B = algorithmic_bytes(V, E, FEAT)
@@ -347,6 +386,7 @@ def run_single(args, dev):
         "reorder_prep_s": t_reorder, "reorder_load_s": t_load, "reorder_cache_hit": t_reorder == 0.0,
         "reorder_walkers": int(os.environ.get("GNNAGG_REORDER_WALKERS", "0")) or (64 if E >= 20000000 else 1),
         "schedule_prep_s": prep.get("schedule_prep_s"),
+        "full": True,
     }
     if mode == "balanced" and which == "reorder":
         del agg0, agg2, agg_u, dx, dx2, rid
@@ -358,14 +398,49 @@ def run_single(args, dev):
     return out
 
 
-def summarize(out):
+def plain_line(args, timed, V, E, which, mode, schedule_prep_s, t_reorder, t_load):
+    """The line of a plain run (no --full): the headline arm's K timed steps and the figures that need no launch of their own -- the
+    gather-model bytes over the measured launch time and the committed counter traffic of config A.  Nothing was compared with the oracle,
+    so the summary says `verified: null` (--full checks the whole output)."""
+    wall, dev_s, _ = timed
+    B, C = algorithmic_bytes(V, E, FEAT), compulsory_bytes(V, E, FEAT)
+    achieved = B / dev_s / 1e9
+    traffic, _, traffic_label, traffic_stale = pmc_traffic("A")
+    traffic_gbps = traffic / dev_s / 1e9 if traffic else None
+    out = {
+        "metric": "aggregated edges/sec, GCN SpMM feat=128", "value": E / (wall / args.steps), "unit": "edges/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "arxiv-shaped CSR 169343x1166243 (seed 123), GCN sum, feat=128, unit weights, %s, mode=%s" % (
+                       "locality reorder applied on load (.reorder_thres_0.2)" if which == "reorder" else "no reorder", mode),
+                   "num_v": V, "num_e": E, "feat": FEAT},
+        "achieved_gbps": achieved,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                     "frac": (traffic_gbps / HBM_PEAK_GBPS) if traffic_gbps else achieved / HBM_PEAK_GBPS,
+                     "frac_is": ("counter traffic (fabric side: Infinity-Cache hits included) / avg launch time / 8 TB/s; DESIGN.md 5"
+                                 if traffic_gbps else "algorithmic bytes / avg launch time / 8 TB/s (no counter file); DESIGN.md 5"),
+                     "traffic": traffic, "traffic_source": traffic_label, "traffic_stale": traffic_stale, "traffic_gbps": traffic_gbps,
+                     "algorithmic_frac": achieved / HBM_PEAK_GBPS, "kernel": "k_gcn_plan", "algorithmic_bytes": B, "compulsory_bytes": C,
+                     "avg_launch_us": dev_s * 1e6},
+        "schedule_prep_s": schedule_prep_s,
+        "full": False,
+    }
+    if which == "reorder":
+        out.update({"reorder_prep_s": t_reorder, "reorder_load_s": t_load, "reorder_cache_hit": t_reorder == 0.0})
+    out["summary"] = summarize(out, verified=False)
+    return out
+
+
+def summarize(out, verified=True):
     """Every record of the line in one compact object: name -> [ms_per_step, roofline.frac, frac_vs_gather_ceiling, verified_rows]
-    (A: the headline, whole output compared; *_no_reorder: the arm without the locality reorder)."""
+    (A: the headline, whole output compared; *_no_reorder: the arm without the locality reorder).  verified=False (a plain run): no
+    record was compared with the oracle -- verified_rows 0 and `verified` null."""
     def row(rec, verified_rows):
         r = rec.get("roofline", {})
-        return [round(rec["ms_per_step"], 5), round(r.get("frac", 0.0), 4), round(r.get("frac_vs_gather_ceiling", 0.0), 4), verified_rows]
+        ceil = r.get("frac_vs_gather_ceiling")   # (not measured by a plain run: null)
+        return [round(rec["ms_per_step"], 5), round(r.get("frac", 0.0), 4), None if ceil is None else round(ceil, 4), verified_rows]
     s = {"fields": ["ms_per_step", "roofline.frac", "frac_vs_gather_ceiling", "verified_rows"],
-         "A": row(out, out["config"]["num_v"])}
+         "A": row(out, out["config"]["num_v"] if verified else 0)}
     if "no_reorder" in out:
         s["A_no_reorder_us"] = round(out["no_reorder"]["avg_launch_us"], 2)
     ok = True
@@ -383,7 +458,7 @@ def summarize(out):
     s["edges_per_s"] = round(out["value"])
     if "cpu_baseline" in out:
         s["cpu_edges_per_s"] = round(out["cpu_baseline"]["value"])
-    s["verified"] = ok
+    s["verified"] = ok if verified else None
     return s
 
 
@@ -509,10 +584,11 @@ def gather_ceiling(dev, key):
     return _CEILINGS[key]
 
 
-def measure_config(cfg, args, dev, graph=None):
+def measure_config(cfg, args, dev, graph=None, dump=None):
     """One of the other single-GPU configurations of BASELINE.json, timed like the headline (time_steps) and checked against the oracle
     on sampled rows: R = reddit-shaped SAGE mean F=602, G = reddit-shaped GAT 8x32, P1 = products-shaped GCN F=100 on one GPU.
-    Reference call sequences being timed: Figure9/main.cu:59-74 (GCN run), Figure10/main_a.cu:82-110 (GAT run)."""
+    Reference call sequences being timed: Figure9/main.cu:59-74 (GCN run), Figure10/main_a.cu:82-110 (GAT run).  dump = DIR: the
+    line's own arm's output after its timed steps (dump_outputs)."""
     import gnn_computing_amd as gnc
     name = {"R": "reddit", "G": "reddit", "P1": "products"}[cfg]
     ptr, idx = graph if graph is not None else gnc.graph.dataset(name, device=dev)
@@ -597,6 +673,7 @@ def measure_config(cfg, args, dev, graph=None):
         return rec
 
     arm = measure_arm(agg, ptr, idx, cfg)
+    rows_r = None
     no_reorder = None
     if cfg == "P1" and os.environ.get("BENCH_P1_REORDER", "1") != "0":
         # north_star applies the locality reorder ON LOAD and SURVEY 8(e) partitions after it, so the line's `value` is the reordered graph
@@ -605,7 +682,7 @@ def measure_config(cfg, args, dev, graph=None):
         no_reorder = arm
         del agg
         torch.cuda.empty_cache()
-        nptr, nidx, _, t_gen, t_load = load_with_locality_reorder("products", ptr.cpu().numpy(), idx.cpu().numpy())
+        nptr, nidx, rows_r, t_gen, t_load = load_with_locality_reorder("products", ptr.cpu().numpy(), idx.cpu().numpy())
         ptr_r, idx_r = torch.from_numpy(nptr).to(dev), torch.from_numpy(nidx).to(dev)
         agg = gnc.Aggregator_GCN(ptr_r, idx_r, val, F, F)
         arm = measure_arm(agg, ptr_r, idx_r, "P1_reorder")
@@ -617,6 +694,8 @@ def measure_config(cfg, args, dev, graph=None):
             "frac": no_reorder["roofline"]["frac"], "frac_vs_gather_ceiling": no_reorder["roofline"]["frac_vs_gather_ceiling"],
             "avg_launch_us": no_reorder["roofline"]["avg_launch_us"], "probe_frac": no_reorder["roofline"]["probe_frac"],
             "traffic_step": no_reorder["roofline"]["traffic_step"]}
+    if dump:
+        dump_outputs(dump, y, rows_r)   # (the probe launches after the timed steps store nothing: y is the last timed step's)
     rec = {"metric": "aggregated edges/sec, config %s" % cfg, "value": arm["value"], "unit": "edges/s",
            "n_gpus": 1, "steps": steps, "warmup": warm, "ms_per_step": arm["ms_per_step"], "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -628,7 +707,7 @@ def measure_config(cfg, args, dev, graph=None):
 
 
 def run_other_config(args, dev):
-    rec = measure_config(args.config, args, dev)
+    rec = measure_config(args.config, args, dev, dump=args.dump_outputs)
     r = rec["roofline"]
     rec["summary"] = {"fields": ["ms_per_step", "roofline.frac", "frac_vs_gather_ceiling", "verified_rows"],
                       args.config: [round(rec["ms_per_step"], 5), round(r["frac"], 4), round(r["frac_vs_gather_ceiling"], 4), rec["verified_rows"]],
@@ -733,9 +812,10 @@ class Watchdog:
         self.deadline = None
 
 
-def partitioned_run(args, dev, rank, world, strong, steps, warmup, transport, dog):
+def partitioned_run(args, dev, rank, world, strong, steps, warmup, transport, dog, dump=None):
     """One row-partitioned configuration over the `world` ranks: weak (N x arxiv-shaped, feat 128) or strong (ONE products-shaped
-    graph, feat 100).  Returns the measurements on rank 0 (None elsewhere)."""
+    graph, feat 100).  Returns the measurements on rank 0 (None elsewhere).  dump = DIR: rank 0 writes its rows of the last timed step's
+    output (dump_outputs, y_rank0)."""
     import torch.distributed as dist
     import gnn_computing_amd as gnc
     from gnn_computing_amd.dist import PartitionedGCN
@@ -830,6 +910,8 @@ def partitioned_run(args, dev, rank, world, strong, steps, warmup, transport, do
     dog.arm(120 + 0.5 * (steps + warmup) * 3, "timed steps over the %s transport" % transport)
     wall, dev_s, med_s = time_steps(pg.step, steps, warmup, dist.barrier)
     dog.disarm()
+    if dump and rank == 0:
+        dump_outputs(dump, pg.y, None, first_row=r0, name="y_rank0")
     t = torch.tensor([wall], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     halo = torch.tensor([hx.halo_bytes(feat), pg.num_e_local, pg.num_e_remote if pg.overlap else 0], dtype=torch.float64, device=dev)
@@ -907,7 +989,7 @@ def run_multi(args, dev, rank, world, dog):
     backend = dist.get_backend()
     transport = os.environ.get("BENCH_TRANSPORT") or ("rccl" if backend == "nccl" else "torch")
     strong = args.config == "P"  # BASELINE configs[4]: ONE products-shaped graph row-partitioned over the N GPUs
-    m = partitioned_run(args, dev, rank, world, strong, args.steps, args.warmup, transport, dog)
+    m = partitioned_run(args, dev, rank, world, strong, args.steps, args.warmup, transport, dog, dump=args.dump_outputs)
     # one driver pass yields both: the N > 1 headline line (weak scaling, feat 128) carries BASELINE configs[4] -- the products-shaped
     # graph strong-scaled over the same ranks -- as a sub-record (fewer steps: a step is milliseconds there)
     ps = None
@@ -1133,7 +1215,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="config A on one GPU: besides the headline arm, time the arm without the reorder and the MinHash-cluster arm, check the "
+                         "output against the oracle, measure the gather probes and ceilings, the other configs (BENCH_CONFIGS) and the CPU baseline. "
+                         "Without it a run sets up, warms up, times the K steps of the headline arm and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed step computed in its last step (a fixed seeded sample of the output rows, "
+                         "original row numbering) as DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--config", default="A", choices=["A", "R", "G", "P1", "P"],
                     help="A (default): arxiv-shaped GCN sum feat=128, the headline line (weak scaling for N > 1, with the products-shaped "

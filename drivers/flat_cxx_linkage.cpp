@@ -1,7 +1,7 @@
 // flat_cxx_linkage.cpp -- the ten flat functions of Figure7/kernel.cpp:15-35 with C++ linkage, forwarding to the extern "C"
 // symbols of libgnnagg.so (include/gnnagg.h section A).  The reference's torch binding DECLARES them without extern "C"
 // (its definitions live in Figure7/kernel_generated.cu); with this translation unit in the link, Figure7/kernel.cpp builds
-// against the library without an edit (drivers/build_reference_torch_ext.py).  A C++ function and a C function of the same
+// against the library without an edit (oracle/build_reference_torch_ext.py).  A C++ function and a C function of the same
 // name and parameters cannot be declared in one scope, hence the asm labels.
 #include <cstdint>
 #define C_SYM(ret, name, params) extern "C" ret c_##name params __asm__(#name)

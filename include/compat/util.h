@@ -234,7 +234,7 @@ inline void argParse(int argc, char **argv, int *p_limit = nullptr, int *p_limit
 
 // ---- The reference's OWN helper names, spelled as its drivers spell them (reference util.h:29,82-104,144-151, util.cu:157-175).
 // With these, a reference driver (Figure8/9/10 main*.cu) needs nothing but the mechanical cuda* -> hip* rename of ROCm's
-// hipify-perl to build against this directory and libgnnagg.so -- no hand edits: drivers/build_reference_drivers.sh.
+// hipify-perl to build against this directory and libgnnagg.so -- no hand edits: oracle/build_reference_drivers.sh.
 #if __has_include(<hiprand.h>)
 #include <hiprand.h>
 #endif

@@ -1,5 +1,5 @@
 #!/bin/bash
-# drivers/build_reference_drivers.sh -- the drop-in claim, exercised: the REFERENCE's own benchmark drivers
+# oracle/build_reference_drivers.sh -- the drop-in claim, exercised: the REFERENCE's own benchmark drivers
 # (/root/reference/Figure8/main.cu, Figure9/main.cu, Figure10/main_a.cu, Figure10/main_b.cu), translated where they lie by ROCm's hipify-perl
 # (the mechanical cuda* -> hip* rename, no hand edits) into a scratch directory, compiled against THIS repo's class shim
 # (include/compat/: Aggregator_GCN / Aggregator_GAT / load_graph / fullGraph / argParse / matmul_NN with the reference's
@@ -13,7 +13,7 @@ set -e
 REF=${REF:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
 ROCM=${ROCM_PATH:-/opt/rocm}
-OUTDIR="$HERE/../oracle/_ref/drivers"   # every reference-derived binary lives under oracle/_ref/ (git-ignored)
+OUTDIR="$HERE/_ref/drivers"   # every reference-derived binary lives under oracle/_ref/ (git-ignored)
 if [ ! -d "$REF/Figure9" ] || [ ! -x "$ROCM/bin/hipify-perl" ]; then echo "oracle/_ref/drivers: no reference tree: not built"; exit 0; fi
 if [ -f "$OUTDIR/fig10b_ref.out" ] && [ -f "$OUTDIR/fig8_ref.out" ] && [ -z "$FORCE" ]; then   # up to date?
   newer=$(find "$REF/Figure8/main.cu" "$REF/Figure9/main.cu" "$REF/Figure10/main_a.cu" "$REF/Figure10/main_b.cu" "$HERE/../include/compat" "$HERE/../include/gnnagg.h" \

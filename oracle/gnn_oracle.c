@@ -22,7 +22,7 @@
  *   - fp32 stages: the reference's kernels run on the MI355X -- orc_gcn_seq is BIT-EQUAL to
  *     aggr_gcn; the grouped / GAT restatements agree with aggr_gcn_target, aggr_gat and
  *     aggr_gat_fine + scaleArray within 1e-5 * sum_e |w_e x_e| (atomicAdd order, __expf) --
- *     tests/test_gpu_reference.py, recorded in tests/golden/reference_device.npz.
+ *     tests/test_gpu_reference.py, recorded in tests/golden/reference_device_<case>.npz.
  *   - edge-softmax stages (attGat, u_add_v, add_to_center, each_div) through the reference's
  *     methods with BLOCK_SIZE = 32 (one of its 32-lane warps per 64-lane wavefront): u_add_v and
  *     each_div exact, attGat within 1e-5 relative, row sums within 1e-5 * sum|v|.

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-arm averages of the aggregation kernel from the rocprofv3 kernel trace of `bench.py --steps K --warmup W`: the bench
+"""Per-arm averages of the aggregation kernel from the rocprofv3 kernel trace of `bench.py --full --steps K --warmup W`: the bench
 launches the same kernel for several inputs one after the other (no reorder, locality reorder = the headline arm, MinHash
 clusters, uniform-random ids), each W warm-up + K timed launches + K launches with one event pair each (the median); the
 probe launches are a different template instantiation.  usage: bench_arms_from_trace.py <kernel_trace.csv> K W"""
@@ -23,7 +23,7 @@ def arms(rs, names):
     return out
 
 
-print("# rocprofv3 --kernel-trace of `python3 bench.py --steps %d --warmup %d --no-cpu`: timed launches per arm, in launch order" % (K, W))
+print("# rocprofv3 --kernel-trace of `python3 bench.py --full --steps %d --warmup %d --no-cpu`: timed launches per arm, in launch order" % (K, W))
 for line in arms(real, ["no reorder", "locality reorder applied on load (HEADLINE arm)", "MinHash clusters, first-member order",
                         "uniform-random neighbor ids (same degrees)"]):
     print(line)

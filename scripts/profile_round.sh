@@ -9,7 +9,7 @@ STEPS=${STEPS:-50}; WARM=${WARM:-5}
 mkdir -p $OUT
 export TMPDIR=/tmp
 export GNNAGG_BUILD_LABEL=${GNNAGG_BUILD_LABEL:-$(md5sum gnn_computing_amd/libgnnagg.so | cut -c1-12)}
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench -o t -- python3 bench.py --steps $STEPS --warmup $WARM --no-cpu > $OUT/bench_under_rocprof.json 2> $OUT/trace_bench.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench -o t -- python3 bench.py --full --steps $STEPS --warmup $WARM --no-cpu > $OUT/bench_under_rocprof.json 2> $OUT/trace_bench.log
 cp $(find $OUT/trace_bench -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 python3 scripts/bench_arms_from_trace.py $(find $OUT/trace_bench -name "*kernel_trace.csv" | head -1) $STEPS $WARM > $OUT/bench_arms.txt
 for cfg in A ${CONFIGS:-R G P1}; do
@@ -17,7 +17,7 @@ for cfg in A ${CONFIGS:-R G P1}; do
 done
 python3 scripts/collect_profiles.py $OUT $OUT/pmc_traffic.json
 ROUND=${ROUND:-r03}; mkdir -p profiles/$ROUND && cp $OUT/pmc_traffic.json profiles/$ROUND/pmc_traffic.json
-python3 bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 for cfg in ${CONFIGS:-R G P1}; do case $cfg in A_rows|P1_reorder) continue;; esac; python3 bench.py --config $cfg --no-cpu >> $OUT/bench_configs.jsonl 2>> $OUT/bench.err; done
 rm -rf $OUT/trace_* $OUT/pmc_[A-Z]*_*
 ls $OUT

@@ -10,8 +10,8 @@ FAKE=$PWD/tests/fake_rccl/libfakerccl.so
 # 1. the driver's command under rocprofv3 (kernel trace + stats), PMC passes per config (A, A_rows, R, G, P1: traffic, L2 hit), pmc_traffic.json,
 #    then the bench line itself (configs sub-records included) and the per-config lines
 CONFIGS="A_rows R G P1" STEPS=${STEPS:-20} WARM=${WARM:-5} SQ=${SQ:-0} bash scripts/profile_round.sh $OUT > $OUT/profile_round.log 2>&1
-# 2. the driver's exact command once more, as the driver runs it (20 steps, 5 warm-up, cpu_baseline included)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err
+# 2. the driver's command once more with everything the line measures (--full: 20 steps, 5 warm-up, cpu_baseline included)
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err
 # 3. N > 1 lines on this ONE GPU -- functional checks of the row-partitioned step, labelled as such by the line itself
 BENCH_ONE_GPU=1 BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu > $OUT/bench_2ranks_one_gpu.json 2> $OUT/bench_2ranks_one_gpu.err
 D="BENCH_ONE_GPU=1 BENCH_BACKEND=gloo BENCH_TRANSPORT=rccl BENCH_NO_FALLBACK=1 GNNAGG_RCCL_LIB=$FAKE"

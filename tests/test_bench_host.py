@@ -24,7 +24,9 @@ print(json.dumps(out))
 def test_supervisors_agree_before_falling_back():
     """a subset of ranks failing must not leave the failed ranks alone in a new rendezvous.  Three supervisors (children of
     this process, like ranks under one launcher); one child 'failed' with 17: all three see 17 and the SAME next port, then 0."""
-    procs = [subprocess.Popen([sys.executable, "-c", CHILD, ROOT, str(r), "3", "17" if r == 1 else "0"], stdout=subprocess.PIPE, text=True)
+    # (each test is its own job: its own rendezvous port, hence its own directory -- sup_dir() keys on this process's pid AND the port)
+    env = dict(os.environ, MASTER_PORT="29601")
+    procs = [subprocess.Popen([sys.executable, "-c", CHILD, ROOT, str(r), "3", "17" if r == 1 else "0"], stdout=subprocess.PIPE, text=True, env=env)
              for r in range(3)]
     outs = [json.loads(p.communicate(timeout=120)[0].strip().splitlines()[-1]) for p in procs]
     assert all(p.returncode == 0 for p in procs)
@@ -44,7 +46,8 @@ def test_agreement_is_per_node():
     sys.path.insert(0, ROOT)
     import bench
     # a node with two local ranks of a (say) 16-rank job: the two agree without waiting for 16 files
-    procs = [subprocess.Popen([sys.executable, "-c", CHILD, ROOT, str(r), "2", "0"], stdout=subprocess.PIPE, text=True) for r in range(2)]
+    env = dict(os.environ, MASTER_PORT="29602")   # not the directory test_supervisors_agree_before_falling_back left its 17 in
+    procs = [subprocess.Popen([sys.executable, "-c", CHILD, ROOT, str(r), "2", "0"], stdout=subprocess.PIPE, text=True, env=env) for r in range(2)]
     outs = [json.loads(p.communicate(timeout=60)[0].strip().splitlines()[-1]) for p in procs]
     assert all(o[0][0] == 0 for o in outs)
     d = bench.sup_dir()
@@ -124,3 +127,28 @@ def test_isa_lint_for_the_cross_block_store_hazard():
         pytest.skip("second tier: set GNNAGG_TEST_TIER=2 (make -C gnn_computing_amd/csrc lint)")
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "gnn_computing_amd", "csrc"), "lint"], capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0 and "0 suspicious place(s)" in r.stdout and "0 violation(s)" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_dump_outputs_undoes_the_reorder_and_keeps_to_its_budget(tmp_path):
+    """--dump-outputs: a fixed seeded sample of the output rows in the ORIGINAL row numbering (the locality reorder's permutation undone),
+    float32 rows + float64 row ids, the same rows on every call, and never more than 64 MB however wide a row is."""
+    sys.path.insert(0, ROOT)
+    import torch
+    import bench
+    bench.np, bench.torch = np, torch
+    rng = np.random.default_rng(5)
+    V, F = 5000, 16
+    y_orig = rng.standard_normal((V, F)).astype(np.float32)
+    rows = rng.permutation(V)                 # entry i = original row at position i
+    y_new = torch.from_numpy(y_orig[rows])    # what a step over the reordered graph leaves
+    bench.dump_outputs(str(tmp_path / "a"), y_new, rows)
+    bench.dump_outputs(str(tmp_path / "b"), torch.from_numpy(y_orig), None)
+    for d in ("a", "b"):
+        got, ids = np.load(tmp_path / d / "y.npy"), np.load(tmp_path / d / "y_rows.npy")
+        assert got.dtype == np.float32 and ids.dtype == np.float64 and got.shape == (V, F) and np.all(np.diff(ids) > 0)
+        assert np.array_equal(got, y_orig[ids.astype(np.int64)])
+    wide = torch.zeros((70000, 602))
+    bench.dump_outputs(str(tmp_path / "w"), wide, None, first_row=100, name="y_rank0")
+    sizes = sum(os.path.getsize(tmp_path / "w" / f) for f in os.listdir(tmp_path / "w"))
+    ids = np.load(tmp_path / "w" / "y_rank0_rows.npy")
+    assert sizes <= 64 << 20 and ids.min() >= 100 and len(ids) == np.load(tmp_path / "w" / "y_rank0.npy").shape[0]

@@ -1,7 +1,8 @@
 """bench.py's output contract, exercised the way the driver runs it (one JSON line on stdout, the fields the round's
 instructions name, roofline.frac tied to a hardware peak, the oracle check inside bench.py passing) -- short runs of the
-headline line, of one other config, and of the N > 1 code paths (weak arxiv-shaped line, strong products-shaped --config P) with
-two ranks sharing the GPU over gloo (test hooks of bench.py)."""
+headline line (plain, and --full with everything it measures), of one other config, and of the N > 1 code paths (weak arxiv-shaped
+line, strong products-shaped --config P) with two ranks sharing the GPU over gloo (test hooks of bench.py).  --dump-outputs is
+checked against the oracle on the rows it wrote."""
 import json
 import os
 import subprocess
@@ -71,9 +72,49 @@ def check_common(d, n_gpus, steps, warmup):
     assert d["value"] > 0 and abs(d["value"] - d["config"]["num_e"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.05 or n_gpus > 1
 
 
-def test_headline_line():
-    d = run(["--steps", "20", "--warmup", "3", "--cpu-budget", "1"])
+def check_dump(dirname):
+    """What --dump-outputs wrote for the headline: sampled rows of Y in the generator's row numbering, inside the 1e-5 bound of the
+    oracle's CSR-order chain over the same rows of the same seeded input (the balanced order associates differently)."""
+    import numpy as np
+    import gnn_computing_amd as gnc
+    from oracle import oracle as orc
+    got, ids = np.load(os.path.join(dirname, "y.npy")), np.load(os.path.join(dirname, "y_rows.npy"))
+    assert got.dtype == np.float32 and ids.dtype == np.float64 and got.shape == (len(ids), 128) and len(ids) == 65536
+    assert sum(os.path.getsize(os.path.join(dirname, f)) for f in os.listdir(dirname)) <= 64 << 20
+    ptr_t, idx_t = gnc.graph.dataset("arxiv")
+    ptr, idx = ptr_t.numpy(), idx_t.numpy()
+    x = np.random.default_rng(123).standard_normal((len(ptr) - 1, 128), dtype=np.float32)   # bench.py's input
+    rows = ids.astype(np.int64)
+    sp = np.zeros(len(rows) + 1, np.int32)
+    sp[1:] = np.cumsum(ptr[rows + 1] - ptr[rows])
+    si = np.concatenate([idx[ptr[r]:ptr[r + 1]] for r in rows]).astype(np.int32)
+    val = np.ones(len(si), np.float32)
+    ref, scale = orc.gcn_seq(sp, si, val, x), orc.gcn_abs_scale(sp, si, val, x)
+    assert np.all(np.abs(got - ref) <= 1e-5 * scale + 1e-30)
+    return got
+
+
+def test_plain_headline_line(tmp_path):
+    """A plain run (no --full) times the headline arm only: the line keeps what the driver reads (value, ms_per_step, the counter-traffic
+    roofline of committed profiles) and carries nothing that needs a launch of its own; --dump-outputs writes the timed step's output."""
+    import time
+    t0 = time.time()
+    d = run(["--gpus", "1", "--steps", "20", "--warmup", "3", "--dump-outputs", str(tmp_path / "out")])
+    wall = time.time() - t0
     check_common(d, 1, 20, 3)
+    assert d["full"] is False and d["config"]["num_e"] == 1166243 and d["config"]["feat"] == 128
+    assert not {"configs", "cpu_baseline", "no_reorder", "reorder_minhash_clusters"} & set(d)
+    assert "ceiling_probe_us" not in d["roofline"] and d["roofline"]["algorithmic_bytes"] == 693827352
+    assert d["summary"]["verified"] is None and d["summary"]["A"][3] == 0
+    assert wall - 23 * d["ms_per_step"] * 1e-3 < 60, wall   # setup, warm-up and exit: seconds, not a sweep
+    check_dump(str(tmp_path / "out"))
+
+
+def test_headline_line(tmp_path):
+    d = run(["--steps", "20", "--warmup", "3", "--cpu-budget", "1", "--full", "--dump-outputs", str(tmp_path / "out")])
+    check_common(d, 1, 20, 3)
+    assert d["full"] is True
+    check_dump(str(tmp_path / "out"))
     assert d["metric"].startswith("aggregated edges/sec") and d["config"]["num_v"] == 169343 and d["config"]["num_e"] == 1166243
     assert d["config"]["feat"] == 128
     r = d["roofline"]
