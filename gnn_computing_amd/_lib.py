@@ -15,6 +15,7 @@ REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
 MODE_ROWS, MODE_SCHEDULED, MODE_BALANCED = 0, 1, 2
 FLAG_ACCUMULATE = 1
 FLAG_RELU = 2
+DTYPE_F32, DTYPE_BF16 = 0, 1
 
 c_int, c_float, c_void_p, c_char_p, c_int64 = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p,
                                                 ctypes.c_int64)
@@ -57,6 +58,7 @@ SIGNATURES = {
     "gnnagg_get_schedule": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gnnagg_gcn_run": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_int, c_int]),
     "gnnagg_gcn_run_ex": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
+    "gnnagg_gcn_run_typed": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "gnnagg_gcn_probe_gather": (c_int, [c_int64, c_void_p, c_int, c_int]),
     "gnnagg_gat_probe_gather": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_int, c_int]),
     "gnnagg_probe_row_gather": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p]),

@@ -31,6 +31,16 @@ class Schedule(enum.IntEnum):
 
 REDUCE = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX}
 MODE = {"rows": _lib.MODE_ROWS, "scheduled": _lib.MODE_SCHEDULED, "balanced": _lib.MODE_BALANCED}
+FEATURE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}   # gnnagg_gcn_run_typed
+
+
+def _feat_dtype(t, name):
+    """GNNAGG_DTYPE_* of a GCN feature tensor; raises TypeError for anything but float32 / bfloat16, before any device work"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype not in FEATURE_DTYPES:
+        raise TypeError("%s must be torch.float32 or torch.bfloat16, got %s" % (name, t.dtype))
+    return FEATURE_DTYPES[t.dtype]
 
 
 def _dev_ptr(t, dtype, name):
@@ -193,14 +203,20 @@ class Aggregator_GCN(Aggregator):
         return self.run_with_feat(vin, vout, BLOCK_SIZE, scheduled, int(vin.shape[1]), reduce, accumulate, relu)
 
     def run_with_feat(self, vin, vout, BLOCK_SIZE, scheduled, feat, reduce="sum", accumulate=False, relu=False):
-        """aggr_gcn.h:411-444"""
+        """aggr_gcn.h:411-444.  vin / vout: torch.float32 or torch.bfloat16 (extension, gnnagg_gcn_run_typed): the accumulation
+        stays fp32, a bfloat16 vout is one round-to-nearest-even of the fp32 result; float32 / float32 is gnnagg_gcn_run_ex."""
+        xt, yt = _feat_dtype(vin, "vin"), _feat_dtype(vout, "vout")
         if vout.numel() < self.num_v * feat:
             raise ValueError("vout must hold num_v * feat floats")
         self.feat_in = feat
+        flags = (_lib.FLAG_ACCUMULATE if accumulate else 0) | (_lib.FLAG_RELU if relu else 0)
         self._use_current_stream()
-        check(lib().gnnagg_gcn_run_ex(self._h, _dev_ptr(vin, torch.float32, "vin"), _dev_ptr(vout, torch.float32, "vout"),
-                                      int(feat), _mode(scheduled), REDUCE[reduce],
-                                      (_lib.FLAG_ACCUMULATE if accumulate else 0) | (_lib.FLAG_RELU if relu else 0)))
+        if xt == _lib.DTYPE_F32 and yt == _lib.DTYPE_F32:
+            check(lib().gnnagg_gcn_run_ex(self._h, _dev_ptr(vin, torch.float32, "vin"), _dev_ptr(vout, torch.float32, "vout"),
+                                          int(feat), _mode(scheduled), REDUCE[reduce], flags))
+        else:
+            check(lib().gnnagg_gcn_run_typed(self._h, _dev_ptr(vin, vin.dtype, "vin"), xt, _dev_ptr(vout, vout.dtype, "vout"), yt,
+                                             int(feat), _mode(scheduled), REDUCE[reduce], flags))
         return 0.0
 
     def probe_gather(self, vin, scheduled="balanced"):

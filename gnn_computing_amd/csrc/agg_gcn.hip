@@ -101,6 +101,7 @@ struct PlanArgs {
     int relu;        // 1: y = max(result, 0)
     int wt;          // 1: write-through (sc1) stores of the short-row results
     unsigned ybytes;
+    int y_bf16;      // typed launches (TYPED = true): Y holds bf16, else fp32; yvec is then Y's alignment class in its own elements
     // hubs (rows with several segments) folded by the last segment workgroup to arrive; hub_count == nullptr: k_combine
     const int *slot_hub, *mrow_ptr, *mrow_id, *row_ptr;
     int *hub_count;
@@ -164,8 +165,9 @@ __device__ __forceinline__ unsigned probe_edges(int beg, int end, int lane, bool
 // the store has completed the workgroup bumps the hub's arrival counter, and the workgroup that finds all other
 // segments already in folds the scratch rows in ascending slot order (device-scope loads; the order of k_combine --
 // so which workgroup arrives last does not matter) and writes the row.  Returns true in that workgroup, with the
-// finished row in acc (group 0's lanes).  `stage` = the segment's LDS stage (kSegChunks rows), free by now.
-template <int VEC, int GROUP, bool IS_MAX>
+// finished row in acc (group 0's lanes).  `stage` = the segment's LDS stage (kSegChunks rows), free by now.  TYPED: the row is
+// stored as a typed launch's Y (store_y_typed); scratch and fold stay fp32.
+template <int VEC, int GROUP, bool IS_MAX, bool TYPED = false>
 __device__ __forceinline__ bool hub_arrive_and_fold(const PlanArgs &a, const int4 d, int tile, int col, bool col_ok, int grp,
                                                     int lane, float (&acc)[VEC], float *stage, int &row_out)
 {
@@ -223,8 +225,9 @@ __device__ __forceinline__ bool hub_arrive_and_fold(const PlanArgs &a, const int
     }
     if (grp == 0 && col_ok) {
         finish_gcn_row<VEC, IS_MAX>(acc, a.mean ? a.row_ptr[row + 1] - a.row_ptr[row] : 1, row, a.y + (size_t)row * F + col, a.mean,
-                                    a.accumulate, a.relu, a.row_aux);
-        store_pack<VEC>(a.y + (size_t)row * F + col, acc);
+                                    a.accumulate, a.relu, a.row_aux, TYPED ? a.yvec : VEC);
+        if constexpr (TYPED) store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)row * F + col, acc);
+        else store_pack<VEC>(a.y + (size_t)row * F + col, acc);
     }
     return true;
 }
@@ -238,9 +241,13 @@ __device__ __forceinline__ bool hub_arrive_and_fold(const PlanArgs &a, const int
 // of the balanced / scheduled orders: 59 instead of 76 VGPRs, 8 instead of 6 waves per SIMD -- the arxiv-shaped headline
 // with the locality reorder 77.9 -> 74.0 us (without reorder, and at F = 100: unchanged); the canonical rows mode keeps 8
 // (its chains are long: 182 -> 209 us with 4), and so do the narrow geometries (F = 32 balanced: 28.6 -> 36.3 us with 4).
-template <int VEC, int GROUP, bool IS_MAX, bool PROBE = false, int UNROLL = kUnroll>
+// TX / TYPED (gnnagg_gcn_run_typed): X holds elements of type TX (__bf16: lanes of VEC 16-bit elements, widened in registers);
+// TYPED = true stores Y through store_y_typed (a.y_bf16, a.yvec).  Chains, LDS stage, partial rows and hub fold stay fp32, so a bf16 X
+// gives bit for bit the fp32 run on X widened.  The defaults are the fp32 kernel, instruction for instruction.
+template <int VEC, int GROUP, bool IS_MAX, bool PROBE = false, int UNROLL = kUnroll, typename TX = float, bool TYPED = false>
 __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(const PlanArgs a)
 {
+    static_assert(TYPED || std::is_same<TX, float>::value, "16-bit X needs the typed store");
     constexpr int GPB = block_of<GROUP>() / GROUP;
     const int F = a.feat;
     const int lane = threadIdx.x & (GROUP - 1);
@@ -273,7 +280,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
             for (int k = 0; k < VEC; ++k) acc[k] = IS_MAX ? -INFINITY : 0.0f;
             const int cb = d.x + c * a.chunk;
             const int ce = cb + a.chunk < d.y ? cb + a.chunk : d.y;
-            chain_edges<VEC, GROUP, IS_MAX, UNROLL>(acc, cb, ce, lane, col_ok, a.idx, a.val, a.x + col, F);
+            chain_edges<VEC, GROUP, IS_MAX, UNROLL, TX>(acc, cb, ce, lane, col_ok, a.idx, a.val, reinterpret_cast<const TX *>(a.x) + col, F);
             store_pack<VEC>(&stage[(c * GROUP + lane) * VEC], acc);
         }
         __syncthreads();
@@ -296,10 +303,12 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
         }
         if (hub_here) {
             int row;
-            hub_arrive_and_fold<VEC, GROUP, IS_MAX>(a, d, tile, col, col_ok, grp, lane, acc, stage, row);
+            hub_arrive_and_fold<VEC, GROUP, IS_MAX, TYPED>(a, d, tile, col, col_ok, grp, lane, acc, stage, row);
         } else if (d.z >= 0) {
-            finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, d.z, a.y + (size_t)d.z * F + col, a.mean, a.accumulate, a.relu, a.row_aux);
-            store_pack<VEC>(a.y + (size_t)d.z * F + col, acc);
+            finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, d.z, a.y + (size_t)d.z * F + col, a.mean, a.accumulate, a.relu, a.row_aux,
+                                        TYPED ? a.yvec : VEC);
+            if constexpr (TYPED) store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)d.z * F + col, acc);
+            else store_pack<VEC>(a.y + (size_t)d.z * F + col, acc);
         } else {
             store_pack<VEC>(a.partial + (size_t)(~d.z) * F + col, acc);
         }
@@ -314,7 +323,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
     const int col = (tile * GROUP + lane) * VEC;
     const bool col_ok = col < F;
     const int4 d = a.t0[item];
-    const float *__restrict__ xcol = a.x + (size_t)tile * a.x_tile_stride + lane * VEC;
+    const TX *__restrict__ xcol = reinterpret_cast<const TX *>(a.x) + (size_t)tile * a.x_tile_stride + lane * VEC;
     if constexpr (PROBE) {
         const unsigned sig = probe_edges<VEC, GROUP, UNROLL>(d.x, d.y, lane, col_ok, a.idx, a.val, xcol, a.xpitch);
         if (sig == 0x9e3779b9u) a.probe_sink[0] = sig;
@@ -324,7 +333,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
     float acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = IS_MAX ? -INFINITY : 0.0f;
-    chain_edges<VEC, GROUP, IS_MAX, UNROLL>(acc, d.x, d.y, lane, col_ok, a.idx, a.val, xcol, a.xpitch);
+    chain_edges<VEC, GROUP, IS_MAX, UNROLL, TX>(acc, d.x, d.y, lane, col_ok, a.idx, a.val, xcol, a.xpitch);
     if (!col_ok) return;
     if (d.z < 0) {  // one of several groups of its row (source-partitioned order): raw partial to its scratch slot
         // write-through when a descriptor can cover the tile: the partials are read back by k_combine only, and must not
@@ -337,11 +346,13 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
     if (d.x == d.y) {  // no edges: 0 (an accumulating run that comes here applies the ReLU to what the row holds)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
-        finish_gcn_row<VEC, false>(acc, 1, d.z, a.y + (size_t)d.z * F + col, 0, a.accumulate, a.relu, nullptr);
+        finish_gcn_row<VEC, false>(acc, 1, d.z, a.y + (size_t)d.z * F + col, 0, a.accumulate, a.relu, nullptr, TYPED ? a.yvec : VEC);
     } else {
-        finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, d.z, a.y + (size_t)d.z * F + col, a.mean, a.accumulate, a.relu, a.row_aux);
+        finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, d.z, a.y + (size_t)d.z * F + col, a.mean, a.accumulate, a.relu, a.row_aux,
+                                    TYPED ? a.yvec : VEC);
     }
-    if (a.yvec < VEC || F - col < VEC) store_pack_any<VEC>(a.y + (size_t)d.z * F + col, acc, F - col, a.yvec);
+    if constexpr (TYPED) store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, a.wt, a.ybytes, (size_t)d.z * F + col, acc);
+    else if (a.yvec < VEC || F - col < VEC) store_pack_any<VEC>(a.y + (size_t)d.z * F + col, acc, F - col, a.yvec);
     else if (a.wt) store_pack_wt<VEC>(a.y, a.ybytes, (size_t)d.z * F + col, acc);
     else store_pack<VEC>(a.y + (size_t)d.z * F + col, acc);
 }
@@ -859,9 +870,10 @@ __global__ __launch_bounds__(BLOCK) void k_gcn_rows_long(const RowsLongArgs a)
     }
 }
 
+// y_bf16: a typed launch's bf16 Y (k_combine<..., TYPED>: 64-lane groups of g.vec fp32 lanes, see launch_gcn_plan)
 static int launch_combine_gcn(const GcnLaunch &L, const Geometry &g, bool is_max, hipStream_t stream,
                               const float *nn_weight = nullptr, float *nn_out = nullptr, int nn_cols = 0,
-                              const TileSpec *tile = nullptr)
+                              const TileSpec *tile = nullptr, bool y_bf16 = false)
 {
     if (L.wl.n_mrows > 0) {
         CombineArgs c;
@@ -871,7 +883,7 @@ static int launch_combine_gcn(const GcnLaunch &L, const Geometry &g, bool is_max
         c.heads = 1; c.dhead = L.feat; c.mean = L.reduce == GNNAGG_REDUCE_MEAN;
         c.accumulate = L.accumulate; c.relu = L.relu; c.row_aux = L.row_aux;
         c.nn_weight = nn_weight; c.nn_out = nn_out; c.nn_cols = nn_cols;
-        c.big_rows = L.wl.big_rows; c.n_big = L.wl.n_big;
+        c.big_rows = L.wl.big_rows; c.n_big = L.wl.n_big; c.y_bf16 = y_bf16 ? 1 : 0;
         c.nblocks_small = ceil_div(c.n_mrows, kBlock / g.group) * g.ntiles;
         const int nb_big = c.n_big * g.ntiles;
 #define CALL_COMB                                                                                           \
@@ -881,7 +893,20 @@ static int launch_combine_gcn(const GcnLaunch &L, const Geometry &g, bool is_max
             if (is_max) hipLaunchKernelGGL((k_combine<VEC, GROUP, true, false, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);  \
             else        hipLaunchKernelGGL((k_combine<VEC, GROUP, false, false, true>), dim3(nb_big), dim3(kBlock), 0, stream, c); \
         }
-        DISPATCH_GEOM(g, CALL_COMB)
+#define CALL_COMB_BF16(V)                                                                                   \
+        if (is_max) hipLaunchKernelGGL((k_combine<V, 64, true, false, false, true>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);  \
+        else        hipLaunchKernelGGL((k_combine<V, 64, false, false, false, true>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c); \
+        if (nb_big > 0) {                                                                                   \
+            if (is_max) hipLaunchKernelGGL((k_combine<V, 64, true, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);  \
+            else        hipLaunchKernelGGL((k_combine<V, 64, false, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c); \
+        }
+        if (y_bf16) {
+            if (g.group != 64 || nn_weight || tile) return fail(GNNAGG_ERR_STATE, "internal: bf16 combine geometry");
+            if (g.vec == 4) { CALL_COMB_BF16(4) } else if (g.vec == 2) { CALL_COMB_BF16(2) } else { CALL_COMB_BF16(1) }
+        } else {
+            DISPATCH_GEOM(g, CALL_COMB)
+        }
+#undef CALL_COMB_BF16
 #undef CALL_COMB
         HIP_TRY(hipGetLastError());
     }
@@ -903,22 +928,91 @@ int launch_dense_rows(const int *rows, int n_rows, const float *Y, const float *
 // geometry of a 2-D blocked launch: 16-byte lanes over tiles of tile_w floats
 static Geometry tile_geometry(const TileSpec &t, int feat) { return {4, t.tile_w / 4, (feat + t.tile_w - 1) / t.tile_w}; }
 
+// ---- typed launches (gnnagg_gcn_run_typed)
+// Alignment class of rows of F elements of `esize` bytes at p: the largest v <= maxvec with F % v == 0 and p aligned to v elements.
+static int align_class(int F, const void *p, int esize, int maxvec)
+{
+    int v = maxvec;
+    while (v > 1 && (F % v != 0 || (uintptr_t)p % ((uintptr_t)v * esize) != 0)) v >>= 1;
+    return v;
+}
+#ifndef GNNAGG_TYPED_LANE_BYTES   // A/B switch (measurement builds only): the widest lane of a typed launch
+#define GNNAGG_TYPED_LANE_BYTES 16
+#endif
+// Lanes as wide as F and X's alignment allow, up to 16 bytes: 8 bf16 elements (F = 128 -> 16-lane groups reading 256-byte rows), 8-,
+// 4- or 2-byte lanes where F or the alignment forces them.  Y's alignment class is set apart (PlanArgs::yvec): a fp32 Y row is twice
+// as wide as the bf16 row a lane reads.  The fp32 partial rows live in scratch the library allocates, aligned for any lane.
+static Geometry typed_geometry(int F, const void *x, int xsize)
+{
+    const int vec = align_class(F, x, xsize, GNNAGG_TYPED_LANE_BYTES / xsize);
+    const int lanes = (F + vec - 1) / vec;
+    int group = 8;
+    while (group < 64 && group < lanes) group <<= 1;
+    return {vec, group, (lanes + group - 1) / group};
+}
+
+// DISPATCH_GEOM plus the 16-byte lanes of 16-bit X (8 elements)
+#define DISPATCH_GEOM_16BIT(g, KERNEL_CALL)                                      \
+    switch ((g).vec * 100 + (g).group) {                                         \
+        case 108: { constexpr int VEC = 1, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 116: { constexpr int VEC = 1, GROUP = 16; KERNEL_CALL; } break;     \
+        case 132: { constexpr int VEC = 1, GROUP = 32; KERNEL_CALL; } break;     \
+        case 164: { constexpr int VEC = 1, GROUP = 64; KERNEL_CALL; } break;     \
+        case 208: { constexpr int VEC = 2, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 216: { constexpr int VEC = 2, GROUP = 16; KERNEL_CALL; } break;     \
+        case 232: { constexpr int VEC = 2, GROUP = 32; KERNEL_CALL; } break;     \
+        case 264: { constexpr int VEC = 2, GROUP = 64; KERNEL_CALL; } break;     \
+        case 408: { constexpr int VEC = 4, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 416: { constexpr int VEC = 4, GROUP = 16; KERNEL_CALL; } break;     \
+        case 432: { constexpr int VEC = 4, GROUP = 32; KERNEL_CALL; } break;     \
+        case 464: { constexpr int VEC = 4, GROUP = 64; KERNEL_CALL; } break;     \
+        case 808: { constexpr int VEC = 8, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 816: { constexpr int VEC = 8, GROUP = 16; KERNEL_CALL; } break;     \
+        case 832: { constexpr int VEC = 8, GROUP = 32; KERNEL_CALL; } break;     \
+        case 864: { constexpr int VEC = 8, GROUP = 64; KERNEL_CALL; } break;     \
+        default: return fail(GNNAGG_ERR_ARG, "unsupported lane geometry");       \
+    }
+
+// One typed launch of k_gcn_plan.  4 gathers per batch (u4) where the fp32 rule's reason holds -- 16-byte lanes in groups of 32 or 64
+// lanes, the geometries whose 8-gather batches cost two waves per SIMD -- so in bf16 from F = 136 on; F = 128 (16-lane groups) keeps 8.
+template <int VEC, int GROUP, typename TX>
+static void launch_plan_typed(const PlanArgs &a, bool is_max, bool u4, int grid, int blk, hipStream_t stream)
+{
+    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= 32) {
+        if (u4) {
+            if (is_max) hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+            else        hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+            return;
+        }
+    }
+    if (is_max) hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+    else        hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+}
+
 int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
     if (L.feat <= 0) return fail(GNNAGG_ERR_ARG, "feature length must be >= 1");
     if (L.tile.on && (L.n1 > 0 || L.accumulate)) return fail(GNNAGG_ERR_STATE, "internal: tiled launch with segments");
-    const Geometry g = L.tile.on ? tile_geometry(L.tile, L.feat) : pick_geometry(L.feat, L.x, L.y, L.partial, L.feat);
+    const bool typed = L.x_dtype != GNNAGG_DTYPE_F32 || L.y_dtype != GNNAGG_DTYPE_F32;
+    if (typed && (L.tile.on || L.probe || L.nn_weight || L.t0_partials))
+        return fail(GNNAGG_ERR_STATE, "internal: typed launch on a path without 16-bit forms");
+    const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
+    const Geometry g = L.tile.on ? tile_geometry(L.tile, L.feat)
+                       : typed   ? typed_geometry(L.feat, L.x, xsize)
+                                 : pick_geometry(L.feat, L.x, L.y, L.partial, L.feat);
     const bool is_max = L.reduce == GNNAGG_REDUCE_MAX;
     PlanArgs a;
     a.t0 = reinterpret_cast<const int4 *>(L.t0); a.t1 = reinterpret_cast<const int4 *>(L.t1);
-    a.idx = L.idx; a.val = L.val; a.x = L.x; a.y = L.y; a.partial = L.partial;
+    a.idx = L.idx; a.val = L.val; a.x = static_cast<const float *>(L.x); a.y = static_cast<float *>(L.y); a.partial = L.partial;
     a.n0 = L.n0; a.n1 = L.n1; a.feat = L.feat; a.ntiles = g.ntiles; a.chunk = L.chunk;
     a.mean = L.reduce == GNNAGG_REDUCE_MEAN; a.remap = L.xcd_remap; a.accumulate = L.accumulate; a.relu = L.relu;
     a.row_aux = L.row_aux;
     a.slot_hub = L.slot_hub; a.mrow_ptr = L.hubs.mrow_ptr; a.mrow_id = L.hubs.mrow_id; a.row_ptr = L.row_ptr;
     a.hub_count = L.hub_count; a.hub_count_stride = L.hub_count_stride; a.partial_bytes = 0;
-    a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec; a.yvec = g.vec;
+    a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec;
+    a.yvec = typed ? align_class(L.feat, L.y, ysize, g.vec) : g.vec;
+    a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
     a.tile_major = 0; a.item_blocks = 0; a.ptile_bytes = 0; a.probe_sink = nullptr;
     if (L.tile.on) {
         a.xpitch = L.tile.xpitch; a.x_tile_stride = L.tile.x_tile_stride; a.ppitch = L.tile.ppitch;
@@ -933,8 +1027,10 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
     }
     const bool hubs_in_kernel = a.hub_count != nullptr;
     {
-        const size_t ybytes = (size_t)L.num_rows * L.feat * sizeof(float);
-        a.wt = (!L.accumulate && ybytes < 0x7fffffffULL) ? 1 : 0;
+        const size_t ybytes = (size_t)L.num_rows * L.feat * ysize;
+        // (typed: not where a lane's Y piece is wider than one 16-byte store -- bf16 X, fp32 Y: each store instruction then writes every
+        // other 16 bytes, half lines that write-through sends on as partial writes; the L2 merges them when it holds the lines)
+        a.wt = (!L.accumulate && ybytes < 0x7fffffffULL && g.vec * ysize <= 16) ? 1 : 0;
         a.ybytes = (unsigned)ybytes;
     }
     // dense combine fused as the epilogue when one lane group spans the row and the [32][K] tile fits LDS
@@ -958,6 +1054,28 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
         else grid0 = 8 * fill_xcd_ranges(L.t0_cost_prefix, a.n0, gpb, item_blocks, a.xr) * g.ntiles;
     }
     const int grid = a.n1 * g.ntiles + grid0;
+    if (typed) {
+        if (grid > 0) {
+            const bool u4t = L.unroll == 4 && g.vec * xsize == 16 && g.group >= 32;
+#define CALL_TYPED(TXT) launch_plan_typed<VEC, GROUP, TXT>(a, is_max, u4t, grid, blk, stream)
+            if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+                DISPATCH_GEOM_16BIT(g, CALL_TYPED(__bf16))
+            } else {
+                DISPATCH_GEOM(g, CALL_TYPED(float))
+            }
+#undef CALL_TYPED
+            HIP_TRY(hipGetLastError());
+        }
+        if (hubs_in_kernel) return GNNAGG_OK;
+        // hubs the kernel does not fold: the ordered combine of their fp32 partial rows, on fp32 lanes of its own (the partial rows are
+        // [slot][F]: any column tiling reads them), storing Y in its type
+        GcnLaunch C;
+        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
+        C.accumulate = L.accumulate; C.relu = L.relu; C.row_aux = L.row_aux;
+        if (L.y_dtype == GNNAGG_DTYPE_F32) return launch_combine_gcn(C, pick_geometry(L.feat, L.partial, L.y, nullptr, L.feat), is_max, stream);
+        const int cv = align_class(L.feat, L.y, ysize, 4);
+        return launch_combine_gcn(C, Geometry{cv, 64, ceil_div(L.feat, 64 * cv)}, is_max, stream, nullptr, nullptr, 0, nullptr, true);
+    }
     if (L.probe) {
         if (is_max) return fail(GNNAGG_ERR_ARG, "probe: sum/mean only");
         a.probe_sink = device_probe_sink();
@@ -984,7 +1102,7 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
             HIP_TRY(hipGetLastError());
         }
         GcnLaunch C;
-        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = L.y; C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
+        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
         if (hubs_in_kernel) return GNNAGG_OK;
         return launch_combine_gcn(C, g, is_max, stream, L.nn_weight, L.nn_out, L.nn_cols);  // hubs: product in the combine
     }
@@ -1003,11 +1121,11 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
         HIP_TRY(hipGetLastError());
     }
     GcnLaunch C;
-    C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = L.y; C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
+    C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
     C.accumulate = L.accumulate; C.relu = L.relu; C.row_aux = L.row_aux;
     const int rc = hubs_in_kernel ? GNNAGG_OK : launch_combine_gcn(C, g, is_max, stream, nullptr, nullptr, 0, &L.tile);
     if (rc || !want_nn) return rc;
-    return launch_dense_nn(L.y, L.nn_weight, L.nn_out, L.num_rows, L.nn_cols, L.feat, stream);
+    return launch_dense_nn(static_cast<const float *>(L.y), L.nn_weight, L.nn_out, L.num_rows, L.nn_cols, L.feat, stream);
 }
 
 int launch_gcn_rows_long(const GcnRowsLongLaunch &L, void *stream_v)

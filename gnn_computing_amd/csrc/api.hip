@@ -274,7 +274,11 @@ static int build_balanced_plan_keep(Ctx *c) { return build_plan_into(c, c->plan,
 // similar degree should share a wavefront.  Sorting by degree inside windows of `sort_window` rows equalises them while
 // consecutive windows (and with them the XCD ranges) still follow the row order.  Measured on the arxiv-shaped input:
 // F=32 43.3 -> 36.8 us, F=64 51.6 -> 51.0 us; F=128 (2 rows per wavefront) gets slower, so it keeps the row order.
-static bool wants_sorted_rows(const Ctx *c, int feat) { return c->sort_window > 1 && feat <= 64; }
+// The rule is about rows per wavefront, i.e. ROW BYTES (16-byte lanes): fp32 F <= 64, bf16 F <= 128 (gnnagg_gcn_run_typed).
+#ifndef GNNAGG_SORT_ROW_BYTES   // A/B switch (measurement builds only)
+#define GNNAGG_SORT_ROW_BYTES 256
+#endif
+static bool wants_sorted_rows(const Ctx *c, long row_bytes) { return c->sort_window > 1 && row_bytes <= GNNAGG_SORT_ROW_BYTES; }
 
 static int ensure_sorted_rows(Ctx *c, BalancedPlan &p)
 {
@@ -1002,8 +1006,11 @@ static int run_rows_blocked_gat(Ctx *c, const float *x, const float *att, float 
     return GNNAGG_OK;
 }
 
-int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags, const NnRequest *nn, int probe)
+int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags, const NnRequest *nn, int probe, int x_dtype,
+            int y_dtype)
 {
+    const bool typed = x_dtype != GNNAGG_DTYPE_F32 || y_dtype != GNNAGG_DTYPE_F32;
+    if (typed && (nn || probe)) return fail(GNNAGG_ERR_ARG, "16-bit features: run_with_nn and the gather probe are fp32 only");
     if ((flags & GNNAGG_FLAG_ACCUMULATE) && (mode != GNNAGG_MODE_BALANCED || (reduce != GNNAGG_REDUCE_SUM && !c->row_aux) || !c->use_plan))
         return fail(GNNAGG_ERR_ARG, "GNNAGG_FLAG_ACCUMULATE needs GNNAGG_MODE_BALANCED and GNNAGG_REDUCE_SUM (mean / max: gnnagg_set_row_aux first)");
     // a row_aux array changes what mean / max compute (the row-partitioned step's two passes): the chunked plan kernel implements it
@@ -1026,21 +1033,29 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
     Schedule *s = nullptr;
     int rc = get_sched(c, mode, &s);
     if (rc) return rc;
-    const bool acc_on_partitioned = ((flags & GNNAGG_FLAG_ACCUMULATE) || aux_run) && c->partitions > 0;
-    if (acc_on_partitioned && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;  // y += A.x needs the plan kernel
-    if ((mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || acc_on_partitioned)) ||
-        (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid)) {
+    // y += A.x and 16-bit features need the plan kernel: on a handle on the 2-D blocked order they run the chunked plan, built beside it
+    const bool acc_on_partitioned = ((flags & GNNAGG_FLAG_ACCUMULATE) || aux_run || typed) && c->partitions > 0;
+    const bool on_plan = (mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || acc_on_partitioned)) ||
+                         (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid);
+    if (typed && !on_plan)
+        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gcn_run_typed (x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                                        (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
+                                        "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
+                                        "neighbor-grouping schedule / \"fast_scheduled\" = 1 for GNNAGG_MODE_SCHEDULED");
+    if (acc_on_partitioned && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
+    if (on_plan) {
         BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
         GcnPlanLaunch P;
         P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk;
         P.t0_cost_prefix = p.t0_cost_prefix.data();
-        if (wants_sorted_rows(c, feat)) {
+        if (wants_sorted_rows(c, (long)feat * (x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4))) {
             if ((rc = ensure_sorted_rows(c, p))) return rc;
             if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
         }
         P.hubs.mrow_id = p.mrow_id.p; P.hubs.mrow_ptr = p.mrow_ptr.p; P.hubs.n_mrows = p.n_mrows;
         P.hubs.n_slots = p.n_slots; P.hubs.big_rows = p.big_rows.p; P.hubs.n_big = p.n_big;
         P.row_ptr = c->d_ptr; P.idx = c->d_idx; P.val = c->d_val; P.x = x; P.y = y; P.feat = feat; P.reduce = reduce;
+        P.x_dtype = x_dtype; P.y_dtype = y_dtype;
         P.xcd_remap = c->xcd_remap; P.accumulate = (flags & GNNAGG_FLAG_ACCUMULATE) ? 1 : 0; P.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
         P.row_aux = aux_run ? c->row_aux : nullptr;
         P.num_rows = c->V;
@@ -1069,7 +1084,7 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
         if (!span_run && s->gpu_built) {   // the descriptor form is needed after all: the host builder makes both
             c->force_host_plan = 1;
             if ((rc = build_partitioned(c, c->partitions))) return rc;
-            return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe);
+            return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe, x_dtype, y_dtype);
         }
         if (span_run) {  // every group owns a partial row (slot = group index): sequential flushes
             tr.spec.p_tile_stride = (long)s->num_target * tr.spec.tile_w;
@@ -1077,7 +1092,7 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
         }
         bool demoted = false;
         if ((rc = reserve_partitioned_scratch(c, tr.partial_floats, 0, tr.xt_floats, &demoted))) return rc;
-        if (demoted) return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe);
+        if (demoted) return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe, x_dtype, y_dtype);
         if ((rc = refresh_partitioned_val(c, s))) return rc;
         if (span_run) {
             SpanLaunch S;
@@ -1215,7 +1230,7 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
         BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
         GatPlanLaunch P;
         P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk; P.t0_cost_prefix = p.t0_cost_prefix.data();
-        if (wants_sorted_rows(c, feat)) {
+        if (wants_sorted_rows(c, (long)feat * 4)) {
             if ((rc = ensure_sorted_rows(c, p))) return rc;
             if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
         }
@@ -1763,6 +1778,25 @@ int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, i
 {
     GET_CTX(h);
     return gcn_run(c, d_x, d_y, feat, mode, reduce, flags);
+}
+
+int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int mode, int reduce, int flags)
+{
+    GET_CTX(h);
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_typed: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32)
+        return gcn_run(c, static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags);
+    const std::string combo = std::string("x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                              (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32");
+    if ((flags & GNNAGG_FLAG_ACCUMULATE) && y_dtype != GNNAGG_DTYPE_F32)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_typed (" + combo + "): GNNAGG_FLAG_ACCUMULATE needs a fp32 y (the accumulation target stays fp32)");
+    if (c->kind == Ctx::GCN && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
+                                    "is fp32 only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
+    return gcn_run(c, static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, nullptr, 0, x_dtype, y_dtype);
 }
 
 int gnnagg_gcn_probe_gather(gnnagg_handle h, const float *d_x, int feat, int mode)

@@ -208,7 +208,10 @@ struct NnRequest {  // run_with_nn: transformed[V, cols] = y . weight[feat, cols
     float *out;
     int cols;
 };
-int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags = 0, const NnRequest *nn = nullptr, int probe = 0);
+// x_dtype / y_dtype (GNNAGG_DTYPE_*): what x / y hold.  16-bit types run on the plan kernel only (gnnagg_gcn_run_typed has validated the
+// call; an order that would leave the plan kernel returns GNNAGG_ERR_ARG)
+int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags = 0, const NnRequest *nn = nullptr, int probe = 0,
+            int x_dtype = GNNAGG_DTYPE_F32, int y_dtype = GNNAGG_DTYPE_F32);
 int edge_launch(Ctx *c, EdgeItemLaunch &L, int heads);
 int do_schedule(Ctx *c, int kind, const int *param, int total_v);
 int fetch_host_ptr(Ctx *c);

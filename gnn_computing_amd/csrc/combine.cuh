@@ -15,6 +15,7 @@ struct CombineArgs {
     const float *nn_weight;
     float *nn_out;
     int nn_cols;
+    int y_bf16 = 0;  // TYPED instantiations: Y holds bf16 (one rounding at the store), else fp32
     const float *partial;
     const float *partial_den;  // GAT only
     float *y;
@@ -39,7 +40,8 @@ static constexpr int kCombineStage = 128;  // partial rows a workgroup stages in
 // BIG = true: the workgroup-per-row path only (64 KB of LDS staging), launched over the rows of big_rows; BIG = false: the
 // lane-group path only, with 4 KB of LDS (the two used to be one kernel, and the staging array capped the lane-group path
 // at two workgroups per CU -- it now runs for every row of the source-partitioned mode).
-template <int VEC, int GROUP, bool IS_MAX, bool IS_GAT, bool BIG>
+// TYPED (GCN, typed launches whose hubs this kernel finishes): Y's element type is a.y_bf16 (store_y_typed); partials stay fp32.
+template <int VEC, int GROUP, bool IS_MAX, bool IS_GAT, bool BIG, bool TYPED = false>
 __global__ __launch_bounds__(kBlock) void k_combine(const CombineArgs a)
 {
     constexpr int ITEMS = kBlock / GROUP;
@@ -110,7 +112,12 @@ __global__ __launch_bounds__(kBlock) void k_combine(const CombineArgs a)
                                           a.accumulate, a.relu, a.row_aux);
                 acc = one[0];
             }
-            a.y[(size_t)row * F + col0 + c] = acc;
+            if constexpr (TYPED) {
+                const float one[1] = {acc};
+                store_y_typed<1>(a.y, a.y_bf16, 1, 0, 0, (size_t)row * F + col0 + c, one);
+            } else {
+                a.y[(size_t)row * F + col0 + c] = acc;
+            }
             if (nn) stage[c] = acc;  // the staging rounds are over
         }
         if (!nn) return;
@@ -180,7 +187,8 @@ __global__ __launch_bounds__(kBlock) void k_combine(const CombineArgs a)
             finish_gcn_row<VEC, IS_MAX>(acc, a.mean ? a.row_ptr[row + 1] - a.row_ptr[row] : 1, row, a.y + (size_t)row * F + col, a.mean,
                                         a.accumulate, a.relu, a.row_aux);
         }
-        if (a.yvec < VEC || F - col < VEC) store_pack_any<VEC>(a.y + (size_t)row * F + col, acc, F - col, a.yvec);
+        if constexpr (TYPED) store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)row * F + col, acc);
+        else if (a.yvec < VEC || F - col < VEC) store_pack_any<VEC>(a.y + (size_t)row * F + col, acc, F - col, a.yvec);
         else store_pack<VEC>(a.y + (size_t)row * F + col, acc);
         if (nn) store_pack<VEC>(&stage[grp * GROUP * VEC + col], acc);  // ntiles == 1: col = lane * VEC
     }

@@ -101,8 +101,9 @@ struct GcnPlanLaunch {
     const int *row_ptr = nullptr;
     const int *idx = nullptr;
     const float *val = nullptr;
-    const float *x = nullptr;
-    float *y = nullptr;
+    const void *x = nullptr;   // elements of x_dtype
+    void *y = nullptr;         // elements of y_dtype
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;  // gnnagg_gcn_run_typed: 16-bit X / Y (fp32 chains, partials, fold)
     float *partial = nullptr;
     int feat = 0;
     int reduce = GNNAGG_REDUCE_SUM;

@@ -59,16 +59,45 @@ static constexpr int kUnroll = KUNROLL;
 static constexpr int kSegChunks = 16;  // chunks of a long row that one segment workgroup folds in LDS (plan kernels)
 
 // ---------------------------------------------------------------------------------- helpers
-template <int VEC>
+// VEC elements of a feature row as one lane loads them.  T = float: the values.  T = __bf16 (gnnagg_gcn_run_typed): the raw
+// 16-bit elements, two per word (element k in the low half of word k / 2 when k is even, the high half when odd), widened to
+// fp32 by at() where the chain consumes them -- exact: a bf16 value is the high half of its fp32 bit pattern.  Keeping the
+// loaded words instead of VEC widened floats holds the registers of the UNROLL gathers in flight at the fp32 path's count.
+template <int VEC, typename T = float>
 struct Pack {
     float v[VEC];
+    __device__ __forceinline__ float at(int k) const { return v[k]; }
+};
+template <int VEC>
+struct Pack<VEC, __bf16> {
+    unsigned w[(VEC + 1) / 2];
+    __device__ __forceinline__ float at(int k) const
+    {
+        return __uint_as_float((k & 1) ? (w[k >> 1] & 0xffff0000u) : (w[k >> 1] << 16));
+    }
 };
 
-template <int VEC>
-__device__ __forceinline__ Pack<VEC> load_pack(const float *p)
+template <int VEC, typename T = float>
+__device__ __forceinline__ Pack<VEC, T> load_pack(const T *p)
 {
-    Pack<VEC> r;
-    if constexpr (VEC == 4) {
+    Pack<VEC, T> r;
+    if constexpr (std::is_same<T, __bf16>::value) {  // 16-, 8-, 4- or 2-byte lanes
+        if constexpr (VEC == 8) {
+            const uint4 t = *reinterpret_cast<const uint4 *>(p);
+            r.w[0] = t.x; r.w[1] = t.y; r.w[2] = t.z; r.w[3] = t.w;
+        } else if constexpr (VEC == 4) {
+            const uint2 t = *reinterpret_cast<const uint2 *>(p);
+            r.w[0] = t.x; r.w[1] = t.y;
+        } else if constexpr (VEC == 2) {
+            r.w[0] = *reinterpret_cast<const unsigned *>(p);
+        } else {
+            r.w[0] = *reinterpret_cast<const unsigned short *>(p);
+        }
+    } else if constexpr (VEC == 8) {  // fp32 partial rows / LDS stage of a 16-byte bf16 lane
+        const float4 t0 = reinterpret_cast<const float4 *>(p)[0], t1 = reinterpret_cast<const float4 *>(p)[1];
+        r.v[0] = t0.x; r.v[1] = t0.y; r.v[2] = t0.z; r.v[3] = t0.w;
+        r.v[4] = t1.x; r.v[5] = t1.y; r.v[6] = t1.z; r.v[7] = t1.w;
+    } else if constexpr (VEC == 4) {
         const float4 t = *reinterpret_cast<const float4 *>(p);
         r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
     } else if constexpr (VEC == 2) {
@@ -92,7 +121,10 @@ __device__ __forceinline__ void relu_pack(float (&a)[VEC])
 template <int VEC>
 __device__ __forceinline__ void store_pack(float *p, const float (&a)[VEC])
 {
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 8) {
+        reinterpret_cast<float4 *>(p)[0] = make_float4(a[0], a[1], a[2], a[3]);
+        reinterpret_cast<float4 *>(p)[1] = make_float4(a[4], a[5], a[6], a[7]);
+    } else if constexpr (VEC == 4) {
         *reinterpret_cast<float4 *>(p) = make_float4(a[0], a[1], a[2], a[3]);
     } else if constexpr (VEC == 2) {
         *reinterpret_cast<float2 *>(p) = make_float2(a[0], a[1]);
@@ -105,9 +137,10 @@ __device__ __forceinline__ void store_pack(float *p, const float (&a)[VEC])
 // row_aux (gnnagg_set_row_aux; the row-partitioned step's two passes) changes two things: the mean divides by row_aux[row]
 // -- the row's degree in the WHOLE graph -- instead of the edges this handle holds, so that local and halo parts can be
 // added; and a max joins as max(old, new) only where row_aux[row] edges > 0 were already folded into y (else y = new).
+// yvec: alignment class of the fp32 Y rows (typed launches: a 16-byte bf16 lane spans 32 bytes of a fp32 row)
 template <int VEC, bool IS_MAX>
 __device__ __forceinline__ void finish_gcn_row(float (&acc)[VEC], int own_deg, int row, const float *yold, int mean, int accumulate,
-                                               int relu, const int *__restrict__ row_aux)
+                                               int relu, const int *__restrict__ row_aux, int yvec = VEC)
 {
     if (mean) {
         const float dg = (float)(row_aux ? row_aux[row] : own_deg);
@@ -117,7 +150,13 @@ __device__ __forceinline__ void finish_gcn_row(float (&acc)[VEC], int own_deg, i
         }
     }
     if (accumulate) {
-        const Pack<VEC> old = load_pack<VEC>(yold);
+        Pack<VEC> old;
+        if (yvec >= VEC) {
+            old = load_pack<VEC>(yold);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) old.v[k] = yold[k];
+        }
         if (IS_MAX) {
             if (!row_aux || row_aux[row] > 0) {
 #pragma unroll
@@ -169,7 +208,12 @@ __device__ __forceinline__ void store_pack_wt(float *ybase, unsigned nbytes, siz
     const int voff = (int)(yoff * sizeof(float));
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 8) {
+        u4 v0 = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
+        u4 v1 = {__float_as_uint(a[4]), __float_as_uint(a[5]), __float_as_uint(a[6]), __float_as_uint(a[7])};
+        __builtin_amdgcn_raw_buffer_store_b128(v0, rsrc, voff, 0, AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(v1, rsrc, voff + 16, 0, AUX);
+    } else if constexpr (VEC == 4) {
         u4 v = {__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])};
         __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, AUX);
     } else if constexpr (VEC == 2) {
@@ -187,7 +231,12 @@ __device__ __forceinline__ Pack<VEC> load_pack_sc1(const float *base, unsigned n
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)nbytes, 0x00020000);
     const int voff = (int)(off * sizeof(float));
     Pack<VEC> r;
-    if constexpr (VEC == 4) {
+    if constexpr (VEC == 8) {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        const u4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 16), v1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + 16, 0, 16);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { r.v[k] = __uint_as_float(v0[k]); r.v[4 + k] = __uint_as_float(v1[k]); }
+    } else if constexpr (VEC == 4) {
         typedef unsigned u4 __attribute__((ext_vector_type(4)));
         const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, 0, 16);
         r.v[0] = __uint_as_float(v[0]); r.v[1] = __uint_as_float(v[1]); r.v[2] = __uint_as_float(v[2]); r.v[3] = __uint_as_float(v[3]);
@@ -199,6 +248,99 @@ __device__ __forceinline__ Pack<VEC> load_pack_sc1(const float *base, unsigned n
         r.v[0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, 0, 16));
     }
     return r;
+}
+
+// ------------------------------------------------------------------ 16-bit outputs (gnnagg_gcn_run_typed)
+// fp32 -> bf16 with ONE round-to-nearest-even per element by a plain conversion: gfx950 compiles it to v_cvt_pk_bf16_f32 (two
+// results per instruction, RNE, NaNs kept -- integer rounding tricks lose them, MI355X_MICROARCH.md).
+__device__ __forceinline__ unsigned bf16x2_bits(float lo, float hi)
+{
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    const f2 f = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, b2));
+}
+
+// VEC results into a bf16 row; avec = the row's alignment class in elements (8 / 4 / 2 / 1: 16-, 8-, 4-, 2-byte aligned)
+template <int VEC>
+__device__ __forceinline__ void store_pack_bf16(__bf16 *p, const float (&a)[VEC], int avec)
+{
+    if constexpr (VEC == 1) {
+        *p = (__bf16)a[0];
+    } else {
+        unsigned w[VEC / 2];
+#pragma unroll
+        for (int k = 0; k < VEC / 2; ++k) w[k] = bf16x2_bits(a[2 * k], a[2 * k + 1]);
+        if (avec >= VEC) {
+            if constexpr (VEC == 8) *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+            else if constexpr (VEC == 4) *reinterpret_cast<uint2 *>(p) = make_uint2(w[0], w[1]);
+            else *reinterpret_cast<unsigned *>(p) = w[0];
+        } else if (avec >= 2) {
+#pragma unroll
+            for (int k = 0; k < VEC / 2; ++k) reinterpret_cast<unsigned *>(p)[k] = w[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC / 2; ++k) {
+                reinterpret_cast<unsigned short *>(p)[2 * k] = (unsigned short)w[k];
+                reinterpret_cast<unsigned short *>(p)[2 * k + 1] = (unsigned short)(w[k] >> 16);
+            }
+        }
+    }
+}
+
+// Write-through form (store_pack_wt) of a whole lane, VEC >= 2: `yoff` in elements from `ybase`
+template <int VEC, int AUX = GNNAGG_WT_AUX>
+__device__ __forceinline__ void store_pack_bf16_wt(__bf16 *ybase, unsigned nbytes, size_t yoff, const float (&a)[VEC])
+{
+    static_assert(VEC >= 2, "whole words only");
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ybase, 0, (int)nbytes, 0x00020000);
+    const int voff = (int)(yoff * sizeof(__bf16));
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    if constexpr (VEC == 8) {
+        u4 v = {bf16x2_bits(a[0], a[1]), bf16x2_bits(a[2], a[3]), bf16x2_bits(a[4], a[5]), bf16x2_bits(a[6], a[7])};
+        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, voff, 0, AUX);
+    } else if constexpr (VEC == 4) {
+        u2 v = {bf16x2_bits(a[0], a[1]), bf16x2_bits(a[2], a[3])};
+        __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, voff, 0, AUX);
+    } else {
+        __builtin_amdgcn_raw_buffer_store_b32(bf16x2_bits(a[0], a[1]), rsrc, voff, 0, AUX);
+    }
+}
+
+// Store of a finished row piece in a typed launch (k_gcn_plan / k_combine with TYPED = true).  Y's element type is a launch argument
+// -- one uniform branch per row piece instead of every kernel instantiated once more per output type -- and yvec is the alignment
+// class of Y's rows in elements of that type; wt: write-through (store_pack_wt) where the lane's store is whole.
+template <int VEC>
+__device__ __forceinline__ void store_y_typed(void *ybase, int y_bf16, int yvec, int wt, unsigned ybytes, size_t off, const float (&a)[VEC])
+{
+    if (y_bf16) {
+        __bf16 *y = static_cast<__bf16 *>(ybase);
+        if constexpr (VEC >= 2) {
+            if (wt && yvec >= VEC) {
+                store_pack_bf16_wt<VEC>(y, ybytes, off, a);
+                return;
+            }
+        }
+        store_pack_bf16<VEC>(y + off, a, yvec);
+    } else {
+        float *y = static_cast<float *>(ybase);
+        if (yvec < VEC) {
+            if constexpr (VEC == 8) {  // a 16-byte bf16 lane's 32 bytes of fp32: 8-byte stores, or 4-byte ones
+                if (yvec >= 2) {
+#pragma unroll
+                    for (int k = 0; k < 8; k += 2) *reinterpret_cast<float2 *>(y + off + k) = make_float2(a[k], a[k + 1]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) y[off + k] = a[k];
+                }
+            } else {
+                store_pack_any<VEC>(y + off, a, VEC, yvec);
+            }
+        }
+        else if (wt) store_pack_wt<VEC>(y, ybytes, off, a);
+        else store_pack<VEC>(y + off, a);
+    }
 }
 
 // Block b runs on XCD b % 8 (observed dispatch rule).  Give every XCD a contiguous range of
@@ -296,10 +438,11 @@ struct GcnArgs {
 // this once-streamed metadata were measured 1-5 % SLOWER, and nontemporal feature gathers 30 % slower at an
 // unchanged L2 hit rate -- `nt` does not bypass L2 allocation here; neither is used), kUnroll feature
 // gathers are issued before the first FMA.  Lanes with col_ok == false still carry metadata.
-template <int VEC, int GROUP, bool IS_MAX, int UNROLL = kUnroll>
+// TX = __bf16: 16-bit feature rows (Pack<VEC, __bf16>), widened in registers; the chain, its order and its fp32 FMAs are the same.
+template <int VEC, int GROUP, bool IS_MAX, int UNROLL = kUnroll, typename TX = float>
 __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end, int lane, bool col_ok,
                                             const int *__restrict__ idx, const float *__restrict__ val,
-                                            const float *__restrict__ xcol, int F)
+                                            const TX *__restrict__ xcol, int F)
 {
     if constexpr (GROUP >= 16 && GNNAGG_DPP_CHAIN) {
         // Windows of 16 edges, one copy per 16-lane DPP row of the group (lanes l and l + 16 load the same id: one request):
@@ -326,7 +469,7 @@ __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end,
                 if (J < n) {
                     int s[UNROLL];
                     float w[UNROLL];
-                    Pack<VEC> xv[UNROLL];
+                    Pack<VEC, TX> xv[UNROLL];
                     static_for<UNROLL>([&](auto uc) {
                         constexpr int u = decltype(uc)::value;
                         s[u] = group_bcast<16, J + u>(my_s);
@@ -341,10 +484,10 @@ __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end,
 #pragma unroll
                             for (int k = 0; k < VEC; ++k) {
                                 if (IS_MAX) {
-                                    const float p = xv[u].v[k] * w[u];
+                                    const float p = xv[u].at(k) * w[u];
                                     acc[k] = p > acc[k] ? p : acc[k];
                                 } else {
-                                    acc[k] = __builtin_fmaf(xv[u].v[k], w[u], acc[k]);
+                                    acc[k] = __builtin_fmaf(xv[u].at(k), w[u], acc[k]);
                                 }
                             }
                         }
@@ -372,7 +515,7 @@ __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end,
         for (int j = 0; j < n; j += UNROLL) {
             int s[UNROLL];
             float w[UNROLL];
-            Pack<VEC> xv[UNROLL];
+            Pack<VEC, TX> xv[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 s[u] = __shfl(my_s, j + u, GROUP);
@@ -387,10 +530,10 @@ __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end,
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         if (IS_MAX) {
-                            const float p = xv[u].v[k] * w[u];
+                            const float p = xv[u].at(k) * w[u];
                             acc[k] = p > acc[k] ? p : acc[k];
                         } else {
-                            acc[k] = __builtin_fmaf(xv[u].v[k], w[u], acc[k]);
+                            acc[k] = __builtin_fmaf(xv[u].at(k), w[u], acc[k]);
                         }
                     }
                 }

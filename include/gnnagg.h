@@ -208,6 +208,22 @@ int gnnagg_gcn_run(gnnagg_handle h, const float *d_x, float *d_y, int feat, int 
  * edges included. */
 #define GNNAGG_FLAG_RELU 2
 int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, int reduce, int flags);
+/* y = A.x with x / y in the given element types (no reference counterpart: the reference's surface is float *).  Accumulation,
+ * partial rows and the hub fold stay fp32; a bf16 y is ONE round-to-nearest-even of the fp32 result, at the store.  bf16 -> fp32 is
+ * exact and the chains keep their order, so a bf16 x gives bit for bit what gnnagg_gcn_run_ex gives on x widened to fp32.
+ * (F32, F32) is gnnagg_gcn_run_ex exactly.  The other three combinations:
+ *   mode    GNNAGG_MODE_BALANCED (a handle on the 2-D blocked order -- high-degree graphs -- runs the chunked plan, built beside it
+ *           on first use); GNNAGG_MODE_SCHEDULED where the plan kernel runs it ("fast_scheduled" = 1, the default, or a
+ *           neighbor-grouping schedule); GNNAGG_MODE_ROWS where "fast_rows" maps it to the balanced order
+ *   reduce  sum, mean, max;   flags  GNNAGG_FLAG_RELU; GNNAGG_FLAG_ACCUMULATE with a fp32 y (the accumulation target stays fp32)
+ *   feat    any F >= 1; x / y at any 2-byte offset (narrower lanes)
+ * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, ACCUMULATE
+ * into a bf16 y, the canonical rows mode (fast_rows = 0), an order the item kernels run -- and nothing falls back to fp32.
+ * gnnagg_gcn_run_with_nn and the GAT entry points are fp32 only. */
+#define GNNAGG_DTYPE_F32 0
+#define GNNAGG_DTYPE_BF16 1
+int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int mode, int reduce,
+                         int flags);
 /* Measurement aid (no reference counterpart): the gather ceiling of gnnagg_gcn_run(h, d_x, ., feat, mode, SUM).  Launches
  * the same kernel over the same work items with the same descriptor / neighbor-id / edge-value loads and the same
  * feature-row gathers (same addresses, same batching), but consumes the data with integer XORs instead of the
