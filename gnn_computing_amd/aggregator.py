@@ -31,11 +31,11 @@ class Schedule(enum.IntEnum):
 
 REDUCE = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX}
 MODE = {"rows": _lib.MODE_ROWS, "scheduled": _lib.MODE_SCHEDULED, "balanced": _lib.MODE_BALANCED}
-FEATURE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}   # gnnagg_gcn_run_typed
+FEATURE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}   # gnnagg_gcn_run_typed / gnnagg_gat_run_typed
 
 
 def _feat_dtype(t, name):
-    """GNNAGG_DTYPE_* of a GCN feature tensor; raises TypeError for anything but float32 / bfloat16, before any device work"""
+    """GNNAGG_DTYPE_* of a feature tensor (GCN / GAT vin, vout); raises TypeError for anything but float32 / bfloat16, before any device work"""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
     if t.dtype not in FEATURE_DTYPES:
@@ -285,13 +285,24 @@ class Aggregator_GAT(Aggregator):
         return self.run_with_feat(vin, vatt, vout, BLOCK_SIZE, scheduled, int(vin.shape[1]), heads, slope, newval)
 
     def run_with_feat(self, vin, vatt, vout, BLOCK_SIZE, scheduled, feat, heads=1, slope=0.2, newval=None):
-        """aggr_gat.h:355-394"""
+        """aggr_gat.h:355-394.  vin / vout: torch.float32 or torch.bfloat16 (extension, gnnagg_gat_run_typed): weights, sums and the
+        softmax division stay fp32, a bfloat16 vout is one round-to-nearest-even of the fp32 result; vatt and newval stay float32;
+        float32 / float32 is gnnagg_gat_run."""
+        xt, yt = _feat_dtype(vin, "vin"), _feat_dtype(vout, "vout")
+        for t, name in ((vatt, "vatt"), (newval, "newval")):
+            if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+                raise TypeError("%s must be torch.float32, got %s" % (name, t.dtype))
         if vatt.numel() < self.num_v * heads * 2:
             raise ValueError("att must hold at least V*heads*2 floats")
         self._use_current_stream()
-        check(lib().gnnagg_gat_run(self._h, _dev_ptr(vin, torch.float32, "vin"), _dev_ptr(vatt, torch.float32, "vatt"),
-                                   _dev_ptr(vout, torch.float32, "vout"), int(feat), int(heads),
-                                   ctypes.c_float(slope), _mode(scheduled), _dev_ptr(newval, torch.float32, "newval")))
+        if xt == _lib.DTYPE_F32 and yt == _lib.DTYPE_F32:
+            check(lib().gnnagg_gat_run(self._h, _dev_ptr(vin, torch.float32, "vin"), _dev_ptr(vatt, torch.float32, "vatt"),
+                                       _dev_ptr(vout, torch.float32, "vout"), int(feat), int(heads),
+                                       ctypes.c_float(slope), _mode(scheduled), _dev_ptr(newval, torch.float32, "newval")))
+        else:
+            check(lib().gnnagg_gat_run_typed(self._h, _dev_ptr(vin, vin.dtype, "vin"), xt, _dev_ptr(vatt, torch.float32, "vatt"),
+                                             _dev_ptr(vout, vout.dtype, "vout"), yt, int(feat), int(heads),
+                                             ctypes.c_float(slope), _mode(scheduled), _dev_ptr(newval, torch.float32, "newval")))
         return 0.0
 
     def run_part(self, vin, vatt, vout, den_io, part, heads=1, slope=0.2):

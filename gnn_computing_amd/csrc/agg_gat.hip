@@ -88,10 +88,12 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_items(const GatArgs a
 // The fused edge-softmax + weighted SpMM (reference aggr_gat / aggr_gat_fine, aggr_gat.h:116-205) on the same
 // plan as k_gcn_plan: short rows one lane group each, long rows one workgroup per <= 16-chunk segment with the
 // numerator AND denominator partials folded in ascending chunk order in LDS, hubs through scratch + k_combine.
-template <int VEC, int GROUP, int UNROLL = kUnroll>
+// TX = __bf16 (gnnagg_gat_run_typed): 16-bit feature rows (Pack<VEC, __bf16>), widened in registers where the chain consumes them; ids,
+// attention terms, weights, the fmaf chains and the denominator chain are the same.
+template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float>
 __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, int beg, int end, int lane, bool col_ok,
                                                 const int *__restrict__ idx, const float *__restrict__ att_src, int H,
-                                                float a_dst, float slope, const float *__restrict__ xcol, int F,
+                                                float a_dst, float slope, const TX *__restrict__ xcol, int F,
                                                 float *newval, int h, bool head_leader, const int *__restrict__ eperm = nullptr)
 {
     int my_s = 0;
@@ -103,7 +105,7 @@ __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, i
         for (int j = 0; j < n; j += UNROLL) {
             int s[UNROLL];
             float as[UNROLL];
-            Pack<VEC> xv[UNROLL];
+            Pack<VEC, TX> xv[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) s[u] = __shfl(my_s, j + u, GROUP);
 #pragma unroll
@@ -118,7 +120,7 @@ __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, i
                     const float w = edge_weight(a_dst, as[u], slope);
                     if (newval && head_leader) newval[(size_t)(eperm ? eperm[cb + j + u] : cb + j + u) * H + h] = w;
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(xv[u].v[k], w, acc[k]);
+                    for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(xv[u].at(k), w, acc[k]);
                     den += w;
                 }
         }
@@ -132,10 +134,10 @@ __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, i
 // every edge.  Ids are fetched two windows ahead and source terms one window ahead, so nothing dependent sits on the path;
 // the first feature gathers of a window are issued before its weights are needed.  Same values, same order as
 // chain_edges_gat (bit-identical results).
-template <int VEC, int GROUP, int UNROLL = kUnroll>
+template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float>
 __device__ __forceinline__ void chain_edges_gat1(float (&acc)[VEC], float &den, int beg, int end, int lane, bool col_ok,
                                                  const int *__restrict__ idx, const float *__restrict__ att_src, float a_dst,
-                                                 float slope, const float *__restrict__ xcol, int F, float *newval,
+                                                 float slope, const TX *__restrict__ xcol, int F, float *newval,
                                                  bool first_tile, const int *__restrict__ eperm = nullptr)
 {
     int s0 = 0, s1 = 0;
@@ -152,7 +154,7 @@ __device__ __forceinline__ void chain_edges_gat1(float (&acc)[VEC], float &den, 
         for (int j = 0; j < n; j += UNROLL) {
             int s[UNROLL];
             float w[UNROLL];
-            Pack<VEC> xv[UNROLL];
+            Pack<VEC, TX> xv[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) s[u] = __shfl(s0, j + u, GROUP);
 #pragma unroll
@@ -168,7 +170,7 @@ __device__ __forceinline__ void chain_edges_gat1(float (&acc)[VEC], float &den, 
             for (int u = 0; u < UNROLL; ++u)
                 if (j + u < n && col_ok) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(xv[u].v[k], w[u], acc[k]);
+                    for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(xv[u].at(k), w[u], acc[k]);
                     den += w[u];
                 }
         }
@@ -201,6 +203,8 @@ struct GatPlanArgs {
     int part_mode;
     float *den_io;
     XcdRanges xr;
+    // typed launches (TYPED = true): x holds TX elements; y holds bf16 (y_bf16) or fp32, and yvec is Y's alignment class in its own elements
+    int y_bf16;
 };
 
 // Last step of a GAT row: softmax division (scaleArray, aggr_gat.h:207-213), or its two-pass form.
@@ -230,7 +234,8 @@ __device__ __forceinline__ void finish_gat_row(const GatPlanArgs &a, float (&acc
 
 // GAT counterpart of hub_arrive_and_fold: numerator rows and per-head denominators of the hub's segments, ascending
 // slot order, one division at the end (scaleArray, aggr_gat.h:207-213) -- the order of k_combine<.., IS_GAT>.
-template <int VEC, int GROUP>
+// TYPED: the row is stored as a typed launch's Y (store_y_typed); scratch, fold and division stay fp32.
+template <int VEC, int GROUP, bool TYPED = false>
 __device__ __forceinline__ void hub_arrive_and_fold_gat(const GatPlanArgs &a, int slot, int tile, int col, bool col_ok, int h,
                                                         bool head_leader, int grp, int lane, float (&acc)[VEC], float den,
                                                         float *stage, float *stage_den)
@@ -286,16 +291,26 @@ __device__ __forceinline__ void hub_arrive_and_fold_gat(const GatPlanArgs &a, in
         __syncthreads();
     }
     if (grp == 0 && col_ok) {
-        finish_gat_row<VEC>(a, acc, den, row, h, head_leader, a.y + (size_t)row * F + col, false);
-        store_pack<VEC>(a.y + (size_t)row * F + col, acc);
+        if constexpr (TYPED) {   // (typed launches are single-pass: part_mode == 0, nothing of y is read)
+            finish_gat_row<VEC>(a, acc, den, row, h, head_leader, nullptr, false);
+            store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)row * F + col, acc);
+        } else {
+            finish_gat_row<VEC>(a, acc, den, row, h, head_leader, a.y + (size_t)row * F + col, false);
+            store_pack<VEC>(a.y + (size_t)row * F + col, acc);
+        }
     }
 }
 
 // (forcing 6 waves/SIMD -- 80 VGPRs, 5-9 spilled -- changes nothing: 100.8 vs 101.5 us on fig10a, 13.8 vs 13.6 ms on config G)
 // (UNROLL: see k_gcn_plan -- 4 on the 32-lane float4 geometry: arxiv-shaped 1 head F = 128, fused balanced 99.8 -> 96.1 us)
-template <int VEC, int GROUP, bool SINGLE, int UNROLL = kUnroll>
+// TX / TYPED (gnnagg_gat_run_typed): X holds elements of type TX (__bf16: lanes of VEC 16-bit elements, widened in registers); TYPED =
+// true stores every finished row through store_y_typed (a.y_bf16, a.yvec).  Weights, chains, denominators, LDS stage, partial rows, hub
+// fold and the division stay fp32 and keep their order, so a bf16 X gives bit for bit the fp32 run on X widened.  The defaults are the
+// fp32 kernel, instruction for instruction.  The segment workgroup's LDS stage grows with VEC: 36 KB at VEC = 8, GROUP = 64.
+template <int VEC, int GROUP, bool SINGLE, int UNROLL = kUnroll, typename TX = float, bool TYPED = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArgs a)
 {
+    static_assert(TYPED || std::is_same<TX, float>::value, "16-bit X needs the typed store");
     constexpr int GPB = block_of<GROUP>() / GROUP;
     const int F = a.feat, H = a.heads;
     const int lane = threadIdx.x & (GROUP - 1);
@@ -322,7 +337,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
     const int h = col_ok ? col / a.dhead : 0;
     const bool head_leader = col_ok && (col % a.dhead) == 0;
     const float *__restrict__ att_src = a.att + (size_t)h * 2 + 1;
-    const float *__restrict__ xcol = a.x + (size_t)tile * a.x_tile_stride + lane * VEC;
+    const TX *__restrict__ xcol = reinterpret_cast<const TX *>(a.x) + (size_t)tile * a.x_tile_stride + lane * VEC;
     if (seg_block) {
         __shared__ float stage[kSegChunks * GROUP * VEC];
         __shared__ float stage_den[kSegChunks * GROUP];
@@ -335,10 +350,10 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
             const int cb = d.x + c * a.chunk;
             const int ce = cb + a.chunk < d.y ? cb + a.chunk : d.y;
             if constexpr (SINGLE)
-                chain_edges_gat1<VEC, GROUP, UNROLL>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, F, a.newval,
+                chain_edges_gat1<VEC, GROUP, UNROLL, TX>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, F, a.newval,
                                              tile == 0);
             else
-                chain_edges_gat<VEC, GROUP, UNROLL>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, F, a.newval,
+                chain_edges_gat<VEC, GROUP, UNROLL, TX>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, F, a.newval,
                                             h, head_leader);
             store_pack<VEC>(&stage[(c * GROUP + lane) * VEC], acc);
             stage_den[c * GROUP + lane] = den;
@@ -359,13 +374,18 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
                 }
         }
         if (hub_here) {
-            hub_arrive_and_fold_gat<VEC, GROUP>(a, ~row_or_dest, tile, col, col_ok, h, head_leader, grp, lane, acc, den, stage,
+            hub_arrive_and_fold_gat<VEC, GROUP, TYPED>(a, ~row_or_dest, tile, col, col_ok, h, head_leader, grp, lane, acc, den, stage,
                                                 stage_den);
             return;
         }
         if (row_or_dest >= 0) {
-            finish_gat_row<VEC>(a, acc, den, row_or_dest, h, head_leader, a.y + (size_t)row_or_dest * F + col, false);
-            store_pack<VEC>(a.y + (size_t)row_or_dest * F + col, acc);
+            if constexpr (TYPED) {
+                finish_gat_row<VEC>(a, acc, den, row_or_dest, h, head_leader, nullptr, false);
+                store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)row_or_dest * F + col, acc);
+            } else {
+                finish_gat_row<VEC>(a, acc, den, row_or_dest, h, head_leader, a.y + (size_t)row_or_dest * F + col, false);
+                store_pack<VEC>(a.y + (size_t)row_or_dest * F + col, acc);
+            }
         } else {
             store_pack<VEC>(a.partial + (size_t)(~row_or_dest) * F + col, acc);
             if (head_leader) a.partial_den[(size_t)(~row_or_dest) * H + h] = den;
@@ -378,10 +398,10 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
     if (d.x < d.y) {
         const float a_dst = a.att[((size_t)row * H + h) * 2];
         if constexpr (SINGLE)
-            chain_edges_gat1<VEC, GROUP, UNROLL>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, a.xpitch, a.newval,
+            chain_edges_gat1<VEC, GROUP, UNROLL, TX>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, a.xpitch, a.newval,
                                          tile == 0, a.eperm);
         else
-            chain_edges_gat<VEC, GROUP, UNROLL>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, a.xpitch, a.newval,
+            chain_edges_gat<VEC, GROUP, UNROLL, TX>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, a.xpitch, a.newval,
                                         h, head_leader, a.eperm);
     }
     if (!col_ok) return;
@@ -390,6 +410,11 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
         if (a.ptile_bytes) store_pack_wt<VEC>(a.partial + (size_t)tile * a.p_tile_stride, a.ptile_bytes, poff, acc);
         else store_pack<VEC>(a.partial + (size_t)tile * a.p_tile_stride + poff, acc);
         if (head_leader) a.partial_den[(size_t)(~d.z) * H + h] = den;
+        return;
+    }
+    if constexpr (TYPED) {   // (write-back stores: a fp32 piece of a 16-byte bf16 lane is 32 bytes)
+        if (d.x < d.y) finish_gat_row<VEC>(a, acc, den, row, h, head_leader, nullptr, a.rows_semantics != 0);
+        store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)row * F + col, acc);
         return;
     }
     if (a.part_mode != 0) finish_gat_row<VEC>(a, acc, den, row, h, head_leader, a.y + (size_t)row * F + col, false);
@@ -442,6 +467,26 @@ int launch_gat(const GatLaunch &L, void *stream_v)
     return GNNAGG_OK;
 }
 
+// One typed launch of k_gat_plan.  4 gathers per batch (u4) on 16-byte lanes, as in the fp32 rule, here from 16-lane groups on: the
+// arxiv-shaped 1 head x 128 in bf16 (16 lanes of 8 elements) runs 73.0 / 65.0 us (fp32 / bf16 y) with 4 gathers (63 VGPRs) against 85.6 /
+// 82.1 us with 8 (89 VGPRs, 5 waves per SIMD); 8 heads x 16: 77.7 / 70.1 against 77.8 / 71.7 (profiles/bf16_gat/).  8-lane groups keep 8.
+#ifndef GNNAGG_GAT_TYPED_U4_GROUP   // A/B switch (measurement builds only): the narrowest lane group that takes 4 gathers per batch
+#define GNNAGG_GAT_TYPED_U4_GROUP 16
+#endif
+template <int VEC, int GROUP, typename TX>
+static void launch_gat_plan_typed(const GatPlanArgs &a, bool u4, int grid, int blk, hipStream_t stream)
+{
+    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= GNNAGG_GAT_TYPED_U4_GROUP) {
+        if (u4) {
+            if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+            else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+            return;
+        }
+    }
+    if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+    else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+}
+
 int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
@@ -449,7 +494,12 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
         return fail(GNNAGG_ERR_ARG, "GAT needs feat >= 1 and feat % heads == 0");
     const int dhead = L.feat / L.heads;
     if (L.tile.on && (L.n1 > 0 || dhead % 4 != 0)) return fail(GNNAGG_ERR_STATE, "internal: tiled GAT launch with segments / odd heads");
+    const bool typed = L.x_dtype != GNNAGG_DTYPE_F32 || L.y_dtype != GNNAGG_DTYPE_F32;
+    if (typed && (L.tile.on || L.part_mode != 0 || L.eperm || L.rows_semantics))
+        return fail(GNNAGG_ERR_STATE, "internal: typed GAT launch on a path without 16-bit forms");
+    const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     const Geometry g = L.tile.on ? Geometry{4, L.tile.tile_w / 4, (L.feat + L.tile.tile_w - 1) / L.tile.tile_w}
+                       : typed   ? typed_geometry(L.feat, L.x, xsize, dhead)
                                  : pick_geometry(L.feat, L.x, L.y, L.partial, dhead);
     GatPlanArgs a;
     a.t0 = reinterpret_cast<const int4 *>(L.t0); a.t1 = reinterpret_cast<const int4 *>(L.t1);
@@ -458,7 +508,9 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     a.heads = L.heads; a.dhead = dhead; a.remap = L.xcd_remap; a.slope = L.slope; a.rows_semantics = L.rows_semantics;
     a.slot_hub = L.slot_hub; a.mrow_ptr = L.hubs.mrow_ptr; a.mrow_id = L.hubs.mrow_id;
     a.hub_count = L.hub_count; a.hub_count_stride = L.hub_count_stride; a.partial_bytes = a.partial_den_bytes = 0;
-    a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec; a.yvec = g.vec;
+    a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec;
+    a.yvec = typed ? align_class(L.feat, L.y, ysize, g.vec) : g.vec;
+    a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
     a.tile_major = 0; a.item_blocks = 0; a.ptile_bytes = 0; a.eperm = L.eperm;
     a.part_mode = L.part_mode; a.den_io = L.den_io;
     if (L.part_mode != 0 && (L.tile.on || !L.den_io || L.newval || g.vec != 4 || g.ntiles != 1))
@@ -492,6 +544,50 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
         else grid0 = 8 * fill_xcd_ranges(L.t0_cost_prefix, a.n0, gpb, item_blocks, a.xr) * g.ntiles;
     }
     const int grid = a.n1 * g.ntiles + grid0;
+    if (typed) {
+        if (grid > 0) {
+            const bool u4t = L.unroll == 4 && g.vec * xsize == 16 && g.group >= GNNAGG_GAT_TYPED_U4_GROUP;
+#define CALL_TYPED(TXT) launch_gat_plan_typed<VEC, GROUP, TXT>(a, u4t, grid, blk, stream)
+            if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+                DISPATCH_GEOM_16BIT(g, CALL_TYPED(__bf16))
+            } else {
+                DISPATCH_GEOM(g, CALL_TYPED(float))
+            }
+#undef CALL_TYPED
+            HIP_TRY(hipGetLastError());
+        }
+        if (L.hubs.n_mrows == 0 || hubs_in_kernel) return GNNAGG_OK;
+        // hubs the kernel does not fold: the ordered combine of their fp32 partial rows and denominators, on fp32 lanes of its own (the
+        // partial rows are [slot][F]: any column tiling inside a head reads them), storing Y in its type
+        CombineArgs c;
+        const bool ybf = L.y_dtype == GNNAGG_DTYPE_BF16;
+        const int cv = align_class(dhead, L.y, ysize, 4);
+        const Geometry cgeo = ybf ? Geometry{cv, 64, ceil_div(L.feat, 64 * cv)} : pick_geometry(L.feat, L.partial, L.y, nullptr, dhead);
+        const int ctiles = cgeo.ntiles;
+        combine_strides(c, L.feat, cgeo, nullptr);
+        c.mrow_id = L.hubs.mrow_id; c.mrow_ptr = L.hubs.mrow_ptr; c.row_ptr = nullptr; c.partial = L.partial;
+        c.partial_den = L.partial_den; c.y = L.y; c.n_mrows = L.hubs.n_mrows; c.feat = L.feat; c.ntiles = ctiles;
+        c.heads = L.heads; c.dhead = dhead; c.mean = 0; c.accumulate = 0; c.y_bf16 = ybf ? 1 : 0;
+        c.nn_weight = nullptr; c.nn_out = nullptr; c.nn_cols = 0;
+        c.big_rows = L.hubs.big_rows; c.n_big = L.heads <= 64 ? L.hubs.n_big : 0;
+        c.nblocks_small = ceil_div(c.n_mrows, kBlock / cgeo.group) * ctiles;
+        const int nb_big = c.n_big * ctiles;
+#define CALL_COMB                                                                                                         \
+        hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, false>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);     \
+        if (nb_big > 0) hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
+#define CALL_COMB_BF16(V)                                                                                                 \
+        hipLaunchKernelGGL((k_combine<V, 64, false, true, false, true>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);    \
+        if (nb_big > 0) hipLaunchKernelGGL((k_combine<V, 64, false, true, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
+        if (ybf) {
+            if (cgeo.vec == 4) { CALL_COMB_BF16(4) } else if (cgeo.vec == 2) { CALL_COMB_BF16(2) } else { CALL_COMB_BF16(1) }
+        } else {
+            DISPATCH_GEOM(cgeo, CALL_COMB)
+        }
+#undef CALL_COMB_BF16
+#undef CALL_COMB
+        HIP_TRY(hipGetLastError());
+        return GNNAGG_OK;
+    }
     if (grid > 0) {
 #define CALL_GP                                                                                              \
         if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a);   \

@@ -928,50 +928,7 @@ int launch_dense_rows(const int *rows, int n_rows, const float *Y, const float *
 // geometry of a 2-D blocked launch: 16-byte lanes over tiles of tile_w floats
 static Geometry tile_geometry(const TileSpec &t, int feat) { return {4, t.tile_w / 4, (feat + t.tile_w - 1) / t.tile_w}; }
 
-// ---- typed launches (gnnagg_gcn_run_typed)
-// Alignment class of rows of F elements of `esize` bytes at p: the largest v <= maxvec with F % v == 0 and p aligned to v elements.
-static int align_class(int F, const void *p, int esize, int maxvec)
-{
-    int v = maxvec;
-    while (v > 1 && (F % v != 0 || (uintptr_t)p % ((uintptr_t)v * esize) != 0)) v >>= 1;
-    return v;
-}
-#ifndef GNNAGG_TYPED_LANE_BYTES   // A/B switch (measurement builds only): the widest lane of a typed launch
-#define GNNAGG_TYPED_LANE_BYTES 16
-#endif
-// Lanes as wide as F and X's alignment allow, up to 16 bytes: 8 bf16 elements (F = 128 -> 16-lane groups reading 256-byte rows), 8-,
-// 4- or 2-byte lanes where F or the alignment forces them.  Y's alignment class is set apart (PlanArgs::yvec): a fp32 Y row is twice
-// as wide as the bf16 row a lane reads.  The fp32 partial rows live in scratch the library allocates, aligned for any lane.
-static Geometry typed_geometry(int F, const void *x, int xsize)
-{
-    const int vec = align_class(F, x, xsize, GNNAGG_TYPED_LANE_BYTES / xsize);
-    const int lanes = (F + vec - 1) / vec;
-    int group = 8;
-    while (group < 64 && group < lanes) group <<= 1;
-    return {vec, group, (lanes + group - 1) / group};
-}
-
-// DISPATCH_GEOM plus the 16-byte lanes of 16-bit X (8 elements)
-#define DISPATCH_GEOM_16BIT(g, KERNEL_CALL)                                      \
-    switch ((g).vec * 100 + (g).group) {                                         \
-        case 108: { constexpr int VEC = 1, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 116: { constexpr int VEC = 1, GROUP = 16; KERNEL_CALL; } break;     \
-        case 132: { constexpr int VEC = 1, GROUP = 32; KERNEL_CALL; } break;     \
-        case 164: { constexpr int VEC = 1, GROUP = 64; KERNEL_CALL; } break;     \
-        case 208: { constexpr int VEC = 2, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 216: { constexpr int VEC = 2, GROUP = 16; KERNEL_CALL; } break;     \
-        case 232: { constexpr int VEC = 2, GROUP = 32; KERNEL_CALL; } break;     \
-        case 264: { constexpr int VEC = 2, GROUP = 64; KERNEL_CALL; } break;     \
-        case 408: { constexpr int VEC = 4, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 416: { constexpr int VEC = 4, GROUP = 16; KERNEL_CALL; } break;     \
-        case 432: { constexpr int VEC = 4, GROUP = 32; KERNEL_CALL; } break;     \
-        case 464: { constexpr int VEC = 4, GROUP = 64; KERNEL_CALL; } break;     \
-        case 808: { constexpr int VEC = 8, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 816: { constexpr int VEC = 8, GROUP = 16; KERNEL_CALL; } break;     \
-        case 832: { constexpr int VEC = 8, GROUP = 32; KERNEL_CALL; } break;     \
-        case 864: { constexpr int VEC = 8, GROUP = 64; KERNEL_CALL; } break;     \
-        default: return fail(GNNAGG_ERR_ARG, "unsupported lane geometry");       \
-    }
+// (typed launches: align_class / typed_geometry / DISPATCH_GEOM_16BIT live in kernel_util.cuh, shared with the GAT launcher)
 
 // One typed launch of k_gcn_plan.  4 gathers per batch (u4) where the fp32 rule's reason holds -- 16-byte lanes in groups of 32 or 64
 // lanes, the geometries whose 8-gather batches cost two waves per SIMD -- so in bf16 from F = 136 on; F = 128 (16-lane groups) keeps 8.
@@ -999,7 +956,7 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
         return fail(GNNAGG_ERR_STATE, "internal: typed launch on a path without 16-bit forms");
     const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     const Geometry g = L.tile.on ? tile_geometry(L.tile, L.feat)
-                       : typed   ? typed_geometry(L.feat, L.x, xsize)
+                       : typed   ? typed_geometry(L.feat, L.x, xsize, L.feat)
                                  : pick_geometry(L.feat, L.x, L.y, L.partial, L.feat);
     const bool is_max = L.reduce == GNNAGG_REDUCE_MAX;
     PlanArgs a;

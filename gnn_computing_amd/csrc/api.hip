@@ -1203,9 +1203,14 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
     return launch_dense_nn(y, nn->weight, nn->out, c->V, nn->cols, feat, c->stream);
 }
 
+// x_dtype / y_dtype (GNNAGG_DTYPE_*): what x / y hold.  16-bit types run on the plan kernel only (gnnagg_gat_run_typed has validated the
+// call; an order that would leave the plan kernel returns GNNAGG_ERR_ARG)
 static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat, int heads, float slope, int mode,
-                   float *newval, int probe = 0, int part = 0, float *den_io = nullptr)
+                   float *newval, int probe = 0, int part = 0, float *den_io = nullptr, int x_dtype = GNNAGG_DTYPE_F32,
+                   int y_dtype = GNNAGG_DTYPE_F32)
 {
+    const bool typed = x_dtype != GNNAGG_DTYPE_F32 || y_dtype != GNNAGG_DTYPE_F32;
+    if (typed && (probe || part != 0)) return fail(GNNAGG_ERR_ARG, "16-bit features: the two-pass form and the gather probe are fp32 only");
     if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "handle is not a GAT aggregator");
     if (!x || !y || !att) return fail(GNNAGG_ERR_ARG, "null feature/attention pointer");
     if (mode < GNNAGG_MODE_ROWS || mode > GNNAGG_MODE_BALANCED) return fail(GNNAGG_ERR_ARG, "bad mode");
@@ -1226,11 +1231,22 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
     }
     if (probe && !(mode == GNNAGG_MODE_BALANCED && c->partitions > 0 && c->plan_part.valid && c->part_descriptors))
         return fail(GNNAGG_ERR_ARG, "GAT probe: only the 2-D blocked balanced order has a probe instantiation");
-    if ((mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || part != 0)) || (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid)) {
+    // 16-bit features need the plan kernel: on a handle on the 2-D blocked order they run the chunked plan, built beside it
+    const bool typed_on_partitioned = typed && c->partitions > 0;
+    const bool on_plan = (mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || part != 0 || typed_on_partitioned)) ||
+                         (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid);
+    if (typed && !on_plan)
+        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gat_run_typed (x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                                        (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
+                                        "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
+                                        "neighbor-grouping schedule / \"fast_scheduled\" = 1 (without newval) for GNNAGG_MODE_SCHEDULED");
+    if (typed_on_partitioned && mode == GNNAGG_MODE_BALANCED && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
+    if (on_plan) {
         BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
         GatPlanLaunch P;
         P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk; P.t0_cost_prefix = p.t0_cost_prefix.data();
-        if (wants_sorted_rows(c, (long)feat * 4)) {
+        P.x_dtype = x_dtype; P.y_dtype = y_dtype;
+        if (wants_sorted_rows(c, (long)feat * (x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4))) {
             if ((rc = ensure_sorted_rows(c, p))) return rc;
             if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
         }
@@ -1849,6 +1865,25 @@ int gnnagg_gat_run(gnnagg_handle h, const float *d_x, const float *d_att, float 
 {
     GET_CTX(h);
     return gat_run(c, d_x, d_att, d_y, feat, heads, slope, mode, d_newval);
+}
+
+int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, void *d_y, int y_dtype, int feat, int heads,
+                         float slope, int mode, float *d_newval)
+{
+    GET_CTX(h);
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_typed: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32)
+        return gat_run(c, static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval);
+    const std::string combo = std::string("x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                              (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32");
+    if (c->kind == Ctx::GAT && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
+                                    "is fp32 only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
+    return gat_run(c, static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval, 0, 0, nullptr,
+                   x_dtype, y_dtype);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

@@ -243,8 +243,9 @@ struct GatPlanLaunch {
     WorkList hubs;
     const int *idx = nullptr;
     const float *att = nullptr;
-    const float *x = nullptr;
-    float *y = nullptr;
+    const float *x = nullptr;   // elements of x_dtype
+    float *y = nullptr;         // elements of y_dtype
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;  // gnnagg_gat_run_typed: 16-bit X / Y (fp32 weights, chains, partials, fold)
     float *partial = nullptr, *partial_den = nullptr, *newval = nullptr;
     int feat = 0, heads = 1;
     float slope = 0.2f;

@@ -622,6 +622,52 @@ static Geometry pick_geometry(int F, const void *p0, const void *p1, const void 
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- typed launches (gnnagg_gcn_run_typed, gnnagg_gat_run_typed)
+// Alignment class of rows of F elements of `esize` bytes at p: the largest v <= maxvec with F % v == 0 and p aligned to v elements.
+static int align_class(int F, const void *p, int esize, int maxvec)
+{
+    int v = maxvec;
+    while (v > 1 && (F % v != 0 || (uintptr_t)p % ((uintptr_t)v * esize) != 0)) v >>= 1;
+    return v;
+}
+#ifndef GNNAGG_TYPED_LANE_BYTES   // A/B switch (measurement builds only): the widest lane of a typed launch
+#define GNNAGG_TYPED_LANE_BYTES 16
+#endif
+// Lanes as wide as F and X's alignment allow, up to 16 bytes: 8 bf16 elements (F = 128 -> 16-lane groups reading 256-byte rows), 8-,
+// 4- or 2-byte lanes where F or the alignment forces them.  Y's alignment class is set apart (PlanArgs::yvec): a fp32 Y row is twice
+// as wide as the bf16 row a lane reads.  The fp32 partial rows live in scratch the library allocates, aligned for any lane.
+// dhead (GAT; pick_geometry's rule): a lane's VEC columns lie inside one head, so VEC divides dhead too (dhead divides F; GCN: dhead = F).
+static Geometry typed_geometry(int F, const void *x, int xsize, int dhead)
+{
+    const int vec = align_class(dhead, x, xsize, GNNAGG_TYPED_LANE_BYTES / xsize);
+    const int lanes = (F + vec - 1) / vec;
+    int group = 8;
+    while (group < 64 && group < lanes) group <<= 1;
+    return {vec, group, (lanes + group - 1) / group};
+}
+
+// DISPATCH_GEOM plus the 16-byte lanes of 16-bit X (8 elements)
+#define DISPATCH_GEOM_16BIT(g, KERNEL_CALL)                                      \
+    switch ((g).vec * 100 + (g).group) {                                         \
+        case 108: { constexpr int VEC = 1, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 116: { constexpr int VEC = 1, GROUP = 16; KERNEL_CALL; } break;     \
+        case 132: { constexpr int VEC = 1, GROUP = 32; KERNEL_CALL; } break;     \
+        case 164: { constexpr int VEC = 1, GROUP = 64; KERNEL_CALL; } break;     \
+        case 208: { constexpr int VEC = 2, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 216: { constexpr int VEC = 2, GROUP = 16; KERNEL_CALL; } break;     \
+        case 232: { constexpr int VEC = 2, GROUP = 32; KERNEL_CALL; } break;     \
+        case 264: { constexpr int VEC = 2, GROUP = 64; KERNEL_CALL; } break;     \
+        case 408: { constexpr int VEC = 4, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 416: { constexpr int VEC = 4, GROUP = 16; KERNEL_CALL; } break;     \
+        case 432: { constexpr int VEC = 4, GROUP = 32; KERNEL_CALL; } break;     \
+        case 464: { constexpr int VEC = 4, GROUP = 64; KERNEL_CALL; } break;     \
+        case 808: { constexpr int VEC = 8, GROUP = 8;  KERNEL_CALL; } break;     \
+        case 816: { constexpr int VEC = 8, GROUP = 16; KERNEL_CALL; } break;     \
+        case 832: { constexpr int VEC = 8, GROUP = 32; KERNEL_CALL; } break;     \
+        case 864: { constexpr int VEC = 8, GROUP = 64; KERNEL_CALL; } break;     \
+        default: return fail(GNNAGG_ERR_ARG, "unsupported lane geometry");       \
+    }
+
 // Launch-site state that belongs to a DEVICE, not to the process (a process may drive several): "this function attribute has been
 // set here" flags and the CU count.  (A relaxed race sets an attribute twice, which is harmless.)
 struct OncePerDevice {

@@ -219,7 +219,7 @@ int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, i
  *   feat    any F >= 1; x / y at any 2-byte offset (narrower lanes)
  * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, ACCUMULATE
  * into a bf16 y, the canonical rows mode (fast_rows = 0), an order the item kernels run -- and nothing falls back to fp32.
- * gnnagg_gcn_run_with_nn and the GAT entry points are fp32 only. */
+ * gnnagg_gcn_run_with_nn is fp32 only; the fused GAT aggregation has its own typed call, gnnagg_gat_run_typed. */
 #define GNNAGG_DTYPE_F32 0
 #define GNNAGG_DTYPE_BF16 1
 int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int mode, int reduce,
@@ -275,6 +275,23 @@ int gnnagg_csr2edgelist(gnnagg_handle h, int *d_edgelist);
  * un-normalised edge weights [E,heads] the reference's scheduled kernel materialises (:187). */
 int gnnagg_gat_run(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads,
                    float slope, int mode, float *d_newval);
+/* gnnagg_gat_run with x / y in the given element types (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16; no reference counterpart).  d_att
+ * [V,heads,2] and d_newval [E,heads] stay fp32.  Numerator, denominator, exp, LDS stage, partial rows, hub fold and the softmax
+ * division stay fp32 and keep their order, and bf16 -> fp32 is exact, so a bf16 x gives bit for bit what gnnagg_gat_run gives on x
+ * widened to fp32 (same handle, same mode), newval included; a bf16 y is ONE round-to-nearest-even of that fp32 result, at the store
+ * (NaN kept, overflow to inf as in a plain conversion); rows without edges are +0.
+ * (F32, F32) is gnnagg_gat_run exactly.  The other three combinations:
+ *   mode    GNNAGG_MODE_BALANCED (a handle on the 2-D blocked order -- high-degree graphs -- runs the chunked plan, built beside it
+ *           on first use; the handle keeps its blocked order for fp32 calls); GNNAGG_MODE_SCHEDULED where the plan kernel runs it (a
+ *           neighbor-grouping schedule, or "fast_scheduled" = 1, the default, on a call without d_newval); GNNAGG_MODE_ROWS where
+ *           "fast_rows" = 1 maps it to the balanced order (handles of the reference-named surface start that way)
+ *   feat    any F >= 1 with feat % heads == 0; x / y at any 2-byte (bf16) or 4-byte (fp32) offset (narrower lanes)
+ * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, the
+ * canonical rows mode (fast_rows = 0), an order the item kernels run -- and nothing falls back to fp32.
+ * Still fp32 only: gnnagg_gat_run_part, gnnagg_gat_probe_gather, the distributed step (gnnagg_dist_step_*), the backward entry point
+ * and the edge-softmax pieces below. */
+int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, void *d_y, int y_dtype,
+                         int feat, int heads, float slope, int mode, float *d_newval);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns.
