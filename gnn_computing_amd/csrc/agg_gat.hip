@@ -423,6 +423,38 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
     else store_pack<VEC>(a.y + (size_t)row * F + col, acc);
 }
 
+// The ordered combine of split rows' partial rows and denominators (k_combine<..., IS_GAT>).  y_bf16: a typed launch's bf16 Y, on 64-lane
+// groups of g.vec fp32 lanes (as in launch_combine_gcn)
+static int launch_combine_gat(const WorkList &wl, const float *partial, const float *partial_den, float *y, int feat, int heads, const Geometry &g,
+                              hipStream_t stream, const TileSpec *tile = nullptr, bool y_bf16 = false)
+{
+    if (wl.n_mrows <= 0) return GNNAGG_OK;
+    CombineArgs c;
+    combine_strides(c, feat, g, tile);
+    c.mrow_id = wl.mrow_id; c.mrow_ptr = wl.mrow_ptr; c.row_ptr = nullptr; c.partial = partial;
+    c.partial_den = partial_den; c.y = y; c.n_mrows = wl.n_mrows; c.feat = feat; c.ntiles = g.ntiles;
+    c.heads = heads; c.dhead = feat / heads; c.mean = 0; c.accumulate = 0; c.y_bf16 = y_bf16 ? 1 : 0;
+    c.nn_weight = nullptr; c.nn_out = nullptr; c.nn_cols = 0;
+    c.big_rows = wl.big_rows; c.n_big = heads <= 64 ? wl.n_big : 0;
+    c.nblocks_small = ceil_div(c.n_mrows, kBlock / g.group) * g.ntiles;
+    const int nb_big = c.n_big * g.ntiles;
+#define CALL_COMB                                                                                                         \
+    hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, false>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);     \
+    if (nb_big > 0) hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
+#define CALL_COMB_BF16(V)                                                                                                 \
+    hipLaunchKernelGGL((k_combine<V, 64, false, true, false, true>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);    \
+    if (nb_big > 0) hipLaunchKernelGGL((k_combine<V, 64, false, true, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
+    if (y_bf16) {
+        if (g.vec == 4) { CALL_COMB_BF16(4) } else if (g.vec == 2) { CALL_COMB_BF16(2) } else { CALL_COMB_BF16(1) }
+    } else {
+        DISPATCH_GEOM(g, CALL_COMB)
+    }
+#undef CALL_COMB_BF16
+#undef CALL_COMB
+    HIP_TRY(hipGetLastError());
+    return GNNAGG_OK;
+}
+
 int launch_gat(const GatLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
@@ -447,44 +479,29 @@ int launch_gat(const GatLaunch &L, void *stream_v)
 #undef CALL_GAT
         HIP_TRY(hipGetLastError());
     }
-    if (L.wl.n_mrows > 0) {
-        CombineArgs c;
-        combine_strides(c, L.feat, g, nullptr);
-        c.nn_weight = nullptr; c.nn_out = nullptr; c.nn_cols = 0;
-        c.mrow_id = L.wl.mrow_id; c.mrow_ptr = L.wl.mrow_ptr; c.row_ptr = nullptr; c.partial = L.partial;
-        c.partial_den = L.partial_den; c.y = L.y; c.n_mrows = L.wl.n_mrows; c.feat = L.feat; c.ntiles = g.ntiles;
-        c.heads = L.heads; c.dhead = dhead; c.mean = 0; c.accumulate = 0;
-        c.big_rows = L.wl.big_rows; c.n_big = L.heads <= 64 ? L.wl.n_big : 0;
-        c.nblocks_small = ceil_div(c.n_mrows, kBlock / g.group) * g.ntiles;
-        const int nb_big = c.n_big * g.ntiles;
-#define CALL_COMB                                                                                                         \
-        hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, false>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);     \
-        if (nb_big > 0) hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
-        DISPATCH_GEOM(g, CALL_COMB)
-#undef CALL_COMB
-        HIP_TRY(hipGetLastError());
-    }
-    return GNNAGG_OK;
+    return launch_combine_gat(L.wl, L.partial, L.partial_den, L.y, L.feat, L.heads, g, stream);
 }
 
-// One typed launch of k_gat_plan.  4 gathers per batch (u4) on 16-byte lanes, as in the fp32 rule, here from 16-lane groups on: the
+// One launch of k_gat_plan on a lane geometry (fp32 and typed alike).  4 gathers per batch (u4) on 16-byte lanes: fp32 in groups of 32 or
+// 64 lanes (the rule of k_gcn_plan), typed launches from 16-lane groups on: the
 // arxiv-shaped 1 head x 128 in bf16 (16 lanes of 8 elements) runs 73.0 / 65.0 us (fp32 / bf16 y) with 4 gathers (63 VGPRs) against 85.6 /
 // 82.1 us with 8 (89 VGPRs, 5 waves per SIMD); 8 heads x 16: 77.7 / 70.1 against 77.8 / 71.7 (profiles/bf16_gat/).  8-lane groups keep 8.
 #ifndef GNNAGG_GAT_TYPED_U4_GROUP   // A/B switch (measurement builds only): the narrowest lane group that takes 4 gathers per batch
 #define GNNAGG_GAT_TYPED_U4_GROUP 16
 #endif
-template <int VEC, int GROUP, typename TX>
-static void launch_gat_plan_typed(const GatPlanArgs &a, bool u4, int grid, int blk, hipStream_t stream)
+template <int VEC, int GROUP, int UNROLL, typename TX, bool TYPED>
+static void launch_gat_plan_unroll(const GatPlanArgs &a, int grid, int blk, hipStream_t stream)
 {
-    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= GNNAGG_GAT_TYPED_U4_GROUP) {
-        if (u4) {
-            if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
-            else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
-            return;
-        }
+    if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
+    else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
+}
+template <int VEC, int GROUP, typename TX, bool TYPED>
+static void launch_gat_plan_geom(const GatPlanArgs &a, bool u4, int grid, int blk, hipStream_t stream)
+{
+    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= (TYPED ? GNNAGG_GAT_TYPED_U4_GROUP : 32)) {
+        if (u4) return launch_gat_plan_unroll<VEC, GROUP, 4, TX, TYPED>(a, grid, blk, stream);
     }
-    if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
-    else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+    launch_gat_plan_unroll<VEC, GROUP, kUnroll, TX, TYPED>(a, grid, blk, stream);
 }
 
 int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
@@ -498,7 +515,7 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     if (typed && (L.tile.on || L.part_mode != 0 || L.eperm || L.rows_semantics))
         return fail(GNNAGG_ERR_STATE, "internal: typed GAT launch on a path without 16-bit forms");
     const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
-    const Geometry g = L.tile.on ? Geometry{4, L.tile.tile_w / 4, (L.feat + L.tile.tile_w - 1) / L.tile.tile_w}
+    const Geometry g = L.tile.on ? tile_geometry(L.tile, L.feat)
                        : typed   ? typed_geometry(L.feat, L.x, xsize, dhead)
                                  : pick_geometry(L.feat, L.x, L.y, L.partial, dhead);
     GatPlanArgs a;
@@ -511,16 +528,10 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec;
     a.yvec = typed ? align_class(L.feat, L.y, ysize, g.vec) : g.vec;
     a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
-    a.tile_major = 0; a.item_blocks = 0; a.ptile_bytes = 0; a.eperm = L.eperm;
+    a.eperm = L.eperm;
     a.part_mode = L.part_mode; a.den_io = L.den_io;
     if (L.part_mode != 0 && (L.tile.on || !L.den_io || L.newval || g.vec != 4 || g.ntiles != 1))
         return fail(GNNAGG_ERR_ARG, "two-pass GAT: 16-byte aligned rows of at most 256 columns on the chunked plan, no newval");
-    if (L.tile.on) {
-        a.xpitch = L.tile.xpitch; a.x_tile_stride = L.tile.x_tile_stride; a.ppitch = L.tile.ppitch;
-        a.p_tile_stride = L.tile.p_tile_stride; a.yvec = L.tile.yvec; a.tile_major = 1;
-        const size_t tb = (size_t)L.hubs.n_slots * L.tile.ppitch * sizeof(float);
-        a.ptile_bytes = tb < 0x7fffffffULL ? (unsigned)tb : 0u;
-    }
     {
         // one column tile only: with several, a head's denominator is written by the tile that holds its first column
         // and the other tiles' last arrivers could not know that store is done
@@ -530,99 +541,31 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     }
     const bool hubs_in_kernel = a.hub_count != nullptr;
     const int blk = block_for(g.group);
-    const int gpb = blk / g.group;
-    const int item_blocks = ceil_div(a.n0, gpb);
-    a.nblocks0 = item_blocks * g.ntiles;
-    a.item_blocks = item_blocks;
-    if (a.remap && a.nblocks0 < 64 && !a.tile_major) a.remap = 0;
-    int grid0 = a.nblocks0;
-    if (a.tile_major) {
-        if (!L.t0_cost_prefix) return fail(GNNAGG_ERR_STATE, "internal: tiled launch without item costs");
-        grid0 = 8 * fill_xcd_ranges_tile_major(L.t0_cost_prefix, a.n0, gpb, item_blocks, g.ntiles, a.xr);
-    } else if (a.remap == 2) {
-        if (!L.t0_cost_prefix) a.remap = 1;
-        else grid0 = 8 * fill_xcd_ranges(L.t0_cost_prefix, a.n0, gpb, item_blocks, a.xr) * g.ntiles;
-    }
-    const int grid = a.n1 * g.ntiles + grid0;
-    if (typed) {
-        if (grid > 0) {
-            const bool u4t = L.unroll == 4 && g.vec * xsize == 16 && g.group >= GNNAGG_GAT_TYPED_U4_GROUP;
-#define CALL_TYPED(TXT) launch_gat_plan_typed<VEC, GROUP, TXT>(a, u4t, grid, blk, stream)
-            if (L.x_dtype == GNNAGG_DTYPE_BF16) {
-                DISPATCH_GEOM_16BIT(g, CALL_TYPED(__bf16))
-            } else {
-                DISPATCH_GEOM(g, CALL_TYPED(float))
-            }
-#undef CALL_TYPED
-            HIP_TRY(hipGetLastError());
-        }
-        if (L.hubs.n_mrows == 0 || hubs_in_kernel) return GNNAGG_OK;
-        // hubs the kernel does not fold: the ordered combine of their fp32 partial rows and denominators, on fp32 lanes of its own (the
-        // partial rows are [slot][F]: any column tiling inside a head reads them), storing Y in its type
-        CombineArgs c;
-        const bool ybf = L.y_dtype == GNNAGG_DTYPE_BF16;
-        const int cv = align_class(dhead, L.y, ysize, 4);
-        const Geometry cgeo = ybf ? Geometry{cv, 64, ceil_div(L.feat, 64 * cv)} : pick_geometry(L.feat, L.partial, L.y, nullptr, dhead);
-        const int ctiles = cgeo.ntiles;
-        combine_strides(c, L.feat, cgeo, nullptr);
-        c.mrow_id = L.hubs.mrow_id; c.mrow_ptr = L.hubs.mrow_ptr; c.row_ptr = nullptr; c.partial = L.partial;
-        c.partial_den = L.partial_den; c.y = L.y; c.n_mrows = L.hubs.n_mrows; c.feat = L.feat; c.ntiles = ctiles;
-        c.heads = L.heads; c.dhead = dhead; c.mean = 0; c.accumulate = 0; c.y_bf16 = ybf ? 1 : 0;
-        c.nn_weight = nullptr; c.nn_out = nullptr; c.nn_cols = 0;
-        c.big_rows = L.hubs.big_rows; c.n_big = L.heads <= 64 ? L.hubs.n_big : 0;
-        c.nblocks_small = ceil_div(c.n_mrows, kBlock / cgeo.group) * ctiles;
-        const int nb_big = c.n_big * ctiles;
-#define CALL_COMB                                                                                                         \
-        hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, false>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);     \
-        if (nb_big > 0) hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
-#define CALL_COMB_BF16(V)                                                                                                 \
-        hipLaunchKernelGGL((k_combine<V, 64, false, true, false, true>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);    \
-        if (nb_big > 0) hipLaunchKernelGGL((k_combine<V, 64, false, true, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
-        if (ybf) {
-            if (cgeo.vec == 4) { CALL_COMB_BF16(4) } else if (cgeo.vec == 2) { CALL_COMB_BF16(2) } else { CALL_COMB_BF16(1) }
-        } else {
-            DISPATCH_GEOM(cgeo, CALL_COMB)
-        }
-#undef CALL_COMB_BF16
-#undef CALL_COMB
-        HIP_TRY(hipGetLastError());
-        return GNNAGG_OK;
-    }
+    int grid = 0;
+    if (int rc = plan_grid(a, g, blk / g.group, L.tile, L.hubs.n_slots, L.t0_cost_prefix, &grid)) return rc;
     if (grid > 0) {
-#define CALL_GP                                                                                              \
-        if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a);   \
-        else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false>), dim3(grid), dim3(blk), 0, stream, a);
-        const bool u4 = L.unroll == 4 && g.vec == 4 && !L.tile.on;
-        if (u4 && g.group == 32) {
-            if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<4, 32, true, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else              hipLaunchKernelGGL((k_gat_plan<4, 32, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-        } else if (u4 && g.group == 64) {
-            if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<4, 64, true, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else              hipLaunchKernelGGL((k_gat_plan<4, 64, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-        } else DISPATCH_GEOM(g, CALL_GP)
+        const bool u4 = L.unroll == 4 && !L.tile.on;   // where the geometry has that instantiation (launch_gat_plan_geom)
+#define CALL_GP(TXT, TYPED) launch_gat_plan_geom<VEC, GROUP, TXT, TYPED>(a, u4, grid, blk, stream)
+        if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+            DISPATCH_GEOM_16BIT(g, CALL_GP(__bf16, true))
+        } else if (typed) {
+            DISPATCH_GEOM(g, CALL_GP(float, true))
+        } else {
+            DISPATCH_GEOM(g, CALL_GP(float, false))
+        }
 #undef CALL_GP
         HIP_TRY(hipGetLastError());
     }
-    if (L.hubs.n_mrows > 0 && !hubs_in_kernel && L.part_mode != 0)
+    if (L.hubs.n_mrows == 0 || hubs_in_kernel) return GNNAGG_OK;
+    if (L.part_mode != 0)
         return fail(GNNAGG_ERR_STATE, "two-pass GAT: hub rows are folded inside the plan kernel only (GNNAGG_INKERNEL_COMBINE=0 set?)");
-    if (L.hubs.n_mrows > 0 && !hubs_in_kernel) {
-        CombineArgs c;
-        combine_strides(c, L.feat, g, &L.tile);
-        c.mrow_id = L.hubs.mrow_id; c.mrow_ptr = L.hubs.mrow_ptr; c.row_ptr = nullptr; c.partial = L.partial;
-        c.partial_den = L.partial_den; c.y = L.y; c.n_mrows = L.hubs.n_mrows; c.feat = L.feat; c.ntiles = g.ntiles;
-        c.heads = L.heads; c.dhead = dhead; c.mean = 0; c.accumulate = 0;
-        c.nn_weight = nullptr; c.nn_out = nullptr; c.nn_cols = 0;
-        c.big_rows = L.hubs.big_rows; c.n_big = L.heads <= 64 ? L.hubs.n_big : 0;
-        c.nblocks_small = ceil_div(c.n_mrows, kBlock / g.group) * g.ntiles;
-        const int nb_big = c.n_big * g.ntiles;
-#define CALL_COMB                                                                                                         \
-        hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, false>), dim3(c.nblocks_small), dim3(kBlock), 0, stream, c);     \
-        if (nb_big > 0) hipLaunchKernelGGL((k_combine<VEC, GROUP, false, true, true>), dim3(nb_big), dim3(kBlock), 0, stream, c);
-        DISPATCH_GEOM(g, CALL_COMB)
-#undef CALL_COMB
-        HIP_TRY(hipGetLastError());
-    }
-    return GNNAGG_OK;
+    if (!typed) return launch_combine_gat(L.hubs, L.partial, L.partial_den, L.y, L.feat, L.heads, g, stream, &L.tile);
+    // typed: the ordered combine of the fp32 partial rows and denominators on fp32 lanes of its own (the partial rows are [slot][F]: any
+    // column tiling inside a head reads them), storing Y in its type
+    const bool ybf = L.y_dtype == GNNAGG_DTYPE_BF16;
+    const int cv = align_class(dhead, L.y, ysize, 4);
+    const Geometry cgeo = ybf ? Geometry{cv, 64, ceil_div(L.feat, 64 * cv)} : pick_geometry(L.feat, L.partial, L.y, nullptr, dhead);
+    return launch_combine_gat(L.hubs, L.partial, L.partial_den, L.y, L.feat, L.heads, cgeo, stream, nullptr, ybf);
 }
 
 // edge values follow a permuted edge list (val_t[e'] = val[perm[e']]): the partitioned orders re-gather them before every run

@@ -925,25 +925,30 @@ int launch_dense_rows(const int *rows, int n_rows, const float *Y, const float *
     return GNNAGG_OK;
 }
 
-// geometry of a 2-D blocked launch: 16-byte lanes over tiles of tile_w floats
-static Geometry tile_geometry(const TileSpec &t, int feat) { return {4, t.tile_w / 4, (feat + t.tile_w - 1) / t.tile_w}; }
-
 // (typed launches: align_class / typed_geometry / DISPATCH_GEOM_16BIT live in kernel_util.cuh, shared with the GAT launcher)
 
-// One typed launch of k_gcn_plan.  4 gathers per batch (u4) where the fp32 rule's reason holds -- 16-byte lanes in groups of 32 or 64
-// lanes, the geometries whose 8-gather batches cost two waves per SIMD -- so in bf16 from F = 136 on; F = 128 (16-lane groups) keeps 8.
-template <int VEC, int GROUP, typename TX>
-static void launch_plan_typed(const PlanArgs &a, bool is_max, bool u4, int grid, int blk, hipStream_t stream)
+template <int VEC, int GROUP, bool PROBE, int UNROLL, typename TX, bool TYPED>
+static void launch_plan_unroll(const PlanArgs &a, bool is_max, int grid, int blk, hipStream_t stream)
 {
-    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= 32) {
-        if (u4) {
-            if (is_max) hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
-            else        hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, false, 4, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+    if constexpr (!PROBE) {   // (the probe is sum / mean only)
+        if (is_max) {
+            hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true, false, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
             return;
         }
     }
-    if (is_max) hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
-    else        hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, false, kUnroll, TX, true>), dim3(grid), dim3(blk), 0, stream, a);
+    hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, PROBE, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
+}
+
+// One launch of k_gcn_plan on a lane geometry (fp32, probe and typed alike).  4 gathers per batch (u4) on 16-byte lanes in groups of 32
+// or 64 lanes, the geometries whose 8-gather batches cost two waves per SIMD: fp32 float4 lanes; in bf16 from F = 136 on, F = 128
+// (16-lane groups) keeps 8.
+template <int VEC, int GROUP, bool PROBE, typename TX, bool TYPED>
+static void launch_plan_geom(const PlanArgs &a, bool is_max, bool u4, int grid, int blk, hipStream_t stream)
+{
+    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= 32) {
+        if (u4) return launch_plan_unroll<VEC, GROUP, PROBE, 4, TX, TYPED>(a, is_max, grid, blk, stream);
+    }
+    launch_plan_unroll<VEC, GROUP, PROBE, kUnroll, TX, TYPED>(a, is_max, grid, blk, stream);
 }
 
 int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
@@ -970,13 +975,7 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
     a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec;
     a.yvec = typed ? align_class(L.feat, L.y, ysize, g.vec) : g.vec;
     a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
-    a.tile_major = 0; a.item_blocks = 0; a.ptile_bytes = 0; a.probe_sink = nullptr;
-    if (L.tile.on) {
-        a.xpitch = L.tile.xpitch; a.x_tile_stride = L.tile.x_tile_stride; a.ppitch = L.tile.ppitch;
-        a.p_tile_stride = L.tile.p_tile_stride; a.yvec = L.tile.yvec; a.tile_major = 1;
-        const size_t tb = (size_t)L.hubs.n_slots * L.tile.ppitch * sizeof(float);
-        a.ptile_bytes = tb < 0x7fffffffULL ? (unsigned)tb : 0u;
-    }
+    a.probe_sink = nullptr;
     {
         const size_t pbytes = (size_t)L.hubs.n_slots * L.feat * sizeof(float);
         if (L.hubs.n_mrows == 0 || pbytes >= 0x7fffffffULL || g.ntiles > L.hub_count_stride) a.hub_count = nullptr;
@@ -994,94 +993,59 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
     const bool want_nn = L.nn_weight != nullptr;
     // (8-lane groups, F <= 32: the GEMM is ~11 us on the arxiv-shaped input and the epilogue costs as much -- not fused)
     const bool fuse_nn = want_nn && !L.tile.on && !L.probe && g.ntiles == 1 && g.group >= 16 && !L.accumulate && !L.relu && !L.t0_partials;
-    // 4 gathers per batch on the 32-lane float4 geometry when the caller asks for it (see k_gcn_plan)
-    const bool u4 = L.unroll == 4 && g.vec == 4 && (g.group == 32 || g.group == 64) && !L.tile.on && !fuse_nn;
+    // 4 gathers per batch when the caller asks for it, where the geometry has that instantiation (launch_plan_geom)
+    const bool u4 = L.unroll == 4 && !L.tile.on && !fuse_nn;
     const int blk = block_for(g.group);
     const int gpb = fuse_nn ? std::max(kNnRows, blk / g.group) : blk / g.group;
-    const int item_blocks = ceil_div(a.n0, gpb);
-    a.nblocks0 = item_blocks * g.ntiles;
-    a.item_blocks = item_blocks;
-    if (a.remap && a.nblocks0 < 64 && !a.tile_major) a.remap = 0;
-    int grid0 = a.nblocks0;
-    if (a.tile_major) {
-        if (!L.t0_cost_prefix) return fail(GNNAGG_ERR_STATE, "internal: tiled launch without item costs");
-        grid0 = 8 * fill_xcd_ranges_tile_major(L.t0_cost_prefix, a.n0, gpb, item_blocks, g.ntiles, a.xr);
-    } else if (a.remap == 2) {
-        if (!L.t0_cost_prefix) a.remap = 1;
-        else grid0 = 8 * fill_xcd_ranges(L.t0_cost_prefix, a.n0, gpb, item_blocks, a.xr) * g.ntiles;
-    }
-    const int grid = a.n1 * g.ntiles + grid0;
-    if (typed) {
-        if (grid > 0) {
-            const bool u4t = L.unroll == 4 && g.vec * xsize == 16 && g.group >= 32;
-#define CALL_TYPED(TXT) launch_plan_typed<VEC, GROUP, TXT>(a, is_max, u4t, grid, blk, stream)
-            if (L.x_dtype == GNNAGG_DTYPE_BF16) {
-                DISPATCH_GEOM_16BIT(g, CALL_TYPED(__bf16))
-            } else {
-                DISPATCH_GEOM(g, CALL_TYPED(float))
-            }
-#undef CALL_TYPED
-            HIP_TRY(hipGetLastError());
-        }
-        if (hubs_in_kernel) return GNNAGG_OK;
-        // hubs the kernel does not fold: the ordered combine of their fp32 partial rows, on fp32 lanes of its own (the partial rows are
-        // [slot][F]: any column tiling reads them), storing Y in its type
-        GcnLaunch C;
-        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
-        C.accumulate = L.accumulate; C.relu = L.relu; C.row_aux = L.row_aux;
-        if (L.y_dtype == GNNAGG_DTYPE_F32) return launch_combine_gcn(C, pick_geometry(L.feat, L.partial, L.y, nullptr, L.feat), is_max, stream);
-        const int cv = align_class(L.feat, L.y, ysize, 4);
-        return launch_combine_gcn(C, Geometry{cv, 64, ceil_div(L.feat, 64 * cv)}, is_max, stream, nullptr, nullptr, 0, nullptr, true);
-    }
+    int grid = 0;
+    if (int rc = plan_grid(a, g, gpb, L.tile, L.hubs.n_slots, L.t0_cost_prefix, &grid)) return rc;
     if (L.probe) {
         if (is_max) return fail(GNNAGG_ERR_ARG, "probe: sum/mean only");
         a.probe_sink = device_probe_sink();
         if (!a.probe_sink) return fail(GNNAGG_ERR_HIP, "probe: no sink");
-        if (grid > 0) {
-#define CALL_PROBE hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false, true>), dim3(grid), dim3(blk), 0, stream, a);
-            if (u4 && g.group == 32) hipLaunchKernelGGL((k_gcn_plan<4, 32, false, true, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else if (u4) hipLaunchKernelGGL((k_gcn_plan<4, 64, false, true, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else DISPATCH_GEOM(g, CALL_PROBE)
-#undef CALL_PROBE
-            HIP_TRY(hipGetLastError());
-        }
-        return GNNAGG_OK;
-    }
-    if (fuse_nn) {
-        NnArgs w;
-        w.weight = L.nn_weight; w.out = L.nn_out; w.n_out = L.nn_cols;
-        if (grid > 0) {
-#define CALL_PLAN_NN                                                                                                 \
-            if (is_max) hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a, w);     \
-            else        hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, false>), dim3(grid), dim3(blk), 0, stream, a, w);
-            DISPATCH_GEOM(g, CALL_PLAN_NN)
-#undef CALL_PLAN_NN
-            HIP_TRY(hipGetLastError());
-        }
-        GcnLaunch C;
-        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
-        if (hubs_in_kernel) return GNNAGG_OK;
-        return launch_combine_gcn(C, g, is_max, stream, L.nn_weight, L.nn_out, L.nn_cols);  // hubs: product in the combine
     }
     if (grid > 0) {
-#define CALL_PLAN                                                                                            \
-        if (is_max) hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a);        \
-        else        hipLaunchKernelGGL((k_gcn_plan<VEC, GROUP, false>), dim3(grid), dim3(blk), 0, stream, a);
-        if (u4 && g.group == 32) {
-            if (is_max) hipLaunchKernelGGL((k_gcn_plan<4, 32, true, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else        hipLaunchKernelGGL((k_gcn_plan<4, 32, false, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-        } else if (u4) {
-            if (is_max) hipLaunchKernelGGL((k_gcn_plan<4, 64, true, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-            else        hipLaunchKernelGGL((k_gcn_plan<4, 64, false, false, 4>), dim3(grid), dim3(blk), 0, stream, a);
-        } else DISPATCH_GEOM(g, CALL_PLAN)
+#define CALL_PLAN(PROBE, TXT, TYPED) launch_plan_geom<VEC, GROUP, PROBE, TXT, TYPED>(a, is_max, u4, grid, blk, stream)
+#define CALL_PLAN_NN                                                                                                 \
+        if (is_max) hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a, w);     \
+        else        hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, false>), dim3(grid), dim3(blk), 0, stream, a, w);
+        if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+            DISPATCH_GEOM_16BIT(g, CALL_PLAN(false, __bf16, true))
+        } else if (typed) {
+            DISPATCH_GEOM(g, CALL_PLAN(false, float, true))
+        } else if (L.probe) {
+            DISPATCH_GEOM(g, CALL_PLAN(true, float, false))
+        } else if (fuse_nn) {
+            NnArgs w;
+            w.weight = L.nn_weight; w.out = L.nn_out; w.n_out = L.nn_cols;
+            DISPATCH_GEOM(g, CALL_PLAN_NN)
+        } else {
+            DISPATCH_GEOM(g, CALL_PLAN(false, float, false))
+        }
+#undef CALL_PLAN_NN
 #undef CALL_PLAN
         HIP_TRY(hipGetLastError());
     }
-    GcnLaunch C;
-    C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
-    C.accumulate = L.accumulate; C.relu = L.relu; C.row_aux = L.row_aux;
-    const int rc = hubs_in_kernel ? GNNAGG_OK : launch_combine_gcn(C, g, is_max, stream, nullptr, nullptr, 0, &L.tile);
-    if (rc || !want_nn) return rc;
+    if (L.probe) return GNNAGG_OK;
+    if (!hubs_in_kernel) {   // hubs the kernel does not fold: the ordered combine of their fp32 partial rows
+        GcnLaunch C;
+        C.wl = L.hubs; C.row_ptr = L.row_ptr; C.y = static_cast<float *>(L.y); C.partial = L.partial; C.feat = L.feat; C.reduce = L.reduce;
+        C.accumulate = L.accumulate; C.relu = L.relu; C.row_aux = L.row_aux;
+        int rc;
+        if (L.y_dtype == GNNAGG_DTYPE_BF16) {
+            // typed launches: on fp32 lanes of the combine's own (the partial rows are [slot][F]: any column tiling reads them), storing Y in its type
+            const int cv = align_class(L.feat, L.y, ysize, 4);
+            rc = launch_combine_gcn(C, Geometry{cv, 64, ceil_div(L.feat, 64 * cv)}, is_max, stream, nullptr, nullptr, 0, nullptr, true);
+        } else if (typed) {
+            rc = launch_combine_gcn(C, pick_geometry(L.feat, L.partial, L.y, nullptr, L.feat), is_max, stream);
+        } else if (fuse_nn) {
+            rc = launch_combine_gcn(C, g, is_max, stream, L.nn_weight, L.nn_out, L.nn_cols);  // hubs: product in the combine
+        } else {
+            rc = launch_combine_gcn(C, g, is_max, stream, nullptr, nullptr, 0, &L.tile);
+        }
+        if (rc) return rc;
+    }
+    if (!want_nn || fuse_nn) return GNNAGG_OK;
     return launch_dense_nn(static_cast<const float *>(L.y), L.nn_weight, L.nn_out, L.num_rows, L.nn_cols, L.feat, stream);
 }
 

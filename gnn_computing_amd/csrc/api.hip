@@ -127,8 +127,37 @@ static int build_grouping(Ctx *c, Schedule &s, int ng, int kind)
     return finalize_schedule(c, s);
 }
 
-static int parts_for_cols(const Ctx *c, long cols);
-static int pick_chunk(const Ctx *c);
+static int pick_chunk(const Ctx *c)
+{
+    // long rows become work items of <= chunk edges: small enough that the hub rows of a
+    // power-law graph spread over many wavefronts, large enough that partial-sum traffic
+    // (2 * F * 4 bytes per extra item) stays a few percent of the gather traffic.
+    int chunk = 64;  // measured on arxiv-shaped input: 64..96 beats 32 (fewer partial rows) and 128+ (tail)
+    while (chunk < 512 && chunk < 2 * c->avg_deg()) chunk <<= 1;
+    return chunk;
+}
+
+// Source-partitioned ("2-D blocked") balanced mode.  On high-degree graphs the aggregation is bound by L2-miss traffic: rows
+// gathered from the Infinity Cache or HBM arrive at 6.3-7.9 TB/s, rows gathered from an XCD's own 4 MB L2 at 24 TB/s
+// (256-byte segments; scripts/micro/gather_ceiling.hip, profiles/r02/gather_ceiling.txt).  The reference's locality
+// schedule (graph_schedule.h:156-243: per column range, per row, the sub-row of edges whose source falls in the range, cut
+// every NG edges) supplies the order; two things make the slice an L2 walks actually fit:
+//  * the features are processed one COLUMN TILE of tile_w floats at a time (tile-major block order), so the slice is
+//    (rows of a range) x (tile_w * 4 bytes), not (rows of a range) x (row pitch);
+//  * the number of ranges is chosen from the slice size, P = ceil(columns * tile_w * 4 / slice bytes), bounded so that a
+//    (row, range) sub-row keeps about a dozen edges on average (every (row, range, tile) costs one partial row).
+// Per-column summation order does not depend on the tiling: partials of a row are folded in ascending group order exactly
+// as the reference's arrays list them (restated by orc_locality_schedule + orc_gcn_grouped_seg with seg = 0).
+// Round 1 (16 ranges x full rows, 35 MB slices): reddit-shaped SAGE F=602 36.9 -> 28.8 ms, L2 hit 0.08 -> 0.41.
+// GNNAGG_PARTITIONS = 0 / N overrides; GNNAGG_TILE_W, GNNAGG_SLICE_KB tune the slice.
+static int parts_for_cols(const Ctx *c, long cols)
+{
+    const long slice = std::max(1L, (long)c->opt_slice_kb) * 1024;
+    long p = (cols * c->opt_tile_w * 4 + slice - 1) / slice;
+    p = std::min<long>(p, std::max(1, c->avg_deg() / 12));
+    return (int)std::max(1L, std::min(p, 1024L));
+}
+
 static double wall_seconds()
 {
     timespec ts;
@@ -266,7 +295,6 @@ static int build_plan_into(Ctx *c, BalancedPlan &p, int chunk, bool describe_in_
 }
 
 static int build_balanced_plan(Ctx *c, int chunk) { return build_plan_into(c, c->plan, chunk, true, nullptr); }
-static int pick_chunk(const Ctx *c);
 // the plan alone, leaving sched[1] (a source-partitioned schedule) untouched: GNNAGG_FLAG_ACCUMULATE on such a handle
 static int build_balanced_plan_keep(Ctx *c) { return build_plan_into(c, c->plan, pick_chunk(c), false, nullptr); }
 
@@ -359,37 +387,6 @@ static int build_rows_plan(Ctx *c, bool medium_ok = true)
     return GNNAGG_OK;
 }
 
-static int pick_chunk(const Ctx *c)
-{
-    // long rows become work items of <= chunk edges: small enough that the hub rows of a
-    // power-law graph spread over many wavefronts, large enough that partial-sum traffic
-    // (2 * F * 4 bytes per extra item) stays a few percent of the gather traffic.
-    int chunk = 64;  // measured on arxiv-shaped input: 64..96 beats 32 (fewer partial rows) and 128+ (tail)
-    while (chunk < 512 && chunk < 2 * c->avg_deg()) chunk <<= 1;
-    return chunk;
-}
-
-// Source-partitioned ("2-D blocked") balanced mode.  On high-degree graphs the aggregation is bound by L2-miss traffic: rows
-// gathered from the Infinity Cache or HBM arrive at 6.3-7.9 TB/s, rows gathered from an XCD's own 4 MB L2 at 24 TB/s
-// (256-byte segments; scripts/micro/gather_ceiling.hip, profiles/r02/gather_ceiling.txt).  The reference's locality
-// schedule (graph_schedule.h:156-243: per column range, per row, the sub-row of edges whose source falls in the range, cut
-// every NG edges) supplies the order; two things make the slice an L2 walks actually fit:
-//  * the features are processed one COLUMN TILE of tile_w floats at a time (tile-major block order), so the slice is
-//    (rows of a range) x (tile_w * 4 bytes), not (rows of a range) x (row pitch);
-//  * the number of ranges is chosen from the slice size, P = ceil(columns * tile_w * 4 / slice bytes), bounded so that a
-//    (row, range) sub-row keeps about a dozen edges on average (every (row, range, tile) costs one partial row).
-// Per-column summation order does not depend on the tiling: partials of a row are folded in ascending group order exactly
-// as the reference's arrays list them (restated by orc_locality_schedule + orc_gcn_grouped_seg with seg = 0).
-// Round 1 (16 ranges x full rows, 35 MB slices): reddit-shaped SAGE F=602 36.9 -> 28.8 ms, L2 hit 0.08 -> 0.41.
-// GNNAGG_PARTITIONS = 0 / N overrides; GNNAGG_TILE_W, GNNAGG_SLICE_KB tune the slice.
-static int parts_for_cols(const Ctx *c, long cols)
-{
-    const long slice = std::max(1L, (long)c->opt_slice_kb) * 1024;
-    long p = (cols * c->opt_tile_w * 4 + slice - 1) / slice;
-    p = std::min<long>(p, std::max(1, c->avg_deg() / 12));
-    return (int)std::max(1L, std::min(p, 1024L));
-}
-
 // 0: chunked plan; -1: source-partitioned with the range count taken from the column count; N > 0: N ranges
 static int auto_partitions(const Ctx *c)
 {
@@ -397,8 +394,6 @@ static int auto_partitions(const Ctx *c)
     if (c->opt_partitions >= 0) return c->opt_partitions;
     return c->avg_deg() >= c->opt_part_min_deg ? -1 : 0;
 }
-
-static int build_locality(Ctx *c, Schedule &s, int par_num, int ng, int total_v, int kind, bool keep_eid = false);
 
 static int build_spans(Ctx *c, Schedule &s);
 
@@ -556,8 +551,6 @@ static int refresh_partitioned_val(Ctx *c, Schedule *s)
     if (rc) return rc;
     return launch_permute_val(s->eperm.p, c->d_val, s->val_s.p, (int)kept, c->stream);
 }
-
-static int get_sched(Ctx *c, int mode, Schedule **out);
 
 // Moves a handle from the source-partitioned order to the chunked plan for good (its scratch does not fit):
 // gnnagg_balanced_partitions reports 0 from then on and sched[1] describes the chunked order again.
@@ -844,9 +837,137 @@ static int build_rows_blocked_host(Ctx *c, int ntiles_hint)
     return GNNAGG_OK;
 }
 
-static int run_rows_blocked(Ctx *c, const float *x, float *y, int feat, int reduce, int flags, const NnRequest *nn, bool *used)
+// ---- launch recipes the run paths share
+
+// The auxiliary stream (created on first use) starts behind what the handle's stream holds so far ...
+static int fork_aux(Ctx *c)
+{
+    if (!c->aux_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+    HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
+    return GNNAGG_OK;
+}
+// ... and the handle's stream goes on behind what the auxiliary stream held when ev_join was recorded (launch_rows_class)
+static int join_aux(Ctx *c)
+{
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    return GNNAGG_OK;
+}
+
+// One class of rows ({beg, end, row, 0} descriptors, heaviest first) on the workgroup-per-row kernel k_gcn_rows_long, for the GCN request
+// or the GAT request (the other is null).  on_aux: forked to the auxiliary stream, beside what the handle's stream runs until join_aux()
+// (hub rows: disjoint rows of y).  One function for both flavours so that the launch descriptor is filled in one place; exactly one of
+// gcn / gat is given.
+static int launch_rows_class(Ctx *c, const int *desc, int n, int medium, bool on_aux, const GcnRequest *gcn, const GatRequest *gat)
+{
+    int rc;
+    if (on_aux && (rc = fork_aux(c))) return rc;
+    GcnRowsLongLaunch R;
+    R.tile_w = c->opt_hub_tile;
+    R.r1 = desc; R.n1 = n; R.idx = c->d_idx; R.medium = medium;
+    if (gcn) {
+        R.val = c->d_val; R.x = gcn->x; R.y = gcn->y; R.feat = gcn->feat; R.reduce = gcn->reduce;
+        R.relu = (gcn->flags & GNNAGG_FLAG_RELU) ? 1 : 0;
+    } else {
+        R.x = gat->x; R.y = gat->y; R.feat = gat->feat; R.att = gat->att; R.heads = gat->heads; R.slope = gat->slope;
+    }
+    if ((rc = launch_gcn_rows_long(R, on_aux ? c->aux_stream : c->stream))) return rc;
+    if (on_aux) HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
+    return GNNAGG_OK;
+}
+
+// What a launch of a plan kernel takes from a BalancedPlan, GCN and GAT alike: the descriptors and their XCD costs (degree-sorted where
+// the row bytes ask for it), the hubs, their partial-row scratch, the counters of the in-kernel hub fold, 4 gathers per batch.  (GAT
+// reserves its denominator scratch after this, i.e. after the hub counters: only the first, allocating call sees that order.)
+static int fill_plan_launch(Ctx *c, BalancedPlan &p, int feat, int x_dtype, int y_dtype, PlanLaunch &P)
+{
+    int rc;
+    P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk;
+    P.t0_cost_prefix = p.t0_cost_prefix.data();
+    if (wants_sorted_rows(c, (long)feat * (x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4))) {
+        if ((rc = ensure_sorted_rows(c, p))) return rc;
+        if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
+    }
+    P.hubs.mrow_id = p.mrow_id.p; P.hubs.mrow_ptr = p.mrow_ptr.p; P.hubs.n_mrows = p.n_mrows;
+    P.hubs.n_slots = p.n_slots; P.hubs.big_rows = p.big_rows.p; P.hubs.n_big = p.n_big;
+    P.idx = c->d_idx; P.feat = feat; P.x_dtype = x_dtype; P.y_dtype = y_dtype; P.xcd_remap = c->xcd_remap;
+    if (p.n_slots > 0) {
+        if ((rc = c->partial.reserve((size_t)p.n_slots * feat))) return rc;
+        P.partial = c->partial.p;
+    }
+    if (p.n_mrows > 0 && c->inkernel_combine) {
+        if ((rc = reserve_hub_counters(c, p.n_mrows, feat, &P.hub_count_stride))) return rc;
+        P.slot_hub = p.slot_hub.p; P.hub_count = c->hub_count.p;
+    }
+    P.unroll = 4;
+    return GNNAGG_OK;
+}
+
+// The image of X a run on a blocked order gathers from: the caller's rows, or their column-tiled copy (rebuilt by every run)
+static int tiled_x(Ctx *c, const Schedule &s, const TiledRun &tr, const float *x, int feat, const float **xin)
+{
+    *xin = x;
+    if (!tr.retile) return GNNAGG_OK;
+    *xin = c->xt.p;
+    return launch_tile_x(x, c->xt.p, s.total_cols, feat, tr.spec.tile_w, c->stream);
+}
+
+// What a SpanLaunch takes from a Schedule and the run's tiles.  Balanced order: all spans, every group owns a partial row (slot = group
+// index: sequential flushes) and the ordered combine's lists.  chain (canonical rows mode, rb.sched): the chains pass through the rows of
+// the Yt image; the caller names the spans of one source range per launch.  (val_s is the GCN kernels' field: a GAT handle has no edge
+// values, c->d_val is null there and the field stays null, as launch_gat_span expects.)
+static void fill_span_launch(SpanLaunch &S, const Ctx *c, const Schedule &s, const TiledRun &tr, bool chain)
+{
+    S.chain = chain ? 1 : 0;
+    S.ptr_s = s.ptr_s.p; S.idx_f = chain ? c->rb.idx_f.p : s.idx_f.p; S.val_s = c->d_val ? s.val_s.p : nullptr; S.target = s.target.p;
+    S.n_groups = chain ? c->V : s.num_target;   // chain: rows of the Yt image (the launcher sizes the partial window from it)
+    S.row_ptr = c->d_ptr; S.x_rows = s.total_cols; S.partial = chain ? c->yt.p : c->partial.p;
+    S.tile = tr.spec;
+    S.tile.p_tile_stride = (long)S.n_groups * tr.spec.tile_w;
+    if (chain) return;
+    S.span_g = s.span_g.p; S.n_spans = s.n_spans; S.span_cost_prefix = s.span_cost_prefix.data();
+    S.crows = s.crows.p; S.n_crows = s.n_crows; S.rg_ptr = s.rg_ptr.p; S.rg_idx = s.rg_idx.p;
+    S.empty_rows = s.empty_rows.p; S.n_empty = s.n_empty;
+}
+
+// Before a balanced run on the 2-D blocked order launches anything.  A run that needs the descriptor form of an order built on the
+// device has it rebuilt by the host builder, which makes both forms; the span form keeps one partial row per group, the descriptor form
+// one per slot (den_per_row floats of denominators beside each: GAT heads, GCN 0); scratch that does not fit demotes the handle to the
+// chunked plan.  *redispatch: the handle's order changed, run the request again.  Last, the permuted copy of the edge values is brought up to
+// date (GCN handles only: refresh_partitioned_val returns at once for a GAT handle).
+static int prepare_blocked(Ctx *c, Schedule &s, TiledRun &tr, bool span_run, int den_per_row, bool *redispatch)
+{
+    int rc;
+    *redispatch = true;
+    if (!span_run && s.gpu_built) {
+        c->force_host_plan = 1;
+        return build_partitioned(c, c->partitions);
+    }
+    const int prows = span_run ? s.num_target : s.n_slots;
+    if (span_run) tr.partial_floats = (size_t)prows * tr.spec.tile_w * tr.ntiles;
+    if ((rc = reserve_partitioned_scratch(c, tr.partial_floats, (size_t)prows * den_per_row, tr.xt_floats, redispatch)) || *redispatch) return rc;
+    return refresh_partitioned_val(c, &s);
+}
+
+// the error of a 16-bit run whose order leaves the plan kernels (kind: "gcn" / "gat"; note: what that flavour adds on "fast_scheduled")
+static int fail_typed_order(const char *kind, int x_dtype, int y_dtype, const char *note)
+{
+    return fail(GNNAGG_ERR_ARG, std::string("gnnagg_") + kind + "_run_typed (x " + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                                    (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
+                                    "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
+                                    "neighbor-grouping schedule / \"fast_scheduled\" = 1" + note + " for GNNAGG_MODE_SCHEDULED");
+}
+
+static int run_rows_blocked(Ctx *c, const GcnRequest &r, bool *used)
 {
     *used = false;
+    const float *x = r.x;
+    float *y = r.y;
+    const int feat = r.feat, reduce = r.reduce, relu = (r.flags & GNNAGG_FLAG_RELU) ? 1 : 0;
     Ctx::RowsBlocked &rb = c->rb;
     int rc;
     if (!rb.tried && (rc = build_rows_blocked(c, (feat + 63) / 64))) return rc;
@@ -870,37 +991,12 @@ static int run_rows_blocked(Ctx *c, const float *x, float *y, int feat, int redu
     // the rows left out of the chained launches, whole, on the workgroup-per-row kernel: beside the launches on the auxiliary stream
     // (disjoint rows of y), or behind them on this stream ("aux_stream" = 0)
     const bool fork = rb.n1 > 0 && c->use_aux_stream;
-    auto hub_rows = [&](hipStream_t st) -> int {
-        GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-        R.r1 = rb.r1.p; R.n1 = rb.n1; R.idx = c->d_idx; R.val = c->d_val; R.x = x; R.y = y; R.feat = feat; R.reduce = reduce;
-        R.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
-        return launch_gcn_rows_long(R, st);
-    };
-    if (fork) {
-        if (!c->aux_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-        if ((rc = hub_rows(c->aux_stream))) return rc;
-        HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
-    }
-    const float *xin = x;
-    if (tr.retile) {
-        if ((rc = launch_tile_x(x, c->xt.p, s.total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-        xin = c->xt.p;
-    }
-    if ((rc = launch_zero_words(c->yt.p, yt_floats, c->stream))) return rc;
+    if (fork && (rc = launch_rows_class(c, rb.r1.p, rb.n1, 0, true, &r, nullptr))) return rc;
     SpanLaunch S;
-    S.chain = 1;
-    S.ptr_s = s.ptr_s.p; S.idx_f = rb.idx_f.p; S.val_s = c->d_val ? s.val_s.p : nullptr; S.target = s.target.p;
-    S.n_groups = c->V;   // rows of the Yt image (the launcher sizes the partial window from it)
-    S.row_ptr = c->d_ptr; S.x = xin; S.x_rows = s.total_cols; S.y = y; S.partial = c->yt.p; S.feat = feat; S.reduce = GNNAGG_REDUCE_SUM;
-    S.tile = tr.spec;
-    S.tile.p_tile_stride = (long)c->V * tr.spec.tile_w;
+    fill_span_launch(S, c, s, tr, true);
+    if ((rc = tiled_x(c, s, tr, x, feat, &S.x))) return rc;
+    if ((rc = launch_zero_words(c->yt.p, yt_floats, c->stream))) return rc;
+    S.y = y; S.feat = feat; S.reduce = GNNAGG_REDUCE_SUM;
     for (int p = 0; p < s.par_num; ++p) {
         const int s0 = rb.span0[(size_t)p], s1 = rb.span0[(size_t)p + 1];
         if (s1 == s0) continue;
@@ -908,12 +1004,13 @@ static int run_rows_blocked(Ctx *c, const float *x, float *y, int feat, int redu
         if ((rc = launch_gcn_span(S, c->stream))) return rc;
     }
     if ((rc = launch_untile_y(c->yt.p, y, c->d_ptr, rb.n1 > 0 ? rb.hub_mask.p : nullptr, c->V, feat, tr.spec.tile_w, reduce == GNNAGG_REDUCE_MEAN,
-                              (flags & GNNAGG_FLAG_RELU) ? 1 : 0, c->stream)))
+                              relu, c->stream)))
         return rc;
-    if (fork) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    else if (rb.n1 > 0 && (rc = hub_rows(c->stream))) return rc;
+    if (fork) rc = join_aux(c);
+    else if (rb.n1 > 0) rc = launch_rows_class(c, rb.r1.p, rb.n1, 0, false, &r, nullptr);
+    if (rc) return rc;
     *used = true;
-    if (nn) return launch_dense_nn(y, nn->weight, nn->out, c->V, nn->cols, feat, c->stream);
+    if (r.nn) return launch_dense_nn(y, r.nn->weight, r.nn->out, c->V, r.nn->cols, feat, c->stream);
     return GNNAGG_OK;
 }
 
@@ -931,9 +1028,12 @@ static bool sched_keeps_every_edge(const Ctx *c)
 // k_untile_y divides.  Rows with a sub-row too long for one lane group go whole to the workgroup-per-row kernel's GAT flavour (head
 // width % 32 == 0); graphs where that does not hold, head widths the span kernel does not tile, and callers that ask for newval stay
 // on the row kernels.
-static int run_rows_blocked_gat(Ctx *c, const float *x, const float *att, float *y, int feat, int heads, float slope, bool *used)
+static int run_rows_blocked_gat(Ctx *c, const GatRequest &r, bool *used)
 {
     *used = false;
+    const float *x = r.x, *att = r.att;
+    float *y = r.y;
+    const int feat = r.feat, heads = r.heads;
     if (heads <= 0 || feat % heads != 0) return GNNAGG_OK;
     const int dhead = feat / heads;
     Ctx::RowsBlocked &rb = c->rb;
@@ -959,39 +1059,15 @@ static int run_rows_blocked_gat(Ctx *c, const float *x, const float *att, float 
         }
     }
     const bool fork = rb.n1 > 0 && c->use_aux_stream;
-    auto hub_rows = [&](hipStream_t st) -> int {
-        GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-        R.r1 = rb.r1.p; R.n1 = rb.n1; R.idx = c->d_idx; R.x = x; R.y = y; R.feat = feat; R.att = att; R.heads = heads; R.slope = slope;
-        return launch_gcn_rows_long(R, st);
-    };
-    if (fork) {
-        if (!c->aux_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-        HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-        if ((rc = hub_rows(c->aux_stream))) return rc;
-        HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
-    }
+    if (fork && (rc = launch_rows_class(c, rb.r1.p, rb.n1, 0, true, nullptr, &r))) return rc;
     GatSpanLaunch G;
     SpanLaunch &S = G.s;
-    S.chain = 1;
-    S.x = x;
-    if (tr.retile) {
-        if ((rc = launch_tile_x(x, c->xt.p, s.total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-        S.x = c->xt.p;
-    }
+    fill_span_launch(S, c, s, tr, true);
+    if ((rc = tiled_x(c, s, tr, x, feat, &S.x))) return rc;
     if ((rc = launch_tile_att(att, c->att_t.p, c->att_t.p + half, arows, heads, ht, c->stream))) return rc;
     if ((rc = launch_zero_words(c->yt.p, yt_floats, c->stream)) || (rc = launch_zero_words(c->den_t.p, den_floats, c->stream))) return rc;
-    S.ptr_s = s.ptr_s.p; S.idx_f = rb.idx_f.p; S.target = s.target.p;
-    S.n_groups = c->V;   // rows of the Yt image
-    S.row_ptr = c->d_ptr; S.x_rows = s.total_cols; S.y = y; S.partial = c->yt.p; S.feat = feat;
-    S.tile = tr.spec;
-    S.tile.p_tile_stride = (long)c->V * tr.spec.tile_w;
-    G.att = att; G.as_t = c->att_t.p; G.ac_t = c->att_t.p + half; G.att_rows = arows; G.heads = heads; G.slope = slope;
+    S.y = y; S.feat = feat;
+    G.att = att; G.as_t = c->att_t.p; G.ac_t = c->att_t.p + half; G.att_rows = arows; G.heads = heads; G.slope = r.slope;
     G.den_t = c->den_t.p; G.den_rows = c->V;
     for (int p = 0; p < s.par_num; ++p) {
         const int s0 = rb.span0[(size_t)p], s1 = rb.span0[(size_t)p + 1];
@@ -1000,16 +1076,21 @@ static int run_rows_blocked_gat(Ctx *c, const float *x, const float *att, float 
         if ((rc = launch_gat_span(G, c->stream))) return rc;
     }
     if ((rc = launch_untile_y_gat(c->yt.p, c->den_t.p, y, rb.n1 > 0 ? rb.hub_mask.p : nullptr, c->V, feat, tr.spec.tile_w, ht, dhead, c->stream))) return rc;
-    if (fork) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    else if (rb.n1 > 0 && (rc = hub_rows(c->stream))) return rc;
+    if (fork) rc = join_aux(c);
+    else if (rb.n1 > 0) rc = launch_rows_class(c, rb.r1.p, rb.n1, 0, false, nullptr, &r);
+    if (rc) return rc;
     *used = true;
     return GNNAGG_OK;
 }
 
-int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags, const NnRequest *nn, int probe, int x_dtype,
-            int y_dtype)
+int gcn_run(Ctx *c, const GcnRequest &r)
 {
-    const bool typed = x_dtype != GNNAGG_DTYPE_F32 || y_dtype != GNNAGG_DTYPE_F32;
+    const float *x = r.x;
+    float *y = r.y;
+    const int feat = r.feat, reduce = r.reduce, flags = r.flags, probe = r.probe, relu = (r.flags & GNNAGG_FLAG_RELU) ? 1 : 0;
+    const NnRequest *nn = r.nn;
+    int mode = r.mode;
+    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32;
     if (typed && (nn || probe)) return fail(GNNAGG_ERR_ARG, "16-bit features: run_with_nn and the gather probe are fp32 only");
     if ((flags & GNNAGG_FLAG_ACCUMULATE) && (mode != GNNAGG_MODE_BALANCED || (reduce != GNNAGG_REDUCE_SUM && !c->row_aux) || !c->use_plan))
         return fail(GNNAGG_ERR_ARG, "GNNAGG_FLAG_ACCUMULATE needs GNNAGG_MODE_BALANCED and GNNAGG_REDUCE_SUM (mean / max: gnnagg_set_row_aux first)");
@@ -1027,7 +1108,7 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
     if (mode == GNNAGG_MODE_SCHEDULED && c->fast_scheduled && c->sched[0].valid && sched_keeps_every_edge(c)) mode = GNNAGG_MODE_BALANCED;
     if (mode == GNNAGG_MODE_ROWS && c->opt_rows_blocked && c->tiled && c->use_plan && reduce != GNNAGG_REDUCE_MAX && !probe) {
         bool used = false;   // canonical chains on the blocked order where the graph allows it (sorted rows, high degree)
-        const int rcb = run_rows_blocked(c, x, y, feat, reduce, flags, nn, &used);
+        const int rcb = run_rows_blocked(c, r, &used);
         if (rcb || used) return rcb;
     }
     Schedule *s = nullptr;
@@ -1037,41 +1118,19 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
     const bool acc_on_partitioned = ((flags & GNNAGG_FLAG_ACCUMULATE) || aux_run || typed) && c->partitions > 0;
     const bool on_plan = (mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || acc_on_partitioned)) ||
                          (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid);
-    if (typed && !on_plan)
-        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gcn_run_typed (x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
-                                        (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
-                                        "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
-                                        "neighbor-grouping schedule / \"fast_scheduled\" = 1 for GNNAGG_MODE_SCHEDULED");
+    if (typed && !on_plan) return fail_typed_order("gcn", r.x_dtype, r.y_dtype, "");
     if (acc_on_partitioned && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
     if (on_plan) {
-        BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
         GcnPlanLaunch P;
-        P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk;
-        P.t0_cost_prefix = p.t0_cost_prefix.data();
-        if (wants_sorted_rows(c, (long)feat * (x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4))) {
-            if ((rc = ensure_sorted_rows(c, p))) return rc;
-            if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
-        }
-        P.hubs.mrow_id = p.mrow_id.p; P.hubs.mrow_ptr = p.mrow_ptr.p; P.hubs.n_mrows = p.n_mrows;
-        P.hubs.n_slots = p.n_slots; P.hubs.big_rows = p.big_rows.p; P.hubs.n_big = p.n_big;
-        P.row_ptr = c->d_ptr; P.idx = c->d_idx; P.val = c->d_val; P.x = x; P.y = y; P.feat = feat; P.reduce = reduce;
-        P.x_dtype = x_dtype; P.y_dtype = y_dtype;
-        P.xcd_remap = c->xcd_remap; P.accumulate = (flags & GNNAGG_FLAG_ACCUMULATE) ? 1 : 0; P.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
+        if ((rc = fill_plan_launch(c, mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched, feat, r.x_dtype, r.y_dtype, P))) return rc;
+        P.row_ptr = c->d_ptr; P.val = c->d_val; P.x = x; P.y = y; P.reduce = reduce;
+        P.accumulate = (flags & GNNAGG_FLAG_ACCUMULATE) ? 1 : 0; P.relu = relu;
         P.row_aux = aux_run ? c->row_aux : nullptr;
         P.num_rows = c->V;
-        if (p.n_slots > 0) {
-            if ((rc = c->partial.reserve((size_t)p.n_slots * feat))) return rc;
-            P.partial = c->partial.p;
-        }
         if (nn) {
             P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols;
         }
-        if (p.n_mrows > 0 && c->inkernel_combine) {
-            if ((rc = reserve_hub_counters(c, p.n_mrows, feat, &P.hub_count_stride))) return rc;
-            P.slot_hub = p.slot_hub.p; P.hub_count = c->hub_count.p;
-        }
         P.probe = probe;
-        P.unroll = 4;
         return launch_gcn_plan(P, c->stream);
     }
     if (mode == GNNAGG_MODE_BALANCED && c->partitions > 0 && c->plan_part.valid && c->part_descriptors) {
@@ -1081,45 +1140,27 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
         BalancedPlan &p = c->plan_part;
         TiledRun tr = plan_tiles(c, *s, x, y, feat, 4);
         const bool span_run = tr.spec.on && s->n_spans > 0;
-        if (!span_run && s->gpu_built) {   // the descriptor form is needed after all: the host builder makes both
-            c->force_host_plan = 1;
-            if ((rc = build_partitioned(c, c->partitions))) return rc;
-            return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe, x_dtype, y_dtype);
-        }
-        if (span_run) {  // every group owns a partial row (slot = group index): sequential flushes
-            tr.spec.p_tile_stride = (long)s->num_target * tr.spec.tile_w;
-            tr.partial_floats = (size_t)s->num_target * tr.spec.tile_w * tr.ntiles;
-        }
-        bool demoted = false;
-        if ((rc = reserve_partitioned_scratch(c, tr.partial_floats, 0, tr.xt_floats, &demoted))) return rc;
-        if (demoted) return gcn_run(c, x, y, feat, mode, reduce, flags, nn, probe, x_dtype, y_dtype);
-        if ((rc = refresh_partitioned_val(c, s))) return rc;
+        bool redispatch = false;
+        if ((rc = prepare_blocked(c, *s, tr, span_run, 0, &redispatch))) return rc;
+        if (redispatch) return gcn_run(c, r);
         if (span_run) {
             SpanLaunch S;
-            S.span_g = s->span_g.p; S.n_spans = s->n_spans; S.span_cost_prefix = s->span_cost_prefix.data();
-            S.ptr_s = s->ptr_s.p; S.idx_f = s->idx_f.p; S.val_s = c->d_val ? s->val_s.p : nullptr; S.target = s->target.p;
-            S.n_groups = s->num_target; S.crows = s->crows.p; S.n_crows = s->n_crows; S.rg_ptr = s->rg_ptr.p; S.rg_idx = s->rg_idx.p;
-            S.empty_rows = s->empty_rows.p; S.n_empty = s->n_empty; S.row_ptr = c->d_ptr;
-            S.x = x; S.x_rows = s->total_cols; S.y = y; S.partial = c->partial.p; S.feat = feat; S.reduce = reduce; S.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
-            S.tile = tr.spec; S.probe = probe;
-            if (tr.retile) {
-                if ((rc = launch_tile_x(x, c->xt.p, s->total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-                S.x = c->xt.p;
-            }
+            fill_span_launch(S, c, *s, tr, false);
+            S.y = y; S.feat = feat; S.reduce = reduce; S.relu = relu; S.probe = probe;
+            if ((rc = tiled_x(c, *s, tr, x, feat, &S.x))) return rc;
             if ((rc = launch_gcn_span(S, c->stream)) || !nn || probe) return rc;
             return launch_dense_nn(y, nn->weight, nn->out, c->V, nn->cols, feat, c->stream);
         }
         GcnPlanLaunch P;
         P.t0 = p.t0.p; P.n0 = p.n0; P.chunk = p.chunk; P.t0_cost_prefix = p.t0_cost_prefix.data();
         P.hubs = s->worklist();
-        P.row_ptr = c->d_ptr; P.idx = s->idx_s.p; P.val = c->d_val ? s->val_s.p : nullptr; P.x = x; P.y = y; P.feat = feat; P.reduce = reduce;
-        P.xcd_remap = c->xcd_remap; P.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0; P.num_rows = c->V; P.t0_partials = 1;
+        P.row_ptr = c->d_ptr; P.idx = s->idx_s.p; P.val = c->d_val ? s->val_s.p : nullptr; P.y = y; P.feat = feat; P.reduce = reduce;
+        P.xcd_remap = c->xcd_remap; P.relu = relu; P.num_rows = c->V; P.t0_partials = 1;
         P.partial = c->partial.p;
         P.tile = tr.spec;
-        if (tr.retile) {
-            if ((rc = launch_tile_x(x, c->xt.p, s->total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-            P.x = c->xt.p;
-        }
+        const float *xin;
+        if ((rc = tiled_x(c, *s, tr, x, feat, &xin))) return rc;
+        P.x = xin;
         if (nn) { P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols; }
         P.probe = probe;
         return launch_gcn_plan(P, c->stream);
@@ -1129,40 +1170,22 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
         if (!c->rows_plan.valid && (rc = build_rows_plan(c))) return rc;
         RowsPlan &p = c->rows_plan;
         const bool fork = p.n1 > 0 && c->use_aux_stream;
-        if (p.n1 > 0) {  // long rows (disjoint output rows): forked to the auxiliary stream, or first on this one
-            if (fork) {
-                if (!c->aux_stream) {
-                    HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-                    HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                    HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-                }
-                HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-            }
-            GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-            R.r1 = p.r1.p; R.n1 = p.n1; R.idx = c->d_idx; R.val = c->d_val; R.x = x; R.y = y; R.feat = feat; R.reduce = reduce;
-            R.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
-            if ((rc = launch_gcn_rows_long(R, fork ? c->aux_stream : c->stream))) return rc;
-            if (fork) HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
-        }
-        if (p.n2 > 0) {  // medium rows: ahead of the short rows on this stream (heaviest first; many workgroups per CU)
-            GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-            R.r1 = p.r2.p; R.n1 = p.n2; R.idx = c->d_idx; R.val = c->d_val; R.x = x; R.y = y; R.feat = feat; R.reduce = reduce;
-            R.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0; R.medium = 1;
-            if ((rc = launch_gcn_rows_long(R, c->stream))) return rc;
-        }
+        // long rows (disjoint output rows): forked to the auxiliary stream, or first on this one
+        if (p.n1 > 0 && (rc = launch_rows_class(c, p.r1.p, p.n1, 0, fork, &r, nullptr))) return rc;
+        // medium rows: ahead of the short rows on this stream (heaviest first; many workgroups per CU)
+        if (p.n2 > 0 && (rc = launch_rows_class(c, p.r2.p, p.n2, 1, false, &r, nullptr))) return rc;
         GcnPlanLaunch P;  // short rows: the descriptor path of the plan kernel (no segments, no hubs)
         P.t0 = p.r0.p; P.n0 = p.n0; P.t0_cost_prefix = p.r0_cost_prefix.data();
         P.row_ptr = c->d_ptr; P.idx = c->d_idx; P.val = c->d_val; P.x = x; P.y = y; P.feat = feat; P.reduce = reduce;
-        P.xcd_remap = c->xcd_remap; P.num_rows = c->V; P.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
+        P.xcd_remap = c->xcd_remap; P.num_rows = c->V; P.relu = relu;
         const bool nn_rows_ok = nn && (p.n1 + p.n2 == 0 || feat <= 15000);
         if (nn_rows_ok) {  // short rows: epilogue of the plan kernel (or the GEMM right behind it)
             P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols;
         }
         rc = launch_gcn_plan(P, c->stream);
-        if (fork) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));  // join
+        if (fork) {
+            if (const int rcj = join_aux(c)) return rcj;
+        }
         if (rc || !nn) return rc;
         if (!nn_rows_ok) return launch_dense_nn(y, nn->weight, nn->out, c->V, nn->cols, feat, c->stream);
         if (p.n1 + p.n2 > 0)  // the long and medium rows' products, once their chains have joined
@@ -1171,7 +1194,7 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
     }
     GcnLaunch L;
     L.row_ptr = c->d_ptr; L.x = x; L.y = y; L.feat = feat; L.reduce = reduce;
-    L.xcd_remap = c->xcd_remap; L.relu = (flags & GNNAGG_FLAG_RELU) ? 1 : 0;
+    L.xcd_remap = c->xcd_remap; L.relu = relu;
     if (!s) {
         L.wl.ptr = c->d_ptr;
         L.wl.n_items = c->V;
@@ -1205,11 +1228,13 @@ int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, in
 
 // x_dtype / y_dtype (GNNAGG_DTYPE_*): what x / y hold.  16-bit types run on the plan kernel only (gnnagg_gat_run_typed has validated the
 // call; an order that would leave the plan kernel returns GNNAGG_ERR_ARG)
-static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat, int heads, float slope, int mode,
-                   float *newval, int probe = 0, int part = 0, float *den_io = nullptr, int x_dtype = GNNAGG_DTYPE_F32,
-                   int y_dtype = GNNAGG_DTYPE_F32)
+static int gat_run(Ctx *c, const GatRequest &r)
 {
-    const bool typed = x_dtype != GNNAGG_DTYPE_F32 || y_dtype != GNNAGG_DTYPE_F32;
+    const float *x = r.x, *att = r.att;
+    float *y = r.y, *newval = r.newval;
+    const int feat = r.feat, heads = r.heads, probe = r.probe, part = r.part;
+    int mode = r.mode;
+    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32;
     if (typed && (probe || part != 0)) return fail(GNNAGG_ERR_ARG, "16-bit features: the two-pass form and the gather probe are fp32 only");
     if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "handle is not a GAT aggregator");
     if (!x || !y || !att) return fail(GNNAGG_ERR_ARG, "null feature/attention pointer");
@@ -1218,14 +1243,14 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
     if (mode == GNNAGG_MODE_SCHEDULED && c->fast_scheduled && c->sched[0].valid && !newval && sched_keeps_every_edge(c)) mode = GNNAGG_MODE_BALANCED;
     if (mode == GNNAGG_MODE_ROWS && c->opt_rows_blocked && c->tiled && c->use_plan && !newval && !probe && part == 0) {
         bool used = false;   // canonical chains on the blocked order where the graph allows it (sorted rows, high degree)
-        const int rcb = run_rows_blocked_gat(c, x, att, y, feat, heads, slope, &used);
+        const int rcb = run_rows_blocked_gat(c, r, &used);
         if (rcb || used) return rcb;
     }
     Schedule *s = nullptr;
     int rc = get_sched(c, mode, &s);
     if (rc) return rc;
     if (part != 0) {  // two-pass form: the chunked plan kernel implements it (a handle on the 2-D blocked order gets a plan beside it)
-        if (mode != GNNAGG_MODE_BALANCED || !c->use_plan || newval || probe || !den_io || part < 1 || part > 3)
+        if (mode != GNNAGG_MODE_BALANCED || !c->use_plan || newval || probe || !r.den_io || part < 1 || part > 3)
             return fail(GNNAGG_ERR_ARG, "gat_run_part: GNNAGG_MODE_BALANCED, part 1, 2 or 3, a denominator array, no newval");
         if (!c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
     }
@@ -1235,73 +1260,37 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
     const bool typed_on_partitioned = typed && c->partitions > 0;
     const bool on_plan = (mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || part != 0 || typed_on_partitioned)) ||
                          (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid);
-    if (typed && !on_plan)
-        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gat_run_typed (x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
-                                        (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
-                                        "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
-                                        "neighbor-grouping schedule / \"fast_scheduled\" = 1 (without newval) for GNNAGG_MODE_SCHEDULED");
+    if (typed && !on_plan) return fail_typed_order("gat", r.x_dtype, r.y_dtype, " (without newval)");
     if (typed_on_partitioned && mode == GNNAGG_MODE_BALANCED && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
     if (on_plan) {
         BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
         GatPlanLaunch P;
-        P.t0 = p.t0.p; P.t1 = p.t1.p; P.n0 = p.n0; P.n1 = p.n1; P.chunk = p.chunk; P.t0_cost_prefix = p.t0_cost_prefix.data();
-        P.x_dtype = x_dtype; P.y_dtype = y_dtype;
-        if (wants_sorted_rows(c, (long)feat * (x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4))) {
-            if ((rc = ensure_sorted_rows(c, p))) return rc;
-            if (p.t0_sorted.p) { P.t0 = p.t0_sorted.p; P.t0_cost_prefix = p.t0s_cost_prefix.data(); }
-        }
-        P.hubs.mrow_id = p.mrow_id.p; P.hubs.mrow_ptr = p.mrow_ptr.p; P.hubs.n_mrows = p.n_mrows;
-        P.hubs.n_slots = p.n_slots; P.hubs.big_rows = p.big_rows.p; P.hubs.n_big = p.n_big;
-        P.idx = c->d_idx; P.att = att; P.x = x; P.y = y; P.newval = newval; P.feat = feat; P.heads = heads; P.slope = slope;
-        P.xcd_remap = c->xcd_remap;
+        if ((rc = fill_plan_launch(c, p, feat, r.x_dtype, r.y_dtype, P))) return rc;
+        P.att = att; P.x = x; P.y = y; P.newval = newval; P.heads = heads; P.slope = r.slope;
         if (p.n_slots > 0) {
-            if ((rc = c->partial.reserve((size_t)p.n_slots * feat))) return rc;
             if ((rc = c->partial_den.reserve((size_t)p.n_slots * heads))) return rc;
-            P.partial = c->partial.p;
             P.partial_den = c->partial_den.p;
         }
-        if (p.n_mrows > 0 && c->inkernel_combine) {
-            if ((rc = reserve_hub_counters(c, p.n_mrows, feat, &P.hub_count_stride))) return rc;
-            P.slot_hub = p.slot_hub.p; P.hub_count = c->hub_count.p;
-        }
-        P.unroll = 4;
-        P.part_mode = part; P.den_io = den_io;
+        P.part_mode = part; P.den_io = r.den_io;
         return launch_gat_plan(P, c->stream);
     }
     if (mode == GNNAGG_MODE_BALANCED && c->partitions > 0 && c->plan_part.valid && c->part_descriptors) {
         BalancedPlan &p = c->plan_part;  // source-partitioned order on the descriptor path, as in gcn_run
         if (heads <= 0 || feat % heads != 0) return fail(GNNAGG_ERR_ARG, "GAT needs feat % heads == 0");
         TiledRun tr = plan_tiles(c, *s, x, y, feat, feat / heads);
+        // (head widths the span kernel does not tile: the descriptor form)
         const bool span_run = tr.spec.on && s->n_spans > 0 && gat_span_tiles(feat, heads, tr.spec.tile_w);
-        if (!span_run && s->gpu_built) {   // head widths the span kernel does not tile: the descriptor form, from the host builder
-            c->force_host_plan = 1;
-            if ((rc = build_partitioned(c, c->partitions))) return rc;
-            return gat_run(c, x, att, y, feat, heads, slope, mode, newval, probe, part, den_io);
-        }
-        size_t den_floats = (size_t)s->n_slots * heads;
-        if (span_run) {
-            tr.spec.p_tile_stride = (long)s->num_target * tr.spec.tile_w;
-            tr.partial_floats = (size_t)s->num_target * tr.spec.tile_w * tr.ntiles;
-            den_floats = (size_t)s->num_target * heads;
-        }
-        bool demoted = false;
-        if ((rc = reserve_partitioned_scratch(c, tr.partial_floats, den_floats, tr.xt_floats, &demoted))) return rc;
-        if (demoted) return gat_run(c, x, att, y, feat, heads, slope, mode, newval, probe);
+        bool redispatch = false;
+        if ((rc = prepare_blocked(c, *s, tr, span_run, heads, &redispatch))) return rc;
+        if (redispatch) return gat_run(c, r);
         if (probe && !span_run) return fail(GNNAGG_ERR_ARG, "GAT probe: the segmented-stream kernel does not cover this width / head count");
         if (span_run) {
             GatSpanLaunch G;
             SpanLaunch &S = G.s;
-            S.probe = probe;
-            S.span_g = s->span_g.p; S.n_spans = s->n_spans; S.span_cost_prefix = s->span_cost_prefix.data();
-            S.ptr_s = s->ptr_s.p; S.idx_f = s->idx_f.p; S.target = s->target.p;
-            S.n_groups = s->num_target; S.crows = s->crows.p; S.n_crows = s->n_crows; S.rg_ptr = s->rg_ptr.p; S.rg_idx = s->rg_idx.p;
-            S.empty_rows = s->empty_rows.p; S.n_empty = s->n_empty; S.row_ptr = c->d_ptr;
-            S.x = x; S.x_rows = s->total_cols; S.y = y; S.partial = c->partial.p; S.feat = feat; S.tile = tr.spec;
-            G.att = att; G.partial_den = c->partial_den.p; G.newval = newval; G.eperm = s->eperm.p; G.heads = heads; G.slope = slope;
-            if (tr.retile) {
-                if ((rc = launch_tile_x(x, c->xt.p, s->total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-                S.x = c->xt.p;
-            }
+            fill_span_launch(S, c, *s, tr, false);
+            S.probe = probe; S.y = y; S.feat = feat;
+            G.att = att; G.partial_den = c->partial_den.p; G.newval = newval; G.eperm = s->eperm.p; G.heads = heads; G.slope = r.slope;
+            if ((rc = tiled_x(c, *s, tr, x, feat, &S.x))) return rc;
             {   // compact attention terms: one HT-float load per edge instead of HT strided ones (k_tile_att)
                 const int dhead = feat / heads, ht = tr.spec.tile_w >= dhead ? tr.spec.tile_w / dhead : 1;
                 const int n_hg = (heads + ht - 1) / ht, arows = c->V > s->total_cols ? c->V : s->total_cols;
@@ -1315,16 +1304,13 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
         GatPlanLaunch P;
         P.t0 = p.t0.p; P.n0 = p.n0; P.chunk = p.chunk; P.t0_cost_prefix = p.t0_cost_prefix.data();
         P.hubs = s->worklist();
-        P.idx = s->idx_s.p; P.att = att; P.x = x; P.y = y; P.newval = newval; P.feat = feat; P.heads = heads; P.slope = slope;
+        P.idx = s->idx_s.p; P.att = att; P.y = y; P.newval = newval; P.feat = feat; P.heads = heads; P.slope = r.slope;
         P.eperm = s->eperm.p;  // newval[E,H] is defined in CSR edge order (gnnagg.h): scattered through the permutation
         P.xcd_remap = c->xcd_remap;
         P.partial = c->partial.p;
         P.partial_den = c->partial_den.p;
         P.tile = tr.spec;
-        if (tr.retile) {
-            if ((rc = launch_tile_x(x, c->xt.p, s->total_cols, feat, tr.spec.tile_w, c->stream))) return rc;
-            P.x = c->xt.p;
-        }
+        if ((rc = tiled_x(c, *s, tr, x, feat, &P.x))) return rc;
         return launch_gat_plan(P, c->stream);
     }
     if (mode == GNNAGG_MODE_ROWS && c->use_plan && !newval && heads > 0 && feat % heads == 0) {
@@ -1336,41 +1322,22 @@ static int gat_run(Ctx *c, const float *x, const float *att, float *y, int feat,
         const bool long_ok = p.n1 > 0 && tile_in_head;
         if (p.n1 + p.n2 == 0 || tile_in_head) {
             const bool fork = long_ok && c->use_aux_stream;
-            if (long_ok) {
-                if (fork) {
-                    if (!c->aux_stream) {
-                        HIP_TRY(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-                        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                        HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-                    }
-                    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-                    HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-                }
-                GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-                R.r1 = p.r1.p; R.n1 = p.n1; R.idx = c->d_idx; R.x = x; R.y = y; R.feat = feat;
-                R.att = att; R.heads = heads; R.slope = slope;
-                if ((rc = launch_gcn_rows_long(R, fork ? c->aux_stream : c->stream))) return rc;
-                if (fork) HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
-            }
-            if (p.n2 > 0) {  // medium rows, ahead of the short rows on this stream
-                GcnRowsLongLaunch R;
-            R.tile_w = c->opt_hub_tile;
-                R.r1 = p.r2.p; R.n1 = p.n2; R.idx = c->d_idx; R.x = x; R.y = y; R.feat = feat;
-                R.att = att; R.heads = heads; R.slope = slope; R.medium = 1;
-                if ((rc = launch_gcn_rows_long(R, c->stream))) return rc;
-            }
+            if (long_ok && (rc = launch_rows_class(c, p.r1.p, p.n1, 0, fork, nullptr, &r))) return rc;
+            // medium rows, ahead of the short rows on this stream
+            if (p.n2 > 0 && (rc = launch_rows_class(c, p.r2.p, p.n2, 1, false, nullptr, &r))) return rc;
             GatPlanLaunch P;
             P.t0 = p.r0.p; P.n0 = p.n0; P.t0_cost_prefix = p.r0_cost_prefix.data();
-            P.idx = c->d_idx; P.att = att; P.x = x; P.y = y; P.feat = feat; P.heads = heads; P.slope = slope;
+            P.idx = c->d_idx; P.att = att; P.x = x; P.y = y; P.feat = feat; P.heads = heads; P.slope = r.slope;
             P.xcd_remap = c->xcd_remap; P.rows_semantics = 1;
             rc = launch_gat_plan(P, c->stream);
-            if (fork) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+            if (fork) {
+                if (const int rcj = join_aux(c)) return rcj;
+            }
             return rc;
         }
     }
     GatLaunch L;
-    L.att = att; L.x = x; L.y = y; L.feat = feat; L.heads = heads; L.slope = slope; L.newval = newval;
+    L.att = att; L.x = x; L.y = y; L.feat = feat; L.heads = heads; L.slope = r.slope; L.newval = newval;
     L.xcd_remap = c->xcd_remap;
     if (!s) {
         L.wl.ptr = c->d_ptr;
@@ -1731,7 +1698,7 @@ int gnnagg_get_schedule(gnnagg_handle h, int mode, int *h_ptr_s, int *h_idx_s, i
 int gnnagg_gcn_run(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, int reduce)
 {
     GET_CTX(h);
-    return gcn_run(c, d_x, d_y, feat, mode, reduce);
+    return gcn_run(c, GcnRequest{d_x, d_y, feat, mode, reduce});
 }
 
 int gnnagg_matmul_nn(const float *d_a, const float *d_b, float *d_c, int m, int n, int k, void *hip_stream)
@@ -1747,7 +1714,7 @@ int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const 
     GET_CTX(h);
     if (!d_weight || !d_transformed || feat_out <= 0) return fail(GNNAGG_ERR_ARG, "bad run_with_nn arguments");
     const NnRequest nn = {d_weight, d_transformed, feat_out};
-    return gcn_run(c, d_x, d_y, feat_in, mode, GNNAGG_REDUCE_SUM, 0, &nn);
+    return gcn_run(c, GcnRequest{d_x, d_y, feat_in, mode, GNNAGG_REDUCE_SUM, 0, &nn});
 }
 
 int gnnagg_gcn_run_clock(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, unsigned long long *d_timer,
@@ -1793,7 +1760,7 @@ long long gnnagg_wall_clock_hz(void)
 int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, int reduce, int flags)
 {
     GET_CTX(h);
-    return gcn_run(c, d_x, d_y, feat, mode, reduce, flags);
+    return gcn_run(c, GcnRequest{d_x, d_y, feat, mode, reduce, flags});
 }
 
 int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int mode, int reduce, int flags)
@@ -1804,7 +1771,7 @@ int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_
         return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_typed: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
     if (x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32)
-        return gcn_run(c, static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags);
+        return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags});
     const std::string combo = std::string("x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
                               (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32");
     if ((flags & GNNAGG_FLAG_ACCUMULATE) && y_dtype != GNNAGG_DTYPE_F32)
@@ -1812,7 +1779,7 @@ int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_
     if (c->kind == Ctx::GCN && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
         return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
                                     "is fp32 only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
-    return gcn_run(c, static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, nullptr, 0, x_dtype, y_dtype);
+    return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, nullptr, 0, x_dtype, y_dtype});
 }
 
 int gnnagg_gcn_probe_gather(gnnagg_handle h, const float *d_x, int feat, int mode)
@@ -1820,7 +1787,7 @@ int gnnagg_gcn_probe_gather(gnnagg_handle h, const float *d_x, int feat, int mod
     GET_CTX(h);
     // y is never written by the probe instantiation; a non-null pointer keeps the argument checks and the lane geometry
     // (alignment class of y) those of a real run
-    return gcn_run(c, d_x, const_cast<float *>(d_x), feat, mode, GNNAGG_REDUCE_SUM, 0, nullptr, 1);
+    return gcn_run(c, GcnRequest{d_x, const_cast<float *>(d_x), feat, mode, GNNAGG_REDUCE_SUM, 0, nullptr, 1});
 }
 
 int gnnagg_check_csr(gnnagg_handle h, int num_cols, int *bad_rows, int *bad_indices)
@@ -1864,7 +1831,7 @@ int gnnagg_gat_run(gnnagg_handle h, const float *d_x, const float *d_att, float 
                    float slope, int mode, float *d_newval)
 {
     GET_CTX(h);
-    return gat_run(c, d_x, d_att, d_y, feat, heads, slope, mode, d_newval);
+    return gat_run(c, GatRequest{d_x, d_att, d_y, feat, heads, slope, mode, d_newval});
 }
 
 int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, void *d_y, int y_dtype, int feat, int heads,
@@ -1876,28 +1843,28 @@ int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const fl
         return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_typed: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
     if (x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32)
-        return gat_run(c, static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval);
+        return gat_run(c, GatRequest{static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval});
     const std::string combo = std::string("x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
                               (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32");
     if (c->kind == Ctx::GAT && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
         return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
                                     "is fp32 only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
-    return gat_run(c, static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval, 0, 0, nullptr,
-                   x_dtype, y_dtype);
+    return gat_run(c, GatRequest{static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval, 0, 0, nullptr,
+                               x_dtype, y_dtype});
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,
                         float *d_den_io)
 {
     GET_CTX(h);
-    return gat_run(c, d_x, d_att, d_y, feat, heads, slope, GNNAGG_MODE_BALANCED, nullptr, 0, part, d_den_io);
+    return gat_run(c, GatRequest{d_x, d_att, d_y, feat, heads, slope, GNNAGG_MODE_BALANCED, nullptr, 0, part, d_den_io});
 }
 
 int gnnagg_gat_probe_gather(gnnagg_handle h, const float *d_x, const float *d_att, int feat, int heads, int mode)
 {
     GET_CTX(h);
     // y is never written by the probe instantiation (see gnnagg_gcn_probe_gather)
-    return gat_run(c, d_x, d_att, const_cast<float *>(d_x), feat, heads, 0.2f, mode, nullptr, 1);
+    return gat_run(c, GatRequest{d_x, d_att, const_cast<float *>(d_x), feat, heads, 0.2f, mode, nullptr, 1});
 }
 
 int gnnagg_probe_row_gather(const void *d_rows, long long pitch_bytes, int seg_bytes, const int *d_ids, long long n_ids, int ids_per_group,

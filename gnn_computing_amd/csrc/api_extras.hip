@@ -73,7 +73,7 @@ int gnnagg_gat_run_bwd(gnnagg_handle h, const float *d_output, const float *d_do
     if ((rc = launch_edge_items_sum(LT, 1, c->stream))) return rc;
     if ((rc = launch_interleave2(t.da.p, t.db.p, d_a_b_grad, c->V, c->stream))) return rc;
     // 4. d_feat = A^T-aggregation of dout with edge values p (balanced GCN kernels)
-    return gcn_run(ct, d_doutput, d_feat_grad, feat, GNNAGG_MODE_BALANCED, GNNAGG_REDUCE_SUM);
+    return gcn_run(ct, GcnRequest{d_doutput, d_feat_grad, feat, GNNAGG_MODE_BALANCED, GNNAGG_REDUCE_SUM});
 }
 
 int gnnagg_gcn_run_bwd(gnnagg_handle h, const float *d_doutput, float *d_dinput, int feat)
@@ -89,7 +89,7 @@ int gnnagg_gcn_run_bwd(gnnagg_handle h, const float *d_doutput, float *d_dinput,
     ct->stream = c->stream;
     // the edge values follow their edges (re-gathered every call: updateval may have re-aliased them)
     if ((rc = launch_permute_val(t.perm.p, c->d_val, t.val_t.p, c->E, c->stream))) return rc;
-    return gcn_run(ct, d_doutput, d_dinput, feat, GNNAGG_MODE_BALANCED, GNNAGG_REDUCE_SUM);
+    return gcn_run(ct, GcnRequest{d_doutput, d_dinput, feat, GNNAGG_MODE_BALANCED, GNNAGG_REDUCE_SUM});
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // api_internal.h -- what the translation units behind the C-ABI share: the handle object (Ctx), its schedules and plans, the handle
-// registry, and the two run dispatchers.  Not installed; include/gnnagg.h is the interface.
+// registry, and the run dispatch.  Not installed; include/gnnagg.h is the interface.
 //
 // GNNAGG_EXTRAS (make -C gnn_computing_amd/csrc extras -> libgnnagg_extras.so): what the DEFAULT library leaves out --
 // the backward entry points (gnnagg_gcn_run_bwd / gnnagg_gat_run_bwd: SURVEY 2.2 marks the reference's kernel out of scope), the older
@@ -208,10 +208,32 @@ struct NnRequest {  // run_with_nn: transformed[V, cols] = y . weight[feat, cols
     float *out;
     int cols;
 };
-// x_dtype / y_dtype (GNNAGG_DTYPE_*): what x / y hold.  16-bit types run on the plan kernel only (gnnagg_gcn_run_typed has validated the
-// call; an order that would leave the plan kernel returns GNNAGG_ERR_ARG)
-int gcn_run(Ctx *c, const float *x, float *y, int feat, int mode, int reduce, int flags = 0, const NnRequest *nn = nullptr, int probe = 0,
-            int x_dtype = GNNAGG_DTYPE_F32, int y_dtype = GNNAGG_DTYPE_F32);
+// What the caller of a run asked for.  Built on the caller's stack by the entry points, passed by reference through the dispatch; a
+// re-dispatch (after a rebuild or a demotion of the handle's order) runs the same request again.
+// x_dtype / y_dtype (GNNAGG_DTYPE_*): what x / y hold.  16-bit types run on the plan kernel only (gnnagg_gcn_run_typed / gnnagg_gat_run_typed
+// have validated the call; an order that would leave the plan kernel returns GNNAGG_ERR_ARG)
+struct GcnRequest {
+    const float *x;
+    float *y;
+    int feat, mode, reduce;
+    int flags = 0;
+    const NnRequest *nn = nullptr;
+    int probe = 0;
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+};
+struct GatRequest {
+    const float *x, *att;
+    float *y;
+    int feat, heads;
+    float slope;
+    int mode;
+    float *newval;
+    int probe = 0;
+    int part = 0;              // two-pass form (gnnagg_gat_run_part)
+    float *den_io = nullptr;
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+};
+int gcn_run(Ctx *c, const GcnRequest &r);
 int edge_launch(Ctx *c, EdgeItemLaunch &L, int heads);
 int do_schedule(Ctx *c, int kind, const int *param, int total_v);
 int fetch_host_ptr(Ctx *c);

@@ -91,39 +91,43 @@ struct GcnLaunch {
     const long *xcd_item_cost_prefix = nullptr;
 };
 
-// Balanced plan (GNNAGG_MODE_BALANCED, GCN): see k_gcn_plan in agg_gcn.hip.
-struct GcnPlanLaunch {
+// What a launch of a plan kernel (k_gcn_plan, k_gat_plan) takes from a balanced plan and the handle, GCN and GAT alike.
+struct PlanLaunch {
     const void *t0 = nullptr;  // int4 {beg,end,row,-} per short row
-    const void *t1 = nullptr;  // int4 {beg,end,dest,-} per long-row segment
+    const void *t1 = nullptr;  // int4 {beg,end,dest,-} per long-row segment (GAT: the destination row in .w, the segment's attention centre)
     int n0 = 0, n1 = 0, chunk = 64;
     const long *t0_cost_prefix = nullptr;  // host, n0+1 entries
     WorkList hubs;                          // only mrow_* / big_rows / n_slots are used (combine of multi-segment rows)
-    const int *row_ptr = nullptr;
     const int *idx = nullptr;
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;  // gnnagg_*_run_typed: 16-bit X / Y (fp32 weights, chains, partials, fold)
+    float *partial = nullptr;
+    int feat = 0;
+    int xcd_remap = 2;
+    // hubs finished inside the plan kernel by the last segment workgroup to arrive (no k_combine launch)
+    const int *slot_hub = nullptr;  // device: scratch slot -> index into hubs.mrow_*
+    int *hub_count = nullptr;       // device: arrival counters, zero between launches; n_mrows * hub_count_stride ints
+    int hub_count_stride = 0;       // counters per hub (>= column tiles of the launch)
+    TileSpec tile;  // 2-D blocked mode (short-row descriptors only: n1 == 0)
+    int unroll = 0; // 4: four gathers per batch where the geometry has that instantiation (balanced / scheduled orders); 0: default (8)
+};
+
+// Balanced plan (GNNAGG_MODE_BALANCED, GCN): see k_gcn_plan in agg_gcn.hip.
+struct GcnPlanLaunch : PlanLaunch {
+    const int *row_ptr = nullptr;
     const float *val = nullptr;
     const void *x = nullptr;   // elements of x_dtype
     void *y = nullptr;         // elements of y_dtype
-    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;  // gnnagg_gcn_run_typed: 16-bit X / Y (fp32 chains, partials, fold)
-    float *partial = nullptr;
-    int feat = 0;
     int reduce = GNNAGG_REDUCE_SUM;
-    int xcd_remap = 2;
     int accumulate = 0;  // y += A.x (sum; mean / max with row_aux); rows without edges keep their value
     const int *row_aux = nullptr;  // gnnagg_set_row_aux: mean divisor / edges already folded into y (finish_gcn_row)
     int relu = 0;        // y = max(result, 0)
     int num_rows = 0;    // rows of y
     int t0_partials = 0; // short-row descriptors may carry scratch slots (dest < 0): source-partitioned order
-    // hubs finished inside the plan kernel by the last segment workgroup to arrive (no k_combine launch)
-    const int *slot_hub = nullptr;  // device: scratch slot -> index into hubs.mrow_*
-    int *hub_count = nullptr;       // device: arrival counters, zero between launches; n_mrows * hub_count_stride ints
-    int hub_count_stride = 0;       // counters per hub (>= column tiles of the launch)
     // dense combine as the epilogue (run_with_nn): nn_out[V, nn_cols] = y . nn_weight[feat, nn_cols]
     const float *nn_weight = nullptr;
     float *nn_out = nullptr;
     int nn_cols = 0;
-    TileSpec tile;  // 2-D blocked mode (short-row descriptors only: n1 == 0)
     int probe = 0;  // 1: gather probe -- the same descriptors, id/value loads and feature gathers, no chain, no stores
-    int unroll = 0; // 4: four gathers per batch where the geometry has that instantiation (balanced / scheduled orders); 0: default (8)
 };
 
 // 2-D blocked order as a segmented stream (agg_span.hip): lane groups walk spans of whole groups of the permuted edge list.
@@ -235,29 +239,16 @@ struct EdgeItemLaunch {
 };
 int launch_edge_items_sum(const EdgeItemLaunch &L, int op, void *stream);
 int launch_edge_items_map(const EdgeItemLaunch &L, int op, void *stream);
-// Balanced plan, GAT (k_gat_plan).  t1 descriptors carry the destination row in .w (the segment's attention centre).
-struct GatPlanLaunch {
-    const void *t0 = nullptr, *t1 = nullptr;
-    int n0 = 0, n1 = 0, chunk = 64;
-    const long *t0_cost_prefix = nullptr;
-    WorkList hubs;
-    const int *idx = nullptr;
+// Balanced plan, GAT (k_gat_plan).
+struct GatPlanLaunch : PlanLaunch {
     const float *att = nullptr;
     const float *x = nullptr;   // elements of x_dtype
     float *y = nullptr;         // elements of y_dtype
-    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;  // gnnagg_gat_run_typed: 16-bit X / Y (fp32 weights, chains, partials, fold)
-    float *partial = nullptr, *partial_den = nullptr, *newval = nullptr;
-    int feat = 0, heads = 1;
+    float *partial_den = nullptr, *newval = nullptr;
+    int heads = 1;
     float slope = 0.2f;
-    int xcd_remap = 2;
     int rows_semantics = 0;  // 1: `scheduled = 0` semantics (aggr_gat: divide by the denominator unconditionally)
-    // hubs folded inside the plan kernel (see GcnPlanLaunch)
-    const int *slot_hub = nullptr;
-    int *hub_count = nullptr;
-    int hub_count_stride = 0;
-    TileSpec tile;              // 2-D blocked mode, as in GcnPlanLaunch
     const int *eperm = nullptr; // permuted orders: original edge of every position (newval is written in CSR edge order)
-    int unroll = 0;             // 4: four gathers per batch where the geometry has that instantiation (balanced / scheduled orders)
     int part_mode = 0;          // two-pass form (gnnagg_gat_run_part): 1 = numerator / denominator out, 2 = add to them and divide
     float *den_io = nullptr;    // [num_v, heads]
 };

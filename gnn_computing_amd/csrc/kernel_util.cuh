@@ -603,20 +603,23 @@ static Geometry pick_geometry(int F, const void *p0, const void *p1, const void 
     return {vec, group, ntiles};
 }
 
+// the 12 (VEC, GROUP) cases of fp32 lanes; variadic: the expanded call carries commas
+#define DISPATCH_GEOM_CASES(...)                                                 \
+        case 108: { constexpr int VEC = 1, GROUP = 8;  __VA_ARGS__; } break;     \
+        case 116: { constexpr int VEC = 1, GROUP = 16; __VA_ARGS__; } break;     \
+        case 132: { constexpr int VEC = 1, GROUP = 32; __VA_ARGS__; } break;     \
+        case 164: { constexpr int VEC = 1, GROUP = 64; __VA_ARGS__; } break;     \
+        case 208: { constexpr int VEC = 2, GROUP = 8;  __VA_ARGS__; } break;     \
+        case 216: { constexpr int VEC = 2, GROUP = 16; __VA_ARGS__; } break;     \
+        case 232: { constexpr int VEC = 2, GROUP = 32; __VA_ARGS__; } break;     \
+        case 264: { constexpr int VEC = 2, GROUP = 64; __VA_ARGS__; } break;     \
+        case 408: { constexpr int VEC = 4, GROUP = 8;  __VA_ARGS__; } break;     \
+        case 416: { constexpr int VEC = 4, GROUP = 16; __VA_ARGS__; } break;     \
+        case 432: { constexpr int VEC = 4, GROUP = 32; __VA_ARGS__; } break;     \
+        case 464: { constexpr int VEC = 4, GROUP = 64; __VA_ARGS__; } break;
 #define DISPATCH_GEOM(g, KERNEL_CALL)                                            \
     switch ((g).vec * 100 + (g).group) {                                         \
-        case 108: { constexpr int VEC = 1, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 116: { constexpr int VEC = 1, GROUP = 16; KERNEL_CALL; } break;     \
-        case 132: { constexpr int VEC = 1, GROUP = 32; KERNEL_CALL; } break;     \
-        case 164: { constexpr int VEC = 1, GROUP = 64; KERNEL_CALL; } break;     \
-        case 208: { constexpr int VEC = 2, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 216: { constexpr int VEC = 2, GROUP = 16; KERNEL_CALL; } break;     \
-        case 232: { constexpr int VEC = 2, GROUP = 32; KERNEL_CALL; } break;     \
-        case 264: { constexpr int VEC = 2, GROUP = 64; KERNEL_CALL; } break;     \
-        case 408: { constexpr int VEC = 4, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 416: { constexpr int VEC = 4, GROUP = 16; KERNEL_CALL; } break;     \
-        case 432: { constexpr int VEC = 4, GROUP = 32; KERNEL_CALL; } break;     \
-        case 464: { constexpr int VEC = 4, GROUP = 64; KERNEL_CALL; } break;     \
+        DISPATCH_GEOM_CASES(KERNEL_CALL)                                         \
         default: return fail(GNNAGG_ERR_ARG, "unsupported lane geometry");       \
     }
 
@@ -649,24 +652,16 @@ static Geometry typed_geometry(int F, const void *x, int xsize, int dhead)
 // DISPATCH_GEOM plus the 16-byte lanes of 16-bit X (8 elements)
 #define DISPATCH_GEOM_16BIT(g, KERNEL_CALL)                                      \
     switch ((g).vec * 100 + (g).group) {                                         \
-        case 108: { constexpr int VEC = 1, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 116: { constexpr int VEC = 1, GROUP = 16; KERNEL_CALL; } break;     \
-        case 132: { constexpr int VEC = 1, GROUP = 32; KERNEL_CALL; } break;     \
-        case 164: { constexpr int VEC = 1, GROUP = 64; KERNEL_CALL; } break;     \
-        case 208: { constexpr int VEC = 2, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 216: { constexpr int VEC = 2, GROUP = 16; KERNEL_CALL; } break;     \
-        case 232: { constexpr int VEC = 2, GROUP = 32; KERNEL_CALL; } break;     \
-        case 264: { constexpr int VEC = 2, GROUP = 64; KERNEL_CALL; } break;     \
-        case 408: { constexpr int VEC = 4, GROUP = 8;  KERNEL_CALL; } break;     \
-        case 416: { constexpr int VEC = 4, GROUP = 16; KERNEL_CALL; } break;     \
-        case 432: { constexpr int VEC = 4, GROUP = 32; KERNEL_CALL; } break;     \
-        case 464: { constexpr int VEC = 4, GROUP = 64; KERNEL_CALL; } break;     \
+        DISPATCH_GEOM_CASES(KERNEL_CALL)                                         \
         case 808: { constexpr int VEC = 8, GROUP = 8;  KERNEL_CALL; } break;     \
         case 816: { constexpr int VEC = 8, GROUP = 16; KERNEL_CALL; } break;     \
         case 832: { constexpr int VEC = 8, GROUP = 32; KERNEL_CALL; } break;     \
         case 864: { constexpr int VEC = 8, GROUP = 64; KERNEL_CALL; } break;     \
         default: return fail(GNNAGG_ERR_ARG, "unsupported lane geometry");       \
     }
+
+// geometry of a 2-D blocked launch: 16-byte lanes over tiles of tile_w floats
+static Geometry tile_geometry(const TileSpec &t, int feat) { return {4, t.tile_w / 4, (feat + t.tile_w - 1) / t.tile_w}; }
 
 // Launch-site state that belongs to a DEVICE, not to the process (a process may drive several): "this function attribute has been
 // set here" flags and the CU count.  (A relaxed race sets an attribute twice, which is harmless.)
@@ -761,6 +756,35 @@ static int fill_xcd_ranges_tile_major(const long *cost_prefix, int n_items, int 
         start = stop;
     }
     return longest;
+}
+
+// Grid of a plan launch (k_gcn_plan / k_gat_plan: n1 segment workgroups, then item blocks of `gpb` short rows per column tile) and the
+// fields PlanArgs and GatPlanArgs share for it: the item blocks, the XCD ranges (a.remap falls back where they do not apply) and, for
+// a 2-D blocked launch, the tile-major addressing of `tile` in place of the caller's row-major defaults.
+template <typename Args>
+static int plan_grid(Args &a, const Geometry &g, int gpb, const TileSpec &tile, int n_slots, const long *t0_cost_prefix, int *grid)
+{
+    a.tile_major = 0; a.ptile_bytes = 0;
+    if (tile.on) {
+        a.xpitch = tile.xpitch; a.x_tile_stride = tile.x_tile_stride; a.ppitch = tile.ppitch;
+        a.p_tile_stride = tile.p_tile_stride; a.yvec = tile.yvec; a.tile_major = 1;
+        const size_t tb = (size_t)n_slots * tile.ppitch * sizeof(float);
+        a.ptile_bytes = tb < 0x7fffffffULL ? (unsigned)tb : 0u;
+    }
+    const int item_blocks = ceil_div(a.n0, gpb);
+    a.nblocks0 = item_blocks * g.ntiles;
+    a.item_blocks = item_blocks;
+    if (a.remap && a.nblocks0 < 64 && !a.tile_major) a.remap = 0;
+    int grid0 = a.nblocks0;
+    if (a.tile_major) {
+        if (!t0_cost_prefix) return fail(GNNAGG_ERR_STATE, "internal: tiled launch without item costs");
+        grid0 = 8 * fill_xcd_ranges_tile_major(t0_cost_prefix, a.n0, gpb, item_blocks, g.ntiles, a.xr);
+    } else if (a.remap == 2) {
+        if (!t0_cost_prefix) a.remap = 1;
+        else grid0 = 8 * fill_xcd_ranges(t0_cost_prefix, a.n0, gpb, item_blocks, a.xr) * g.ntiles;
+    }
+    *grid = a.n1 * g.ntiles + grid0;
+    return GNNAGG_OK;
 }
 
 }  // namespace gnnagg
