@@ -27,7 +27,7 @@ DIMS = [512, 128, 64, 32]                                    # our.py:92-95
 class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
-    def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123):
+    def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -43,6 +43,12 @@ class Model:
         self.weights_lr = [torch.randn(DIMS[k + 1], 2, device=dev) / DIMS[k + 1] ** 0.5 for k in range(3)]
         self.h = torch.randn(self.num_v, DIMS[0], device=dev)
         self.outs = [torch.empty(self.num_v, DIMS[k + 1], device=dev) for k in range(3)]
+        # dtype = torch.bfloat16: features, weights, intermediates and outputs in bf16 (the same seeded values, cast); accumulation stays
+        # fp32 in every kernel (gnnagg_matmul_nn_typed, gnnagg_gcn_run_typed, gnnagg_gat_run_typed); the attention terms stay fp32
+        self.dtype = dtype
+        if dtype != torch.float32:
+            self.weights, self.weights_lr = [w.to(dtype) for w in self.weights], [w.to(dtype) for w in self.weights_lr]
+            self.h, self.outs = self.h.to(dtype), [o.to(dtype) for o in self.outs]
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -57,9 +63,15 @@ class Model:
             self.trace.append(dict(feat=feat, w=w, feat2=feat2, out=res.clone()))
         return res
 
+    def dense_f32(self, a, b):
+        """a . b with an fp32 result whatever the operands' type (the GAT attention terms)"""
+        if self.dtype == torch.float32:
+            return self.dense(a, b)
+        return self.dense(a, b, out_dtype=torch.float32) if self.dense is gnc.matmul_NN else self.dense(a, b).float()
+
     def gat_layer(self, feat, out, w, w_lr):                  # our.py:179-188
         feat2 = self.dense(feat, w)
-        att_lr = self.dense(feat2, w_lr)
+        att_lr = self.dense_f32(feat2, w_lr)
         gnc.gat_run(self.at_gat, feat2, att_lr, out, 128, self.sched)
         if self.trace is not None:
             self.trace.append(dict(feat=feat, w=w, w_lr=w_lr, feat2=feat2, att=att_lr, out=out.clone()))
@@ -90,6 +102,9 @@ def main():
     ap.add_argument("--dense", default="library", choices=["library", "torch"],
                     help="dense layers: the library's f32-MFMA GEMM (gnnagg_matmul_nn: bit-exact against the oracle, every stage of "
                          "the forward then is; 512 -> 128: 261 us vs rocBLAS 239 us) or torch.mm as the reference script uses")
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
+                    help="element type of features, weights and layer outputs; bf16: fp32 accumulation everywhere (typed entry points), "
+                         "the dense layers on the bf16 MFMA (gnnagg_matmul_nn_typed)")
     ap.add_argument("--hip-graph", action="store_true",
                     help="capture one forward in a HIP graph and replay it (the 9-12 launches of a forward are short "
                          "enough on the arxiv-sized graph for launch gaps to show)")
@@ -101,7 +116,7 @@ def main():
     else:
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
-              gnc.matmul_NN if args.dense == "library" else torch.mm)
+              gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -132,7 +147,7 @@ def main():
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
     print(json.dumps({"model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
-                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "balanced": bool(args.balanced), "dense": args.dense, "finite": bool(torch.isfinite(y).all().item())}))
+                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "finite": bool(torch.isfinite(y).all().item())}))
 
 
 if __name__ == "__main__":

@@ -68,6 +68,7 @@ SIGNATURES = {
     "gnnagg_check_csr": (c_int, [c_int64, c_int, P_INT, P_INT]),
     "gnnagg_csr2edgelist": (c_int, [c_int64, c_void_p]),
     "gnnagg_matmul_nn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_matmul_nn_typed": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gnnagg_gcn_run_with_nn": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "gnnagg_gat_run": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "gnnagg_gat_run_typed": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),

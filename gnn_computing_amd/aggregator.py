@@ -362,14 +362,34 @@ class Aggregator_GAT(Aggregator):
 # Flat functions with the reference pybind names (Figure7/kernel.cpp:166-179).  Handles are
 # Python objects here (the reference returns the raw pointer as int64 and leaks it).
 # ------------------------------------------------------------------------------------------
-def matmul_NN(A, B, C=None):
-    """include/dense.h:4-23: row-major C = A @ B on the MFMA kernel of libgnnagg (device fp32 tensors)."""
+def matmul_NN(A, B, C=None, out_dtype=None):
+    """include/dense.h:4-23: row-major C = A @ B on the MFMA kernels of libgnnagg.  Device tensors: A and B both float32 (C float32;
+    the ascending-k fp32 chain of gnnagg_matmul_nn) or both bfloat16 (C float32 or bfloat16: fp32 accumulation on the bf16 MFMA, a bf16
+    C is one rounding of the fp32 one; gnnagg_matmul_nn_typed).  C defaults to out_dtype if given, else to A.dtype."""
+    ta, tb = _feat_dtype(A, "A"), _feat_dtype(B, "B")
+    if C is not None:
+        tc = _feat_dtype(C, "C")
+        if out_dtype is not None and out_dtype != C.dtype:
+            raise TypeError("C is %s but out_dtype is %s" % (C.dtype, out_dtype))
+    else:
+        if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+            raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+        tc = FEATURE_DTYPES[A.dtype if out_dtype is None else out_dtype]
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[0]:
+        raise ValueError("matmul_NN: A %s and B %s do not multiply" % (tuple(A.shape), tuple(B.shape)))
     M, K = A.shape
     N = B.shape[1]
     if C is None:
-        C = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    check(lib().gnnagg_matmul_nn(_dev_ptr(A, torch.float32, "A"), _dev_ptr(B, torch.float32, "B"), _dev_ptr(C, torch.float32, "C"),
-                                 int(M), int(N), int(K), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        C = torch.empty((M, N), dtype=A.dtype if out_dtype is None else out_dtype, device=A.device)
+    elif tuple(C.shape) != (M, N):
+        raise ValueError("matmul_NN: C %s is not [%d, %d]" % (tuple(C.shape), M, N))
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream) if A.is_cuda else None   # (a host tensor is refused by _dev_ptr)
+    if (ta, tb, tc) == (_lib.DTYPE_F32,) * 3:
+        check(lib().gnnagg_matmul_nn(_dev_ptr(A, torch.float32, "A"), _dev_ptr(B, torch.float32, "B"), _dev_ptr(C, torch.float32, "C"),
+                                     int(M), int(N), int(K), stream))
+    else:   # (mixed operand types, fp32 operands with a bf16 C: refused by the library, which names the combination)
+        check(lib().gnnagg_matmul_nn_typed(_dev_ptr(A, A.dtype, "A"), ta, _dev_ptr(B, B.dtype, "B"), tb, _dev_ptr(C, C.dtype, "C"), tc,
+                                           int(M), int(N), int(K), stream))
     return C
 
 

@@ -1708,6 +1708,24 @@ int gnnagg_matmul_nn(const float *d_a, const float *d_b, float *d_c, int m, int 
     return launch_dense_nn(d_a, d_b, d_c, m, n, k, hip_stream);
 }
 
+int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_dtype, void *d_c, int c_dtype, int m, int n, int k,
+                           void *hip_stream)
+{
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(a_dtype) || !known(b_dtype) || !known(c_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_matmul_nn_typed: unknown dtype code (a " + std::to_string(a_dtype) + ", b " + std::to_string(b_dtype) +
+                                        ", c " + std::to_string(c_dtype) + "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    auto name = [](int t) { return t == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32"; };
+    if (a_dtype != b_dtype || (a_dtype == GNNAGG_DTYPE_F32 && c_dtype != GNNAGG_DTYPE_F32))
+        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_matmul_nn_typed (a ") + name(a_dtype) + ", b " + name(b_dtype) + ", c " + name(c_dtype) +
+                                        "): the dense combine runs fp32 . fp32 -> fp32 and bf16 . bf16 -> fp32 or bf16; nothing is converted");
+    if (a_dtype == GNNAGG_DTYPE_F32)
+        return gnnagg_matmul_nn(static_cast<const float *>(d_a), static_cast<const float *>(d_b), static_cast<float *>(d_c), m, n, k, hip_stream);
+    if (m < 0 || n < 0 || k < 0 || ((long)m * n > 0 && !d_c) || ((long)m * k > 0 && !d_a) || ((long)k * n > 0 && !d_b))
+        return fail(GNNAGG_ERR_ARG, "bad matmul_nn_typed arguments");
+    return launch_dense_nn_bf16(d_a, d_b, d_c, c_dtype == GNNAGG_DTYPE_BF16, m, n, k, hip_stream);
+}
+
 int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const float *d_weight, float *d_transformed,
                            int feat_in, int feat_out, int mode)
 {

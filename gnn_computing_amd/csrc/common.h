@@ -281,6 +281,8 @@ int launch_validate_reordered(const float *ref, const float *ans, const int *map
                               void *stream);
 int launch_dense_rows(const int *rows, int n_rows, const float *Y, const float *W, float *out, int K, int N, void *stream);
 int launch_dense_nn(const float *A, const float *B, float *C, int M, int N, int K, void *stream);
+// bf16 A / B, fp32 accumulation on the bf16 MFMA; C fp32 or (c_bf16) one RNE rounding of it (dense_bf16.hip)
+int launch_dense_nn_bf16(const void *A, const void *B, void *C, int c_bf16, int M, int N, int K, void *stream);
 int launch_check_csr(const int *ptr, const int *idx, int V, int E, int num_cols, int *d_counts, void *stream);
 int launch_pack_rows(const float *x, const int *ids, int n, int feat, float *out, void *stream);
 int launch_pack_rows2(const float *x, const float *att, const int *ids, int n, int feat, int att_w, float *out, void *stream);

@@ -258,6 +258,24 @@ int gnnagg_gcn_run_edgewise(gnnagg_handle h, const float *d_x, float *d_y, int f
 /* matmul_NN, include/dense.h:4-23: c[m,n] = a[m,k] . b[k,n], row-major fp32 (the dense combine after an
  * aggregation).  f32 MFMA, accumulation in ascending k. */
 int gnnagg_matmul_nn(const float *d_a, const float *d_b, float *d_c, int m, int n, int k, void *hip_stream);
+/* gnnagg_matmul_nn with a / b / c in the given element types (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16; no reference counterpart).
+ * (F32, F32, F32) is gnnagg_matmul_nn exactly: the same launch, the same bits.  (BF16, BF16, F32) and (BF16, BF16, BF16) run the bf16
+ * MFMA (v_mfma_f32_32x32x16_bf16) with fp32 accumulators:
+ *   sizes   any m, n, k >= 0 (k == 0: c = +0; m == 0 or n == 0: nothing is done); a / b / c at any element-aligned address (a 2-byte
+ *           offset for bf16, a 4-byte one for a fp32 c: narrower loads, the same kernel)
+ *   sums    a bf16 x bf16 product is exact in fp32; the order and rounding of the additions inside a bf16 MFMA are not documented, so
+ *           the result is NOT bit-comparable to the ascending-k chain of gnnagg_matmul_nn.  What holds: where every partial sum in any
+ *           order is an integer below 2^24 the result is that integer exactly; otherwise |c - c64| <= 1e-5 . sum_k |a_k b_k| against
+ *           the float64 product of the same bf16 operands (16-bit accumulation would sit at 4-5e-4)
+ *   tails   k, row and column tails contribute exact zeros built in registers; nothing behind an operand is read, and a NaN / inf in
+ *           row r of a reaches row r of c only
+ *   bf16 c  the same accumulation, then ONE round-to-nearest-even of what the fp32-c call stores (NaN kept, overflow to inf)
+ *   the same inputs give the same bits on every call; no allocation, synchronisation or memset: capturable in a HIP graph
+ * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, a and b of
+ * different types, fp32 operands with a bf16 c -- nothing is converted and nothing falls back.  Arguments are checked before any
+ * device call.  gnnagg_gcn_run_with_nn and its fused aggregation -> GEMM epilogue stay fp32 only. */
+int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_dtype, void *d_c, int c_dtype,
+                           int m, int n, int k, void *hip_stream);
 /* Aggregator_GCN::run_with_nn, aggr_gcn.h:491-499 (kernel aggr_gcn_nn :304-359): y = A.x, then
  * transformed[V,feat_out] = y . weight[feat_in,feat_out].  Both outputs are fully overwritten (the
  * reference accumulates into whatever they held). */
