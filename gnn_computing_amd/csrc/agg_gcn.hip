@@ -542,18 +542,13 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
                 else store_pack<VEC>(a.y + (size_t)row * F + col, acc);
             }
         }
-#if !defined(NN_DBG) || NN_DBG != 1
         if (!col_ok) {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
         }
         store_pack<VEC>(&lds[slot * PITCH + col], acc);
         if (lane == 0) tile_rows[slot] = row;
-#endif
     }
-#if defined(NN_DBG) && (NN_DBG == 1 || NN_DBG == 2)
-    return;
-#endif
     tile_times_weight<(GROUP * VEC >= 128 ? 32 : GROUP * VEC / 4), ROWS>(lds, PITCH, tile_rows, w.weight, F, F, w.n_out, w.out);
 }
 

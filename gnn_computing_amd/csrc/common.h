@@ -31,7 +31,7 @@ void halo_stage_plan_send(const long long *send_rows, int world, int rank, int m
 int cluster_reorder(const int *ptr, const int *idx, int V, double threshold, int num_perm, int cap, uint64_t seed,
                     int max_bucket, int *rows_out, int *num_clusters_out, int order_mode = 0, int cache_rows = 4096);
 
-// ---- agg_gcn.hip / agg_gat.hip / aux_kernels.hip : launch descriptors (all pointers are device pointers)
+// ---- agg_gcn.hip / agg_gat.hip / aux_kernels.hip / dense_f32.hip : launch descriptors (all pointers are device pointers)
 
 // A work list: item g covers edges [ptr[g], ptr[g+1]) of output row (target ? target[g] : g).
 //   slot == nullptr : every item owns its whole row -> direct store.

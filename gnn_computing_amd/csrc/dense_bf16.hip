@@ -1,5 +1,5 @@
 // dense_bf16.hip -- the dense combine with 16-bit operands (gnnagg_matmul_nn_typed): C[M,N] = A[M,K] . B[K,N], A and B row-major bf16,
-// C row-major fp32 or bf16, fp32 accumulation on v_mfma_f32_32x32x16_bf16.  The fp32 GEMM (aux_kernels.hip) is a separate set of kernels.
+// C row-major fp32 or bf16, fp32 accumulation on v_mfma_f32_32x32x16_bf16.  The fp32 GEMM (dense_f32.hip) is a separate set of kernels.
 //
 // Regime: tall and skinny (M = |V|, K = 32 .. 602, N = 2 .. 128) -- the job is to stream A from HBM once; B is small.
 //  * One wavefront owns 32 rows x (32 * NT) columns at a time: NT accumulator tiles of 32 x 32 (NT = 4: N up to 128 in one pass over A).

@@ -1,6 +1,6 @@
 #pragma once
 // kernel_util.cuh -- shared device helpers of the hand-written CDNA4 (gfx950) kernels of the neighbor-aggregation hot
-// path (agg_gcn.hip, agg_gat.hip, aux_kernels.hip).
+// path (agg_gcn.hip, agg_gat.hip, aux_kernels.hip, dense_f32.hip).
 //
 // Design (wave64, HBM/L2-bound integer+fp32 gather work; no MFMA -- 0.25 flop/B):
 //  * A "lane group" of GROUP = 8/16/32/64 lanes owns one work item (a CSR row, or a chunk of a

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Where a wavefront of the wide GEMM spends a K chunk (A/B build with -DGNNAGG_GEMM_TIMELINE: s_memtime stamps of wave 0 of every workgroup
-at six points of the chunk loop).  usage: GNNAGG_LIB=<timeline build> exp_gemm_timeline.py [M K N]"""
+at six points of the chunk loop).  usage: GNNAGG_LIB=<timeline build> exp_gemm_timeline.py [M K N]
+The stamps and their setter are retired: gemm_switches_retired.patch (beside this file) holds them and says which commit builds them."""
 import ctypes
 import os
 import sys

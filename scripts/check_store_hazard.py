@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""ISA lint for a hazard the gfx950 code generator left open once (aux_kernels.hip, k_dense_nn_lean, round 5): a VMEM / LDS store of more
+"""ISA lint for a hazard the gfx950 code generator left open once (k_dense_nn_lean, now dense_f32.hip, round 5): a VMEM / LDS store of more
 than 8 bytes reads its upper data registers a cycle after it issues, so a VALU write of one of those registers needs wait states in
 between.  The compiler inserts them inside a basic block; when the store is the LAST instruction of a block and the next block starts
 with such a write, nothing separated them.  usage: check_store_hazard.py [--require kernel[,kernel...]] file.s [...]
@@ -79,7 +79,7 @@ for path in sys.argv[1:]:
                 break
 print("%d suspicious place(s)" % bad)
 
-# Second check: k_dense_nn_ahead / _ahead2 keep their prefetch registers (v192 .. v255) out of the compiler's hands with amdgpu_num_vgpr(192) and
+# Second check: k_dense_nn_ahead<4> / <2> (dense_f32.hip) keep their prefetch registers (v192 .. v255) out of the compiler's hands with amdgpu_num_vgpr(192) and
 # count their own vmcnt.  A toolchain that stopped honouring the attribute, or spilled (scratch loads carry vmcnt waits of their own), would corrupt
 # products silently: outside the ;;#ASMSTART ... ;;#ASMEND blocks no instruction of those kernels may name a VGPR >= 192 or touch scratch.
 VREG = re.compile(r"\bv\[?(\d+)(?::(\d+))?\]?")
