@@ -693,7 +693,7 @@ __global__ __launch_bounds__(BLOCK) void k_gcn_rows_long(const RowsLongArgs a)
                 if (r == nrounds - 1 && i == nb - 1) {
                     if (consumer) {
                         if (a.mean) acc = acc / (float)(d.y - d.x);
-                        if (a.relu) acc = acc > 0.0f ? acc : 0.0f;
+                        if (a.relu) acc = acc < 0.0f ? 0.0f : acc;   // (a NaN stays a NaN: relu_pack, kernel_util.cuh)
                         a.y[(size_t)d.z * F + tile * TW + c] = acc;
                     }
                 } else {
@@ -780,7 +780,7 @@ __global__ __launch_bounds__(BLOCK) void k_gcn_rows_long(const RowsLongArgs a)
         if (consumer) {
             if (IS_GAT) acc = acc / den;  // aggr_gat.h:163 (rows here are never empty)
             else if (a.mean) acc = acc / (float)(d.y - d.x);
-            if (!IS_GAT && a.relu) acc = acc > 0.0f ? acc : 0.0f;
+            if (!IS_GAT && a.relu) acc = acc < 0.0f ? 0.0f : acc;   // (a NaN stays a NaN: relu_pack, kernel_util.cuh)
             a.y[(size_t)d.z * F + tile * TW + c] = acc;
         }
         return;

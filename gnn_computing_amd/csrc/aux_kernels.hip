@@ -515,7 +515,7 @@ __global__ __launch_bounds__(256) void k_untile_y(const float *__restrict__ yt, 
     }
     if (relu) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.0f ? v[k] : 0.0f;
+        for (int k = 0; k < 4; ++k) v[k] = v[k] < 0.0f ? 0.0f : v[k];   // (a NaN stays a NaN: relu_pack, kernel_util.cuh)
     }
     float *dst = y + (size_t)r * feat + c;
     if (c + 3 < feat && (((uintptr_t)dst) & 15) == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);

@@ -115,7 +115,7 @@ template <int VEC>
 __device__ __forceinline__ void relu_pack(float (&a)[VEC])
 {
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) a[k] = a[k] > 0.0f ? a[k] : 0.0f;
+    for (int k = 0; k < VEC; ++k) a[k] = a[k] < 0.0f ? 0.0f : a[k];   // (not a > 0 ? a : 0: a NaN stays a NaN, as in torch.clamp_min)
 }
 
 template <int VEC>
@@ -169,7 +169,7 @@ __device__ __forceinline__ void finish_gcn_row(float (&acc)[VEC], int own_deg, i
     }
     if (relu) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = acc[k] > 0.0f ? acc[k] : 0.0f;
+        for (int k = 0; k < VEC; ++k) acc[k] = acc[k] < 0.0f ? 0.0f : acc[k];   // (a NaN stays a NaN: relu_pack)
     }
 }
 

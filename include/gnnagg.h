@@ -205,7 +205,10 @@ int gnnagg_gcn_run(gnnagg_handle h, const float *d_x, float *d_y, int feat, int 
 /* GNNAGG_FLAG_RELU (any mode / reduce): y = max(result, 0) -- the activation that follows the aggregation in the
  * reference's 3-layer model (Figure7/our.py:176, F.relu on the output of gcn_run), applied to the finished row by the
  * producing kernel instead of one more pass over y.  With GNNAGG_FLAG_ACCUMULATE: y = max(y + A.x, 0), rows without
- * edges included. */
+ * edges included.
+ * Non-finite features (GCN and GAT, every mode): plain IEEE propagation -- an Inf or NaN in x[s] reaches exactly the rows that have s
+ * as a neighbor (the padding of the kernels never multiplies a real source by zero); GNNAGG_FLAG_RELU keeps a NaN (-Inf becomes 0);
+ * GNNAGG_REDUCE_MAX over a NaN operand is unspecified. */
 #define GNNAGG_FLAG_RELU 2
 int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, int reduce, int flags);
 /* y = A.x with x / y in the given element types (no reference counterpart: the reference's surface is float *).  Accumulation,
