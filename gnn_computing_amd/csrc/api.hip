@@ -1075,7 +1075,7 @@ static int run_rows_blocked_gat(Ctx *c, const GatRequest &r, bool *used)
         S.span_g = rb.span_g.p + s0; S.n_spans = s1 - s0; S.span_cost_prefix = rb.cost[(size_t)p].data();
         if ((rc = launch_gat_span(G, c->stream))) return rc;
     }
-    if ((rc = launch_untile_y_gat(c->yt.p, c->den_t.p, y, rb.n1 > 0 ? rb.hub_mask.p : nullptr, c->V, feat, tr.spec.tile_w, ht, dhead, c->stream))) return rc;
+    if ((rc = launch_untile_y_gat(c->yt.p, c->den_t.p, y, c->d_ptr, rb.n1 > 0 ? rb.hub_mask.p : nullptr, c->V, feat, tr.spec.tile_w, ht, dhead, c->stream))) return rc;
     if (fork) rc = join_aux(c);
     else if (rb.n1 > 0) rc = launch_rows_class(c, rb.r1.p, rb.n1, 0, false, nullptr, &r);
     if (rc) return rc;

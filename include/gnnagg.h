@@ -127,6 +127,7 @@ int gnnagg_set_stream(gnnagg_handle h, void *hip_stream);
  *                                         a single queue); 1 (default)
  *   "rows_blocked"                        1 (default): GNNAGG_MODE_ROWS runs its canonical chains on the 2-D blocked order where the
  *                                         graph allows it (gnnagg_rows_blocked_ranges); 0: always the row kernels.  Same bits either way
+ *                                         (GAT included: non-finite weights and zero denominators, "Attention logits" below)
  *   "rows_medium_edges"                   GNNAGG_MODE_ROWS on the row kernels: rows above this many edges, up to the hub threshold
  *                                         max(1024, 16 x mean degree), run on 128-thread workgroups (one gather wavefront + the chain)
  *                                         instead of one lane group each.  0 (default): max(128, E / 4500), an empty class from 4.6 M
@@ -293,7 +294,26 @@ int gnnagg_csr2edgelist(gnnagg_handle h, int *d_edgelist);
 
 /* Aggregator_GAT::run / run_with_feat, aggr_gat.h:317-394.  att is [V,heads,2] (heads = 1 is the
  * reference layout), x,y are [V,feat], feat % heads == 0.  d_newval (may be NULL) receives the
- * un-normalised edge weights [E,heads] the reference's scheduled kernel materialises (:187). */
+ * un-normalised edge weights [E,heads] the reference's scheduled kernel materialises (:187).
+ * Attention logits (every GAT call, slope > 0):
+ *   weights    w_e = expf(s > s * slope ? s : s * slope) with s = att[dst, h, 0] + att[src, h, 1], all in fp32 and WITHOUT subtracting a
+ *              row maximum, as the reference (aggr_gat.h:138-143): w_e is +Inf above expf's overflow threshold (a leaky logit above
+ *              88.7), +0 below its underflow threshold (below -104), NaN for a NaN term.  Callers that may reach those ranges shift
+ *              att[., h, 0] by the row maximum themselves.
+ *   locality   att[s, h, 1] reaches exactly head h of the rows that have s as a neighbor, att[r, h, 0] exactly head h of row r: every
+ *              other element of y and d_newval is bit-equal to the run without the change.
+ *   +Inf, NaN  a +Inf or NaN weight in a (row, head) makes that head's columns of the row NaN, in every mode; d_newval holds the +Inf or
+ *              NaN itself at those edges.
+ *   0 / 0      a (row, head) that has edges whose weights are all +0 -- the denominator is 0 --
+ *                GNNAGG_MODE_ROWS in its canonical order ("fast_rows" = 0), on the row kernels and on the 2-D blocked order alike:
+ *                  NaN, aggr_gat's 0 / 0 (aggr_gat.h:163);
+ *                every grouped order (the balanced chunked plan, the 2-D blocked balanced order, GNNAGG_MODE_SCHEDULED, "fast_rows" =
+ *                  1): the un-divided numerator, as scaleArray divides where the scalar is non-zero (aggr_gat.h:207-213) -- +0 for
+ *                  finite features;
+ *              rows without edges stay +0 everywhere.  A zero weight is an exact no-op in every chain: the other (row, head)s keep their
+ *              bound, and d_newval holds +0 at those edges.
+ * (tests/test_gpu_gat_logits.py, tests/test_gat_logits_host.py.  Not specified: denormal weights and logits within a few ulps of the
+ * two thresholds -- device expf and libm may differ there by a class --, slope <= 0.) */
 int gnnagg_gat_run(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads,
                    float slope, int mode, float *d_newval);
 /* gnnagg_gat_run with x / y in the given element types (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16; no reference counterpart).  d_att
@@ -319,10 +339,15 @@ int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const fl
  *   part = 1  d_y[row, :] receives the NUMERATOR sum_e w_e x_e and d_den_io[row, h] the denominator sum_e w_e; no division
  *   part = 2  both are added to what part 1 left (old + new, one fp32 add per element), then the row is divided
  *             (scaleArray, aggr_gat.h:207-213); rows this handle has no edges for are divided all the same
- *   part = 3  a pass in between (staged halo exchange, gnnagg_dist_step_create_staged): both are added, nothing is divided */
+ *   part = 3  a pass in between (staged halo exchange, gnnagg_dist_step_create_staged): both are added, nothing is divided
+ * Weights as under "Attention logits": a +Inf / NaN weight in either pass makes the (row, head) NaN (d_den_io holds the +Inf / NaN
+ * after part 1), zero weights are no-ops.  What a (row, head) with edges receives when its denominator over BOTH passes is 0 is not
+ * specified. */
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,
                         float *d_den_io);
-/* Aggregator_GAT::run_att, aggr_gat.h:395-401 (attGat :5-31): out_val[E,heads] = softmax weights */
+/* Aggregator_GAT::run_att, aggr_gat.h:395-401 (attGat :5-31): out_val[E,heads] = softmax weights w_e / sum_row(w), divided unguarded as
+ * attGat does: with the weights of "Attention logits" above, NaN at an edge whose weight is +Inf or NaN and +0 at the finite edges of that
+ * (row, head); NaN on every edge of a (row, head) whose weights are all +0. */
 int gnnagg_gat_run_att(gnnagg_handle h, const float *d_att, float *d_out_val, int heads, float slope);
 /* aggr_gat.h:402-425, single head as in the reference */
 int gnnagg_gat_run_u_add_v(gnnagg_handle h, const float *d_att, float *d_out_val);
