@@ -27,7 +27,8 @@ DIMS = [512, 128, 64, 32]                                    # our.py:92-95
 class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
-    def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32):
+    def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
+                 stable_softmax=False):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -38,7 +39,9 @@ class Model:
         gnc.gat_schedule(self.at_gat, neighbor_num)
         self.sched, self.fused_relu, self.dense = sched, fused_relu, dense
         # 1/sqrt(fan_in) scaling keeps activations O(1): the reference's GAT kernel exponentiates raw scores without a
-        # max-subtraction (aggr_gat.h:138-143), so un-scaled randn weights overflow exp() in the deeper layers
+        # max-subtraction (aggr_gat.h:138-143), so un-scaled randn weights overflow exp() in the deeper layers.  stable_softmax
+        # (--stable-softmax) runs the GAT layers with the row maximum subtracted (gnnagg_gat_run_shifted), which needs no such scaling
+        self.stable_softmax = stable_softmax
         self.weights = [torch.randn(DIMS[k], DIMS[k + 1], device=dev) / DIMS[k] ** 0.5 for k in range(3)]
         self.weights_lr = [torch.randn(DIMS[k + 1], 2, device=dev) / DIMS[k + 1] ** 0.5 for k in range(3)]
         self.h = torch.randn(self.num_v, DIMS[0], device=dev)
@@ -72,7 +75,7 @@ class Model:
     def gat_layer(self, feat, out, w, w_lr):                  # our.py:179-188
         feat2 = self.dense(feat, w)
         att_lr = self.dense_f32(feat2, w_lr)
-        gnc.gat_run(self.at_gat, feat2, att_lr, out, 128, self.sched)
+        gnc.gat_run(self.at_gat, feat2, att_lr, out, 128, self.sched, stable=self.stable_softmax)
         if self.trace is not None:
             self.trace.append(dict(feat=feat, w=w, w_lr=w_lr, feat2=feat2, att=att_lr, out=out.clone()))
         return out
@@ -105,6 +108,9 @@ def main():
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="element type of features, weights and layer outputs; bf16: fp32 accumulation everywhere (typed entry points), "
                          "the dense layers on the bf16 MFMA (gnnagg_matmul_nn_typed)")
+    ap.add_argument("--stable-softmax", action="store_true",
+                    help="GAT: subtract every row's maximal leaky logit before the exp (gnnagg_gat_run_shifted, stable=True): no overflow "
+                         "whatever the scale of the weights")
     ap.add_argument("--hip-graph", action="store_true",
                     help="capture one forward in a HIP graph and replay it (the 9-12 launches of a forward are short "
                          "enough on the arxiv-sized graph for launch gaps to show)")
@@ -116,7 +122,8 @@ def main():
     else:
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
-              gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+              gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
+              stable_softmax=args.stable_softmax)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -147,7 +154,7 @@ def main():
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
     print(json.dumps({"model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
-                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "finite": bool(torch.isfinite(y).all().item())}))
+                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
 
 
 if __name__ == "__main__":

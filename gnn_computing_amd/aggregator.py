@@ -275,25 +275,58 @@ class Aggregator_GCN(Aggregator):
 class Aggregator_GAT(Aggregator):
     """reference include/aggr_gat.h:299-441"""
 
+    # k_gat_row_shift as built (csrc/common.h: kShiftGroup, kShiftHeads, kShiftHubEdges): lanes per short row, heads per pass, and the
+    # row length above which the whole workgroup walks a row
+    ROW_SHIFT_THRESHOLDS = (8, 4, 1024)
+
     def __init__(self, ptr, idx, feat_in=32, feat_out=32):
         super().__init__(ptr, idx, feat_in, feat_out)
         check(lib().gnnagg_gat_create(_dev_ptr(ptr, torch.int32, "ptr"), _dev_ptr(idx, torch.int32, "idx"),
                                       self.num_v, self.num_e, ctypes.byref(self._h)))
 
-    def run(self, vin, vatt, vout, BLOCK_SIZE=128, scheduled=0, heads=1, slope=0.2, newval=None):
-        """aggr_gat.h:317-354 (slope 0.2 at :347); heads > 1 takes att [V,H,2]."""
-        return self.run_with_feat(vin, vatt, vout, BLOCK_SIZE, scheduled, int(vin.shape[1]), heads, slope, newval)
+    def run(self, vin, vatt, vout, BLOCK_SIZE=128, scheduled=0, heads=1, slope=0.2, newval=None, stable=False, shift=None):
+        """aggr_gat.h:317-354 (slope 0.2 at :347); heads > 1 takes att [V,H,2].  stable / shift: see run_with_feat."""
+        return self.run_with_feat(vin, vatt, vout, BLOCK_SIZE, scheduled, int(vin.shape[1]), heads, slope, newval, stable, shift)
 
-    def run_with_feat(self, vin, vatt, vout, BLOCK_SIZE, scheduled, feat, heads=1, slope=0.2, newval=None):
+    def row_shift(self, vatt, heads=1, slope=0.2, out=None):
+        """gnnagg_gat_row_shift (extension): float32 [V, heads], the maximum over each row's edges of the fp32 leaky logit
+        max(s, s * slope), s = att[r, h, 0] + att[src, h, 1]; +0 for rows without edges.  What run(..., stable=True) subtracts."""
+        if not isinstance(vatt, torch.Tensor) or vatt.dtype != torch.float32:
+            raise TypeError("vatt must be a torch.float32 tensor")
+        if vatt.numel() < self.num_v * heads * 2:
+            raise ValueError("att must hold at least V*heads*2 floats")
+        if out is None:
+            out = torch.empty((self.num_v, int(heads)), dtype=torch.float32, device=vatt.device)
+        elif out.numel() < self.num_v * heads:
+            raise ValueError("out must hold at least V*heads floats")
+        self._use_current_stream()
+        check(lib().gnnagg_gat_row_shift(self._h, _dev_ptr(vatt, torch.float32, "vatt"), int(heads), ctypes.c_float(slope),
+                                         _dev_ptr(out, torch.float32, "out")))
+        return out
+
+    def run_with_feat(self, vin, vatt, vout, BLOCK_SIZE, scheduled, feat, heads=1, slope=0.2, newval=None, stable=False, shift=None):
         """aggr_gat.h:355-394.  vin / vout: torch.float32 or torch.bfloat16 (extension, gnnagg_gat_run_typed): weights, sums and the
         softmax division stay fp32, a bfloat16 vout is one round-to-nearest-even of the fp32 result; vatt and newval stay float32;
-        float32 / float32 is gnnagg_gat_run."""
+        float32 / float32 is gnnagg_gat_run.
+        stable=True (extension, gnnagg_gat_run_shifted): the overflow-safe edge softmax, every leaky logit minus its row maximum (which
+        the library computes first, row_shift); shift=tensor [V, heads] float32: the caller's shift instead.  Neither goes with newval."""
         xt, yt = _feat_dtype(vin, "vin"), _feat_dtype(vout, "vout")
-        for t, name in ((vatt, "vatt"), (newval, "newval")):
+        for t, name in ((vatt, "vatt"), (newval, "newval"), (shift, "shift")):
             if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
                 raise TypeError("%s must be torch.float32, got %s" % (name, t.dtype))
         if vatt.numel() < self.num_v * heads * 2:
             raise ValueError("att must hold at least V*heads*2 floats")
+        if stable or shift is not None:
+            if newval is not None:
+                raise _lib.GnnAggError(_lib.ERR_ARG, "Aggregator_GAT.run: stable / shift with newval -- gnnagg_gat_run_shifted has no "
+                                                     "newval output (the un-normalised weights of a shifted run are in another scale)")
+            if shift is not None and shift.numel() < self.num_v * heads:
+                raise ValueError("shift must hold at least V*heads floats")
+            self._use_current_stream()
+            check(lib().gnnagg_gat_run_shifted(self._h, _dev_ptr(vin, vin.dtype, "vin"), xt, _dev_ptr(vatt, torch.float32, "vatt"),
+                                               _dev_ptr(shift, torch.float32, "shift"), _dev_ptr(vout, vout.dtype, "vout"), yt, int(feat),
+                                               int(heads), ctypes.c_float(slope), _mode(scheduled)))
+            return 0.0
         self._use_current_stream()
         if xt == _lib.DTYPE_F32 and yt == _lib.DTYPE_F32:
             check(lib().gnnagg_gat_run(self._h, _dev_ptr(vin, torch.float32, "vin"), _dev_ptr(vatt, torch.float32, "vatt"),
@@ -453,8 +486,9 @@ def gat_init(ptrs, idxs):
     return at
 
 
-def gat_run(at, feat, att, outfeat, blocksize, scheduled):
-    at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]))
+def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
+    """Figure7/kernel.cpp's gat_run; stable=True (extension): the overflow-safe edge softmax (Aggregator_GAT.run_with_feat)."""
+    at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]), stable=stable)
 
 
 def gat_schedule(at, neighbor_num):

@@ -90,11 +90,12 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_items(const GatArgs a
 // numerator AND denominator partials folded in ascending chunk order in LDS, hubs through scratch + k_combine.
 // TX = __bf16 (gnnagg_gat_run_typed): 16-bit feature rows (Pack<VEC, __bf16>), widened in registers where the chain consumes them; ids,
 // attention terms, weights, the fmaf chains and the denominator chain are the same.
-template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float>
+template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float, bool SHIFT = false>
 __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, int beg, int end, int lane, bool col_ok,
                                                 const int *__restrict__ idx, const float *__restrict__ att_src, int H,
                                                 float a_dst, float slope, const TX *__restrict__ xcol, int F,
-                                                float *newval, int h, bool head_leader, const int *__restrict__ eperm = nullptr)
+                                                float *newval, int h, bool head_leader, const int *__restrict__ eperm = nullptr,
+                                                float shift = 0.0f)
 {
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
@@ -117,7 +118,9 @@ __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, i
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u)
                 if (j + u < n && col_ok) {
-                    const float w = edge_weight(a_dst, as[u], slope);
+                    float w;
+                    if constexpr (SHIFT) w = edge_weight_shifted(a_dst, as[u], slope, shift);
+                    else w = edge_weight(a_dst, as[u], slope);
                     if (newval && head_leader) newval[(size_t)(eperm ? eperm[cb + j + u] : cb + j + u) * H + h] = w;
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(xv[u].at(k), w, acc[k]);
@@ -133,12 +136,13 @@ __device__ __forceinline__ void chain_edges_gat(float (&acc)[VEC], float &den, i
 // shares it with ds_bpermute like the edge values of the GCN chain, instead of every lane gathering and exponentiating
 // every edge.  Ids are fetched two windows ahead and source terms one window ahead, so nothing dependent sits on the path;
 // the first feature gathers of a window are issued before its weights are needed.  Same values, same order as
-// chain_edges_gat (bit-identical results).
-template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float>
+// chain_edges_gat (bit-identical results).  SHIFT (gnnagg_gat_run_shifted): the weight is edge_weight_shifted(., shift), shift the
+// (row, head)'s entry of the shift array; nothing else changes.
+template <int VEC, int GROUP, int UNROLL = kUnroll, typename TX = float, bool SHIFT = false>
 __device__ __forceinline__ void chain_edges_gat1(float (&acc)[VEC], float &den, int beg, int end, int lane, bool col_ok,
                                                  const int *__restrict__ idx, const float *__restrict__ att_src, float a_dst,
                                                  float slope, const TX *__restrict__ xcol, int F, float *newval,
-                                                 bool first_tile, const int *__restrict__ eperm = nullptr)
+                                                 bool first_tile, const int *__restrict__ eperm = nullptr, float shift = 0.0f)
 {
     int s0 = 0, s1 = 0;
     float a0 = 0.0f, a1 = 0.0f;
@@ -161,7 +165,8 @@ __device__ __forceinline__ void chain_edges_gat1(float (&acc)[VEC], float &den, 
             for (int u = 0; u < UNROLL; ++u)
                 if (j + u < n && col_ok) xv[u] = load_pack<VEC>(xcol + (size_t)s[u] * F);
             if (j == 0) {  // this lane's edge of the window
-                my_w = lane < n ? edge_weight(a_dst, a0, slope) : 0.0f;
+                if constexpr (SHIFT) my_w = lane < n ? edge_weight_shifted(a_dst, a0, slope, shift) : 0.0f;
+                else my_w = lane < n ? edge_weight(a_dst, a0, slope) : 0.0f;
                 if (newval && first_tile && lane < n) newval[eperm ? eperm[cb + lane] : cb + lane] = my_w;
             }
 #pragma unroll
@@ -205,6 +210,8 @@ struct GatPlanArgs {
     XcdRanges xr;
     // typed launches (TYPED = true): x holds TX elements; y holds bf16 (y_bf16) or fp32, and yvec is Y's alignment class in its own elements
     int y_bf16;
+    // shifted launches (SHIFT = true, gnnagg_gat_run_shifted): shift[V, heads], subtracted from every leaky logit of its (row, head)
+    const float *shift;
 };
 
 // Last step of a GAT row: softmax division (scaleArray, aggr_gat.h:207-213), or its two-pass form.
@@ -307,10 +314,13 @@ __device__ __forceinline__ void hub_arrive_and_fold_gat(const GatPlanArgs &a, in
 // true stores every finished row through store_y_typed (a.y_bf16, a.yvec).  Weights, chains, denominators, LDS stage, partial rows, hub
 // fold and the division stay fp32 and keep their order, so a bf16 X gives bit for bit the fp32 run on X widened.  The defaults are the
 // fp32 kernel, instruction for instruction.  The segment workgroup's LDS stage grows with VEC: 36 KB at VEC = 8, GROUP = 64.
-template <int VEC, int GROUP, bool SINGLE, int UNROLL = kUnroll, typename TX = float, bool TYPED = false>
+// SHIFT (gnnagg_gat_run_shifted): where the destination term of a (row, head) is read, its shift is read too, and every weight is
+// edge_weight_shifted; partials, folds and the division see weights of one scale per (row, head) and stay as they are.  Typed launches only.
+template <int VEC, int GROUP, bool SINGLE, int UNROLL = kUnroll, typename TX = float, bool TYPED = false, bool SHIFT = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArgs a)
 {
     static_assert(TYPED || std::is_same<TX, float>::value, "16-bit X needs the typed store");
+    static_assert(TYPED || !SHIFT, "shifted launches run the typed instantiations");
     constexpr int GPB = block_of<GROUP>() / GROUP;
     const int F = a.feat, H = a.heads;
     const int lane = threadIdx.x & (GROUP - 1);
@@ -343,6 +353,8 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
         __shared__ float stage_den[kSegChunks * GROUP];
         const int row = d.w;  // destination row of this segment (its attention centre term)
         const float a_dst = a.att[((size_t)row * H + h) * 2];
+        float shift = 0.0f;
+        if constexpr (SHIFT) shift = a.shift[(size_t)row * H + h];
         const int nch = (d.y - d.x + a.chunk - 1) / a.chunk;
         for (int c = grp; c < nch; c += GPB) {
             float acc[VEC] = {};
@@ -350,11 +362,11 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
             const int cb = d.x + c * a.chunk;
             const int ce = cb + a.chunk < d.y ? cb + a.chunk : d.y;
             if constexpr (SINGLE)
-                chain_edges_gat1<VEC, GROUP, UNROLL, TX>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, F, a.newval,
-                                             tile == 0);
+                chain_edges_gat1<VEC, GROUP, UNROLL, TX, SHIFT>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, F, a.newval,
+                                             tile == 0, nullptr, shift);
             else
-                chain_edges_gat<VEC, GROUP, UNROLL, TX>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, F, a.newval,
-                                            h, head_leader);
+                chain_edges_gat<VEC, GROUP, UNROLL, TX, SHIFT>(acc, den, cb, ce, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, F, a.newval,
+                                            h, head_leader, nullptr, shift);
             store_pack<VEC>(&stage[(c * GROUP + lane) * VEC], acc);
             stage_den[c * GROUP + lane] = den;
         }
@@ -397,12 +409,14 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gat_plan(const GatPlanArg
     float den = 0.0f;
     if (d.x < d.y) {
         const float a_dst = a.att[((size_t)row * H + h) * 2];
+        float shift = 0.0f;
+        if constexpr (SHIFT) shift = a.shift[(size_t)row * H + h];
         if constexpr (SINGLE)
-            chain_edges_gat1<VEC, GROUP, UNROLL, TX>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, a.xpitch, a.newval,
-                                         tile == 0, a.eperm);
+            chain_edges_gat1<VEC, GROUP, UNROLL, TX, SHIFT>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, a_dst, a.slope, xcol, a.xpitch, a.newval,
+                                         tile == 0, a.eperm, shift);
         else
-            chain_edges_gat<VEC, GROUP, UNROLL, TX>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, a.xpitch, a.newval,
-                                        h, head_leader, a.eperm);
+            chain_edges_gat<VEC, GROUP, UNROLL, TX, SHIFT>(acc, den, d.x, d.y, lane, col_ok, a.idx, att_src, H, a_dst, a.slope, xcol, a.xpitch, a.newval,
+                                        h, head_leader, a.eperm, shift);
     }
     if (!col_ok) return;
     if (d.z < 0) {  // one of several groups of its row (source-partitioned order): numerator and denominator to scratch
@@ -489,19 +503,19 @@ int launch_gat(const GatLaunch &L, void *stream_v)
 #ifndef GNNAGG_GAT_TYPED_U4_GROUP   // A/B switch (measurement builds only): the narrowest lane group that takes 4 gathers per batch
 #define GNNAGG_GAT_TYPED_U4_GROUP 16
 #endif
-template <int VEC, int GROUP, int UNROLL, typename TX, bool TYPED>
+template <int VEC, int GROUP, int UNROLL, typename TX, bool TYPED, bool SHIFT>
 static void launch_gat_plan_unroll(const GatPlanArgs &a, int grid, int blk, hipStream_t stream)
 {
-    if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
-    else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, UNROLL, TX, TYPED>), dim3(grid), dim3(blk), 0, stream, a);
+    if (a.heads == 1) hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, true, UNROLL, TX, TYPED, SHIFT>), dim3(grid), dim3(blk), 0, stream, a);
+    else              hipLaunchKernelGGL((k_gat_plan<VEC, GROUP, false, UNROLL, TX, TYPED, SHIFT>), dim3(grid), dim3(blk), 0, stream, a);
 }
-template <int VEC, int GROUP, typename TX, bool TYPED>
+template <int VEC, int GROUP, typename TX, bool TYPED, bool SHIFT = false>
 static void launch_gat_plan_geom(const GatPlanArgs &a, bool u4, int grid, int blk, hipStream_t stream)
 {
     if constexpr (VEC * sizeof(TX) == 16 && GROUP >= (TYPED ? GNNAGG_GAT_TYPED_U4_GROUP : 32)) {
-        if (u4) return launch_gat_plan_unroll<VEC, GROUP, 4, TX, TYPED>(a, grid, blk, stream);
+        if (u4) return launch_gat_plan_unroll<VEC, GROUP, 4, TX, TYPED, SHIFT>(a, grid, blk, stream);
     }
-    launch_gat_plan_unroll<VEC, GROUP, kUnroll, TX, TYPED>(a, grid, blk, stream);
+    launch_gat_plan_unroll<VEC, GROUP, kUnroll, TX, TYPED, SHIFT>(a, grid, blk, stream);
 }
 
 int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
@@ -511,7 +525,10 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
         return fail(GNNAGG_ERR_ARG, "GAT needs feat >= 1 and feat % heads == 0");
     const int dhead = L.feat / L.heads;
     if (L.tile.on && (L.n1 > 0 || dhead % 4 != 0)) return fail(GNNAGG_ERR_STATE, "internal: tiled GAT launch with segments / odd heads");
-    const bool typed = L.x_dtype != GNNAGG_DTYPE_F32 || L.y_dtype != GNNAGG_DTYPE_F32;
+    // a shifted launch (gnnagg_gat_run_shifted) runs the typed instantiations, fp32 x / y included (TX = float stores an fp32 y)
+    if (L.shift && (L.tile.on || L.part_mode != 0 || L.eperm || L.rows_semantics || L.newval))
+        return fail(GNNAGG_ERR_STATE, "internal: shifted GAT launch on a path without shifted forms");
+    const bool typed = L.x_dtype != GNNAGG_DTYPE_F32 || L.y_dtype != GNNAGG_DTYPE_F32 || L.shift != nullptr;
     if (typed && (L.tile.on || L.part_mode != 0 || L.eperm || L.rows_semantics))
         return fail(GNNAGG_ERR_STATE, "internal: typed GAT launch on a path without 16-bit forms");
     const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
@@ -528,7 +545,7 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     a.xpitch = L.feat; a.ppitch = L.feat; a.x_tile_stride = a.p_tile_stride = g.group * g.vec;
     a.yvec = typed ? align_class(L.feat, L.y, ysize, g.vec) : g.vec;
     a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
-    a.eperm = L.eperm;
+    a.eperm = L.eperm; a.shift = L.shift;
     a.part_mode = L.part_mode; a.den_io = L.den_io;
     if (L.part_mode != 0 && (L.tile.on || !L.den_io || L.newval || g.vec != 4 || g.ntiles != 1))
         return fail(GNNAGG_ERR_ARG, "two-pass GAT: 16-byte aligned rows of at most 256 columns on the chunked plan, no newval");
@@ -546,13 +563,17 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     if (grid > 0) {
         const bool u4 = L.unroll == 4 && !L.tile.on;   // where the geometry has that instantiation (launch_gat_plan_geom)
 #define CALL_GP(TXT, TYPED) launch_gat_plan_geom<VEC, GROUP, TXT, TYPED>(a, u4, grid, blk, stream)
-        if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+#define CALL_GPS(TXT) launch_gat_plan_geom<VEC, GROUP, TXT, true, true>(a, u4, grid, blk, stream)
+        if (L.shift) {
+            if (L.x_dtype == GNNAGG_DTYPE_BF16) { DISPATCH_GEOM_16BIT(g, CALL_GPS(__bf16)) } else { DISPATCH_GEOM(g, CALL_GPS(float)) }
+        } else if (L.x_dtype == GNNAGG_DTYPE_BF16) {
             DISPATCH_GEOM_16BIT(g, CALL_GP(__bf16, true))
         } else if (typed) {
             DISPATCH_GEOM(g, CALL_GP(float, true))
         } else {
             DISPATCH_GEOM(g, CALL_GP(float, false))
         }
+#undef CALL_GPS
 #undef CALL_GP
         HIP_TRY(hipGetLastError());
     }
@@ -566,6 +587,115 @@ int launch_gat_plan(const GatPlanLaunch &L, void *stream_v)
     const int cv = align_class(dhead, L.y, ysize, 4);
     const Geometry cgeo = ybf ? Geometry{cv, 64, ceil_div(L.feat, 64 * cv)} : pick_geometry(L.feat, L.partial, L.y, nullptr, dhead);
     return launch_combine_gat(L.hubs, L.partial, L.partial_den, L.y, L.feat, L.heads, cgeo, stream, nullptr, ybf);
+}
+
+// ------------------------------------------------------------------------- row maximum of the leaky logits
+// shift[r, h] = leaky(att[r, h, 0] + max_{s in N(r)} att[s, h, 1]) (gnnagg_gat_row_shift).  For slope > 0 the fp32 addition, the fp32
+// multiplication by the slope and the select are all non-decreasing in the source term, so this IS the maximum over the row's edges of
+// the fp32 leaky logit the chains form, bit for bit -- from one gather-max over the 4-byte source terms; no feature row is touched.
+// One launch: a workgroup of 256 threads gives its 32 rows to 8-lane groups (lane j reads the ids of edges beg + j + k * 8, coalesced,
+// four gathers in flight); a row above kShiftHubEdges edges is only flagged in LDS and then walked by the whole workgroup, 256 lanes
+// striding, with a wavefront shuffle + LDS reduce.  Heads in blocks of kShiftHeads (the terms of all heads of a source lie in 8 * H
+// contiguous bytes), whatever H.  A maximum is exact in any association: the same bits on every call.  fmaxf drops a NaN term where
+// the other operand is a number (the header leaves that case open).
+struct RowShiftArgs {
+    const int *ptr, *idx;
+    const float *att;
+    float *shift;
+    int V, heads;
+    float slope;
+};
+
+// running maxima of the source terms of heads h0 .. h0 + kShiftHeads - 1 over edges beg + first, + stride, ... of [beg, end)
+__device__ __forceinline__ void shift_gather_max(float (&m)[kShiftHeads], const RowShiftArgs &a, int beg, int end, int first, int stride, int h0)
+{
+    constexpr int U = 4;
+    const int H = a.heads;
+#pragma unroll
+    for (int k = 0; k < kShiftHeads; ++k) m[k] = -INFINITY;
+    for (int e = beg + first; e < end; e += U * stride) {
+        int s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e + u * stride < end) s[u] = a.idx[e + u * stride];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e + u * stride < end) {
+                const float *__restrict__ t = a.att + ((size_t)s[u] * H + h0) * 2 + 1;
+#pragma unroll
+                for (int k = 0; k < kShiftHeads; ++k)
+                    if (h0 + k < H) m[k] = fmaxf(m[k], t[2 * k]);
+            }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gat_row_shift(const RowShiftArgs a)
+{
+    constexpr int G = kShiftGroup, RPB = 256 / G, HB = kShiftHeads, WAVES = 256 / 64;
+    __shared__ int s_hub[RPB];
+    __shared__ float s_red[WAVES][HB];
+    const int H = a.heads;
+    const int lane = threadIdx.x & (G - 1);
+    const int grp = (int)threadIdx.x / G;
+    const int row = blockIdx.x * RPB + grp;
+    int beg = 0, end = 0;
+    if (row < a.V) { beg = a.ptr[row]; end = a.ptr[row + 1]; }
+    const bool hub = end - beg > kShiftHubEdges;
+    if (lane == 0) s_hub[grp] = hub ? row : -1;
+    if (row < a.V && !hub) {
+        for (int h0 = 0; h0 < H; h0 += HB) {
+            float m[HB];
+            shift_gather_max(m, a, beg, end, lane, G, h0);
+#pragma unroll
+            for (int k = 0; k < HB; ++k)
+#pragma unroll
+                for (int off = G / 2; off > 0; off >>= 1) m[k] = fmaxf(m[k], __shfl_xor(m[k], off, G));
+            float v = m[0];   // lane k of the group finishes head h0 + k
+#pragma unroll
+            for (int k = 1; k < HB; ++k)
+                if (lane == k) v = m[k];
+            const int h = h0 + lane;
+            if (lane < HB && h < H)
+                a.shift[(size_t)row * H + h] = beg == end ? 0.0f : leaky_logit(a.att[((size_t)row * H + h) * 2], v, a.slope);
+        }
+    }
+    __syncthreads();
+    for (int g = 0; g < RPB; ++g) {
+        const int hrow = s_hub[g];   // workgroup-uniform
+        if (hrow < 0) continue;
+        const int hb = a.ptr[hrow], he = a.ptr[hrow + 1];
+        for (int h0 = 0; h0 < H; h0 += HB) {
+            float m[HB];
+            shift_gather_max(m, a, hb, he, (int)threadIdx.x, 256, h0);
+#pragma unroll
+            for (int k = 0; k < HB; ++k)
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) m[k] = fmaxf(m[k], __shfl_xor(m[k], off, 64));
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int k = 0; k < HB; ++k) s_red[threadIdx.x / 64][k] = m[k];
+            }
+            __syncthreads();
+            const int h = h0 + (int)threadIdx.x;
+            if (threadIdx.x < HB && h < H) {
+                float v = s_red[0][threadIdx.x];
+#pragma unroll
+                for (int w = 1; w < WAVES; ++w) v = fmaxf(v, s_red[w][threadIdx.x]);
+                a.shift[(size_t)hrow * H + h] = leaky_logit(a.att[((size_t)hrow * H + h) * 2], v, a.slope);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+int launch_gat_row_shift(const int *ptr, const int *idx, const float *att, float *shift, int V, int heads, float slope, void *stream_v)
+{
+    if (V <= 0) return GNNAGG_OK;
+    RowShiftArgs a;
+    a.ptr = ptr; a.idx = idx; a.att = att; a.shift = shift; a.V = V; a.heads = heads; a.slope = slope;
+    hipLaunchKernelGGL(k_gat_row_shift, dim3(ceil_div(V, 256 / kShiftGroup)), dim3(256), 0, (hipStream_t)stream_v, a);
+    HIP_TRY(hipGetLastError());
+    return GNNAGG_OK;
 }
 
 // edge values follow a permuted edge list (val_t[e'] = val[perm[e']]): the partitioned orders re-gather them before every run

@@ -954,11 +954,13 @@ static int prepare_blocked(Ctx *c, Schedule &s, TiledRun &tr, bool span_run, int
 }
 
 // the error of a 16-bit run whose order leaves the plan kernels (kind: "gcn" / "gat"; note: what that flavour adds on "fast_scheduled")
-static int fail_typed_order(const char *kind, int x_dtype, int y_dtype, const char *note)
+// (shifted: the refusal of gnnagg_gat_run_shifted, whose weights only the plan kernel forms)
+static int fail_typed_order(const char *kind, int x_dtype, int y_dtype, const char *note, bool shifted = false)
 {
-    return fail(GNNAGG_ERR_ARG, std::string("gnnagg_") + kind + "_run_typed (x " + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
-                                    (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
-                                    "): this order runs on the item kernels, which are fp32 only -- use GNNAGG_MODE_BALANCED, or a "
+    return fail(GNNAGG_ERR_ARG, std::string("gnnagg_") + kind + (shifted ? "_run_shifted (x " : "_run_typed (x ") +
+                                    (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " + (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") +
+                                    "): this order runs on the item kernels, which " + (shifted ? "have no shifted form" : "are fp32 only") +
+                                    " -- use GNNAGG_MODE_BALANCED, or a "
                                     "neighbor-grouping schedule / \"fast_scheduled\" = 1" + note + " for GNNAGG_MODE_SCHEDULED");
 }
 
@@ -1234,7 +1236,8 @@ static int gat_run(Ctx *c, const GatRequest &r)
     float *y = r.y, *newval = r.newval;
     const int feat = r.feat, heads = r.heads, probe = r.probe, part = r.part;
     int mode = r.mode;
-    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32;
+    // a shifted request (gnnagg_gat_run_shifted) is dispatched like a typed one, fp32 x / y included: the plan kernel or an error
+    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32 || r.shifted;
     if (typed && (probe || part != 0)) return fail(GNNAGG_ERR_ARG, "16-bit features: the two-pass form and the gather probe are fp32 only");
     if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "handle is not a GAT aggregator");
     if (!x || !y || !att) return fail(GNNAGG_ERR_ARG, "null feature/attention pointer");
@@ -1260,7 +1263,7 @@ static int gat_run(Ctx *c, const GatRequest &r)
     const bool typed_on_partitioned = typed && c->partitions > 0;
     const bool on_plan = (mode == GNNAGG_MODE_BALANCED && c->use_plan && (c->partitions == 0 || part != 0 || typed_on_partitioned)) ||
                          (mode == GNNAGG_MODE_SCHEDULED && c->plan_sched.valid);
-    if (typed && !on_plan) return fail_typed_order("gat", r.x_dtype, r.y_dtype, " (without newval)");
+    if (typed && !on_plan) return fail_typed_order("gat", r.x_dtype, r.y_dtype, r.shifted ? "" : " (without newval)", r.shifted != 0);
     if (typed_on_partitioned && mode == GNNAGG_MODE_BALANCED && !c->plan.valid && (rc = build_balanced_plan_keep(c))) return rc;
     if (on_plan) {
         BalancedPlan &p = mode == GNNAGG_MODE_BALANCED ? c->plan : c->plan_sched;
@@ -1272,6 +1275,15 @@ static int gat_run(Ctx *c, const GatRequest &r)
             P.partial_den = c->partial_den.p;
         }
         P.part_mode = part; P.den_io = r.den_io;
+        if (r.shifted) {
+            if (heads <= 0 || feat <= 0 || feat % heads != 0) return fail(GNNAGG_ERR_ARG, "GAT needs feat >= 1 and feat % heads == 0");
+            P.shift = r.shift;
+            if (!P.shift) {   // the row maxima of this call's logits, into the handle's scratch, ahead of the run on the same stream
+                if ((rc = c->shift.reserve((size_t)std::max(c->V, 1) * heads))) return rc;
+                if ((rc = launch_gat_row_shift(c->d_ptr, c->d_idx, att, c->shift.p, c->V, heads, r.slope, c->stream))) return rc;
+                P.shift = c->shift.p;
+            }
+        }
         return launch_gat_plan(P, c->stream);
     }
     if (mode == GNNAGG_MODE_BALANCED && c->partitions > 0 && c->plan_part.valid && c->part_descriptors) {
@@ -1635,7 +1647,7 @@ int gnnagg_plan_info(gnnagg_handle h, double *plan_seconds, double *rows_plan_se
     if (rows_plan_seconds) *rows_plan_seconds = c->rb_plan_seconds;
     if (plan_bytes)
         *plan_bytes = (long long)(c->plan_bytes + sched_device_bytes(c->rb.sched) + (c->rb.span_g.n + c->rb.idx_f.n + c->rb.r1.n) * sizeof(int) + c->rb.hub_mask.n);
-    if (scratch_bytes) *scratch_bytes = (long long)((c->partial.n + c->partial_den.n + c->xt.n + c->yt.n + c->den_t.n + c->att_t.n + c->den.n) * sizeof(float));
+    if (scratch_bytes) *scratch_bytes = (long long)((c->partial.n + c->partial_den.n + c->xt.n + c->yt.n + c->den_t.n + c->att_t.n + c->den.n + c->shift.n) * sizeof(float));
     return GNNAGG_OK;
 }
 
@@ -1869,6 +1881,38 @@ int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const fl
                                     "is fp32 only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
     return gat_run(c, GatRequest{static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, d_newval, 0, 0, nullptr,
                                x_dtype, y_dtype});
+}
+
+int gnnagg_gat_row_shift(gnnagg_handle h, const float *d_att, int heads, float slope, float *d_shift)
+{
+    GET_CTX(h);
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_gat_row_shift: handle is not a GAT aggregator");
+    if (!d_att || !d_shift || heads <= 0) return fail(GNNAGG_ERR_ARG, "gnnagg_gat_row_shift: null attention / shift pointer or heads < 1");
+    if (!(slope > 0.0f)) return fail(GNNAGG_ERR_ARG, "gnnagg_gat_row_shift: slope must be > 0 (the row maximum is taken through a non-decreasing leaky-ReLU)");
+    return launch_gat_row_shift(c->d_ptr, c->d_idx, d_att, d_shift, c->V, heads, slope, c->stream);
+}
+
+int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, const float *d_shift, void *d_y, int y_dtype,
+                           int feat, int heads, float slope, int mode)
+{
+    GET_CTX(h);
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_shifted: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    const std::string combo = std::string("x ") + (x_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32") + ", y " +
+                              (y_dtype == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32");
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_shifted (" + combo + "): handle is not a GAT aggregator");
+    if (heads <= 0 || feat <= 0 || feat % heads != 0)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_shifted (" + combo + "): GAT needs feat >= 1 and feat % heads == 0");
+    if (!d_shift && !(slope > 0.0f))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_shifted (" + combo + "): d_shift == NULL needs slope > 0 (gnnagg_gat_row_shift)");
+    if (mode == GNNAGG_MODE_ROWS && !c->fast_rows)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_run_shifted (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
+                                    "has no shifted form -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
+    GatRequest r{static_cast<const float *>(d_x), d_att, static_cast<float *>(d_y), feat, heads, slope, mode, nullptr, 0, 0, nullptr, x_dtype, y_dtype};
+    r.shift = d_shift; r.shifted = 1;
+    return gat_run(c, r);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

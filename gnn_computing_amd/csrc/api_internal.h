@@ -143,6 +143,7 @@ struct Ctx {
     Schedule sched_edges;    // chunked work items of the edge kernels (run_att, u_add_v, add_to_center, div_each)
     DevBuf<float> den;       // [V,heads] row sums of run_att
     DevBuf<float> partial, partial_den;
+    DevBuf<float> shift;   // gnnagg_gat_run_shifted without a caller's array: V * heads row maxima of the leaky logits
     DevBuf<float> xt;      // 2-D blocked mode: column-tiled image of X, rebuilt by every run (k_tile_x)
     DevBuf<float> att_t;   // 2-D blocked GAT: compact source / centre attention terms per head group, rebuilt by every run (k_tile_att)
 #ifdef GNNAGG_EXTRAS   // older forms kept for A/B parity tests (second tier): run-time switches there, constants in the default build
@@ -232,6 +233,8 @@ struct GatRequest {
     int part = 0;              // two-pass form (gnnagg_gat_run_part)
     float *den_io = nullptr;
     int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+    const float *shift = nullptr;   // gnnagg_gat_run_shifted: the caller's shift array (NULL with shifted set: the handle's scratch)
+    int shifted = 0;
 };
 int gcn_run(Ctx *c, const GcnRequest &r);
 int edge_launch(Ctx *c, EdgeItemLaunch &L, int heads);

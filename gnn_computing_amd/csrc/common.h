@@ -250,10 +250,15 @@ struct GatPlanLaunch : PlanLaunch {
     float slope = 0.2f;
     int rows_semantics = 0;  // 1: `scheduled = 0` semantics (aggr_gat: divide by the denominator unconditionally)
     const int *eperm = nullptr; // permuted orders: original edge of every position (newval is written in CSR edge order)
+    const float *shift = nullptr; // gnnagg_gat_run_shifted: [num_v, heads], subtracted from every leaky logit (typed instantiations)
     int part_mode = 0;          // two-pass form (gnnagg_gat_run_part): 1 = numerator / denominator out, 2 = add to them and divide
     float *den_io = nullptr;    // [num_v, heads]
 };
 int launch_gat_plan(const GatPlanLaunch &a, void *stream);
+// k_gat_row_shift (gnnagg_gat_row_shift): shift[V, heads] = the row maximum of the fp32 leaky logits, +0 for rows without edges.  Rows of
+// up to kShiftHubEdges edges run on kShiftGroup-lane groups, longer ones on their whole workgroup; heads in blocks of kShiftHeads.
+constexpr int kShiftGroup = 8, kShiftHeads = 4, kShiftHubEdges = 1024;
+int launch_gat_row_shift(const int *ptr, const int *idx, const float *att, float *shift, int V, int heads, float slope, void *stream);
 // Backward of the single-head fused GAT aggregation (k_rowdot + k_gat_bwd_edges); wl = chunked edge work items.
 struct GatBwdLaunch {
     WorkList wl;

@@ -552,6 +552,26 @@ __device__ __forceinline__ float edge_weight(float a_dst, float a_src, float slo
     return expf(sc > l ? sc : l);
 }
 
+// max(s, s * slope) with s = a_dst + a_src: the fp32 leaky logit edge_weight() exponentiates (k_gat_row_shift forms the row maximum of it)
+__device__ __forceinline__ float leaky_logit(float a_dst, float a_src, float slope)
+{
+    const float sc = a_dst + a_src;
+    const float l = sc * slope;
+    return sc > l ? sc : l;
+}
+
+// exp(leaky_relu(a_dst + a_src) - shift) (gnnagg_gat_run_shifted): ONE fp32 subtraction of the rounded leaky logit, taken after the select
+// and with contraction off, so that no fma(sc, slope, -shift) can form; shift = 0.0f gives the bits of edge_weight()
+__device__ __forceinline__ float edge_weight_shifted(float a_dst, float a_src, float slope, float shift)
+{
+#pragma clang fp contract(off)
+    const float sc = a_dst + a_src;
+    const float l = sc * slope;
+    const float m = sc > l ? sc : l;
+    const float d = m - shift;
+    return expf(d);
+}
+
 // out_row[j] = sum_k yrow[k] * W[k, j] for j = tid, tid + nthreads, ...: one ascending-k fmaf chain per output (the order of
 // the MFMA tiles and of the oracle's GEMM); yrow lives in LDS.  For the few rows that are finished one at a time.
 __device__ __forceinline__ void row_times_weight(const float *yrow, int K, const float *__restrict__ W, int N, float *out_row,

@@ -298,8 +298,9 @@ int gnnagg_csr2edgelist(gnnagg_handle h, int *d_edgelist);
  * Attention logits (every GAT call, slope > 0):
  *   weights    w_e = expf(s > s * slope ? s : s * slope) with s = att[dst, h, 0] + att[src, h, 1], all in fp32 and WITHOUT subtracting a
  *              row maximum, as the reference (aggr_gat.h:138-143): w_e is +Inf above expf's overflow threshold (a leaky logit above
- *              88.7), +0 below its underflow threshold (below -104), NaN for a NaN term.  Callers that may reach those ranges shift
- *              att[., h, 0] by the row maximum themselves.
+ *              88.7), +0 below its underflow threshold (below -104), NaN for a NaN term.  Callers that may reach those ranges use
+ *              gnnagg_gat_run_shifted below, which subtracts the row maximum of the leaky logits (gnnagg_gat_row_shift) before the exp.
+ *              (Shifting att[., h, 0] instead is NOT the same softmax unless slope = 1: leaky-ReLU does not commute with a shift.)
  *   locality   att[s, h, 1] reaches exactly head h of the rows that have s as a neighbor, att[r, h, 0] exactly head h of row r: every
  *              other element of y and d_newval is bit-equal to the run without the change.
  *   +Inf, NaN  a +Inf or NaN weight in a (row, head) makes that head's columns of the row NaN, in every mode; d_newval holds the +Inf or
@@ -333,6 +334,44 @@ int gnnagg_gat_run(gnnagg_handle h, const float *d_x, const float *d_att, float 
  * and the edge-softmax pieces below. */
 int gnnagg_gat_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, void *d_y, int y_dtype,
                          int feat, int heads, float slope, int mode, float *d_newval);
+/* The max-shifted, overflow-safe edge softmax (no reference counterpart; what DGL's and PyG's edge softmax do).
+ *
+ * shift[V,heads] (fp32): the maximum over the row's edges of the fp32 leaky logit, formed as
+ * leaky(att[r,h,0] + max_s att[s,h,1]) (slope > 0); +0 for a row without edges.
+ * For slope > 0 the fp32 addition, the fp32 multiplication by the slope and the select are non-decreasing, so this is bit for bit the
+ * per-edge maximum of max(s, s * slope), from one gather-max over the 4-byte source terms: no feature row is touched.  Any heads >= 1;
+ * column ids up to max(num_v, largest id + 1) as everywhere.  The same bits on every call.  A (row, head) whose logits are all -Inf
+ * holds -Inf, one with a +Inf logit +Inf; what it holds for a (row, head) with a NaN term is not specified (NaN, or the maximum of the
+ * others).  slope <= 0 returns GNNAGG_ERR_ARG.  Asynchronous on the handle's stream, no allocation, no synchronisation. */
+int gnnagg_gat_row_shift(gnnagg_handle h, const float *d_att, int heads, float slope, float *d_shift);
+/* gnnagg_gat_run_typed with w_e = expf(leaky(att[dst,h,0] + att[src,h,1]) - shift[dst,h]).
+ * d_shift == NULL: the library computes gnnagg_gat_row_shift into scratch of the handle first (same stream).
+ * With the row maximum as the shift every weight is <= 1, the maximal edge of a (row, head) has weight exactly 1, the denominator lies
+ * in [1, degree], and finite attention terms can give neither +Inf nor 0 / 0.
+ *   subtraction  ONE fp32 subtraction of the rounded leaky logit: d = fl32(max(s, s * slope) - shift), then expf(d); never a fused
+ *                s * slope - shift.
+ *   order        the chains, the LDS stage, the partial rows, the hub fold and the division keep the order of gnnagg_gat_run_typed (the
+ *                shift is constant per (row, head): all partial sums of a row are in one scale).  d_shift may be ANY array: an all-zero
+ *                d_shift gives bit for bit what gnnagg_gat_run_typed gives on the same handle and mode (x - 0.0f is x), Inf and NaN
+ *                inputs included.
+ *   types        all four combinations of GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16 for x and y; d_att and d_shift stay fp32.  bf16 as in
+ *                gnnagg_gat_run_typed: exact widening, ONE round-to-nearest-even at the store.  Rows without edges are +0.
+ *   orders       those the 16-bit combinations of gnnagg_gat_run_typed run on, for fp32 x / y too: GNNAGG_MODE_BALANCED on the chunked plan
+ *                (a handle on the 2-D blocked order builds the chunked plan beside it and keeps its blocked order for the other calls),
+ *                GNNAGG_MODE_SCHEDULED where the plan kernel runs it, GNNAGG_MODE_ROWS where "fast_rows" = 1.  Everything else returns
+ *                GNNAGG_ERR_ARG with a text naming the combination -- the canonical rows mode, an order the item kernels run, an unknown
+ *                dtype code -- and nothing falls back to the unshifted run.  There is no d_newval.  Arguments are checked before any
+ *                device call.
+ *   non-finite   plain IEEE: a (row, head) with a NaN or +Inf logit is NaN in that head's columns (Inf - Inf), every other (row, head)
+ *                is bit-equal to the run without the change; a -Inf logit is a weight of +0; a (row, head) whose logits are all -Inf is
+ *                NaN.
+ *   streams      asynchronous on the handle's stream; nothing is synchronised or allocated once the handle's scratch (V * heads floats
+ *                more when d_shift == NULL) exists, and a warm call can be captured in a HIP graph.
+ * Unshifted still: gnnagg_gat_run / _typed themselves, gnnagg_gat_run_att and the three-step adapter below, the span kernels of the 2-D
+ * blocked order, the canonical rows mode, gnnagg_gat_run_part, the distributed step and the backward extras.
+ * (tests/test_gpu_gat_shift.py, tests/test_gat_shift_host.py) */
+int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, const float *d_shift,
+                           void *d_y, int y_dtype, int feat, int heads, float slope, int mode);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns.
