@@ -28,7 +28,7 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False):
+                 stable_softmax=False, fused_nn=False):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -52,6 +52,10 @@ class Model:
         if dtype != torch.float32:
             self.weights, self.weights_lr = [w.to(dtype) for w in self.weights], [w.to(dtype) for w in self.weights_lr]
             self.h, self.outs = self.h.to(dtype), [o.to(dtype) for o in self.outs]
+        # fused_nn (GCN): layer k's aggregation applies the ReLU and multiplies the finished rows by W_{k+1} in the same call
+        # (gnnagg_gcn_run_with_nn_typed): two dense launches fewer, and the activation is not read back for its product
+        self.fused_nn = fused_nn
+        self.feat2 = [torch.empty(self.num_v, DIMS[k + 1], device=dev, dtype=dtype) for k in range(1, 3)] if fused_nn else None
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -65,6 +69,22 @@ class Model:
         if self.trace is not None:
             self.trace.append(dict(feat=feat, w=w, feat2=feat2, out=res.clone()))
         return res
+
+    def forward_gcn_fused_nn(self):
+        """feat2_0 = dense(h, W0); layers 0 and 1: out_k = relu(A . feat2_k) and feat2_{k+1} = out_k . W_{k+1} in one call; a plain
+        aggregation + ReLU for the last layer"""
+        feat, feat2 = self.h, self.dense(self.h, self.weights[0])
+        for k in range(3):
+            out = self.outs[k]
+            if k < 2:
+                self.at.run_with_nn_typed(feat2, out, self.weights[k + 1], self.feat2[k], scheduled=self.sched, relu=True)
+            else:
+                gnc.gcn_run(self.at, feat2, out, 128, self.sched, relu=True)
+            if self.trace is not None:
+                self.trace.append(dict(feat=feat, w=self.weights[k], feat2=feat2, out=out.clone()))
+            if k < 2:
+                feat, feat2 = out, self.feat2[k]
+        return self.outs[2]
 
     def dense_f32(self, a, b):
         """a . b with an fp32 result whatever the operands' type (the GAT attention terms)"""
@@ -81,6 +101,8 @@ class Model:
         return out
 
     def forward(self, model="our_GCN"):
+        if self.fused_nn and model == "our_GCN":
+            return self.forward_gcn_fused_nn()
         x = self.h
         for k in range(3):
             x = (self.gcn_layer(x, self.outs[k], self.weights[k]) if model == "our_GCN"
@@ -102,6 +124,9 @@ def main():
                          "schedule (on high-degree graphs that is the source-partitioned order)")
     ap.add_argument("--fused-relu", action="store_true",
                     help="GCN: apply the ReLU inside the aggregation kernel (GNNAGG_FLAG_RELU) instead of F.relu")
+    ap.add_argument("--fused-nn", action="store_true",
+                    help="GCN: aggregation, ReLU and the NEXT layer's dense combine in one call for layers 0 and 1 "
+                         "(gnnagg_gcn_run_with_nn_typed; fp32 and bf16); ignored by the GAT model")
     ap.add_argument("--dense", default="library", choices=["library", "torch"],
                     help="dense layers: the library's f32-MFMA GEMM (gnnagg_matmul_nn: bit-exact against the oracle, every stage of "
                          "the forward then is; 512 -> 128: 261 us vs rocBLAS 239 us) or torch.mm as the reference script uses")
@@ -123,7 +148,7 @@ def main():
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
-              stable_softmax=args.stable_softmax)
+              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -154,7 +179,7 @@ def main():
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
     print(json.dumps({"model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
-                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
+                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "fused_nn": bool(args.fused_nn), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
 
 
 if __name__ == "__main__":

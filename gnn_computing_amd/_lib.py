@@ -70,6 +70,9 @@ SIGNATURES = {
     "gnnagg_matmul_nn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_matmul_nn_typed": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "gnnagg_gcn_run_with_nn": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
+    "gnnagg_gcn_run_with_nn_typed": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                             c_int, c_int]),
+    "gnnagg_last_nn_path": (c_int, [c_int64, P_INT]),
     "gnnagg_gat_run": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "gnnagg_gat_run_typed": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "gnnagg_gat_row_shift": (c_int, [c_int64, c_void_p, c_int, c_float, c_void_p]),

@@ -252,6 +252,41 @@ class Aggregator_GCN(Aggregator):
                                            _dev_ptr(transformed, torch.float32, "transformed"), int(vin.shape[1]),
                                            int(weight.shape[1]), _mode(scheduled)))
 
+    def run_with_nn_typed(self, vin, vout, weight, transformed, scheduled="balanced", reduce="sum", relu=False):
+        """gnnagg_gcn_run_with_nn_typed: vout = [relu](A.vin) exactly as run() writes it with the same dtypes, and transformed = vout @ weight
+        taken from vout AS STORED.  vin float32 / bfloat16; (vout, weight, transformed) = (float32, float32, float32): the ascending-k fp32
+        chain of matmul_NN; (bfloat16, bfloat16, float32 | bfloat16): the bf16 MFMA product of matmul_NN with fp32 accumulation.
+        vin [V, F], weight [F, N], vout >= V * F elements, transformed >= V * N.  Dtypes and shapes are checked before the library is reached."""
+        xt, yt = _feat_dtype(vin, "vin"), _feat_dtype(vout, "vout")
+        wt, tt = _feat_dtype(weight, "weight"), _feat_dtype(transformed, "transformed")
+        if wt != yt or (yt == _lib.DTYPE_F32 and tt != _lib.DTYPE_F32):
+            raise TypeError("run_with_nn_typed: (vout, weight, transformed) must be (float32, float32, float32) or (bfloat16, bfloat16, "
+                            "float32 | bfloat16), got (%s, %s, %s)" % (vout.dtype, weight.dtype, transformed.dtype))
+        if vin.dim() != 2 or weight.dim() != 2:
+            raise ValueError("run_with_nn_typed: vin must be [V, F] and weight [F, N]")
+        feat, n_out = int(vin.shape[1]), int(weight.shape[1])
+        if int(vin.shape[0]) < self.num_v or int(weight.shape[0]) != feat or feat < 1 or n_out < 1:
+            raise ValueError("run_with_nn_typed: vin [%d, %d] and weight [%d, %d] do not fit num_v = %d rows of F features"
+                             % (vin.shape[0], feat, weight.shape[0], n_out, self.num_v))
+        if vout.numel() < self.num_v * feat:
+            raise ValueError("vout must hold num_v * feat elements")
+        if transformed.numel() < self.num_v * n_out:
+            raise ValueError("transformed must hold num_v * feat_out elements")
+        if reduce not in REDUCE:
+            raise ValueError("reduce must be one of %s" % sorted(REDUCE))
+        self._use_current_stream()
+        check(lib().gnnagg_gcn_run_with_nn_typed(self._h, _dev_ptr(vin, vin.dtype, "vin"), xt, _dev_ptr(vout, vout.dtype, "vout"), yt,
+                                                 _dev_ptr(weight, weight.dtype, "weight"), wt,
+                                                 _dev_ptr(transformed, transformed.dtype, "transformed"), tt, feat, n_out,
+                                                 _mode(scheduled), REDUCE[reduce], _lib.FLAG_RELU if relu else 0))
+
+    def last_nn_path(self):
+        """gnnagg_last_nn_path: 0 no run_with_nn / run_with_nn_typed call on this aggregator yet, 1 the product ran as the epilogue of the
+        aggregation kernel, 2 as a separate GEMM behind the aggregation."""
+        p = ctypes.c_int(0)
+        check(lib().gnnagg_last_nn_path(self._h, ctypes.byref(p)))
+        return p.value
+
     def run_bwd(self, doutput, dinput):
         """d(input) = A^T . d(output) for the sum aggregation with this aggregator's edge values (extension: the reference
         is forward-only).  Deterministic gather over the transposed CSR."""

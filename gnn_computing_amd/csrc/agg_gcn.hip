@@ -372,12 +372,22 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
 #define NN_ROWS 16
 #endif
 static constexpr int kNnRows = NN_ROWS;  // short rows a workgroup of the fused kernel aggregates and multiplies
+#ifndef NN_ROWS_BF16
+#define NN_ROWS_BF16 16
+#endif
+// ... with the bf16 product, which stages W in LDS once per workgroup.  More rows per staging lose: every pass of GPB rows is one more
+// dependent round of gathers per wavefront (arxiv-shaped, bf16 128 -> 32: 16 / 32 / 64 rows 65.3 / 74.6 / 99.0 us; 64 -> 32: 44.1 / 57.6 / 81.3).
+static constexpr int kNnRowsBf16 = NN_ROWS_BF16;
 
 struct NnArgs {
-    const float *weight;  // [K, N] row-major
-    float *out;           // [V, N]
+    const void *weight;  // [K, N] row-major: fp32; bf16 in the bf16-product instantiations (YB)
+    void *out;           // [V, N]: fp32; bf16 where out_bf16 is set (YB only)
     int n_out;
+    int out_bf16;        // (in the struct's tail padding: the kernel arguments of the fp32 instantiations keep their size and offsets)
 };
+// bf16 product: K rounded up to the MFMA's k block, and the pitch of the W image in LDS (elements) -- launcher and kernel agree through these
+__host__ __device__ constexpr int nn_kp(int K) { return (K + 31) & ~31; }
+__host__ __device__ constexpr int nn_wpitch(int K) { return nn_kp(K) + 8; }
 
 // tile: [32][pitch] floats in LDS, columns [K, roundup4(K)) zero; tile_rows[32] = output row or -1.
 // Call right after this thread's tile writes: the function holds the barrier that completes the tile, and issues the
@@ -444,13 +454,128 @@ __device__ __forceinline__ void tile_times_weight(const float *tile, int pitch, 
     if (!synced) __syncthreads();
 }
 
-template <int VEC, int GROUP, bool IS_MAX>
+// ---- bf16 product (gnnagg_gcn_run_with_nn_typed with a bf16 y): the tile holds the rows as Y stores them -- bf16, the one rounding of
+// store_y_typed -- and the product runs on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (the contract of gnnagg_matmul_nn_typed).
+// Operands (cdna_hip_programming.md section 3): lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15],
+// j = 0 .. 7: 16 bytes of a tile row, and 8 consecutive k of ONE column of W -- in row-major W[K, N] eight 2-byte loads N elements
+// apart.  So W is transposed once per workgroup into LDS, wimg[column][k] with k contiguous (8.5 KB at 128 x 32), and both operands are
+// one ds_read_b128 per MFMA.  Both pitches are (a multiple of 32) + 8 elements, an odd number of 16-byte slots: the 16 rows (columns)
+// a b128 lane group reads fall on 16 different slots of the 256-byte bank row.  k >= K and columns >= N are zeros in the image, tile
+// columns >= K are zeros too: nothing behind an operand is read, and a NaN row meets a padding column only where nothing is stored.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// fp32 -> the bf16 value Y stores (bf16x2_bits: the conversion of store_pack_bf16), widened again
+__device__ __forceinline__ float round_to_bf16(float v) { return __uint_as_float(bf16x2_bits(v, 0.0f) << 16); }
+
+// wimg[n][0 .. kp) = W[0 .. K)[n] for the columns n < roundup16(N), zeros beyond K and N.  Where N % 8 == 0 and W is 16-byte aligned, one
+// thread per 8 k x 8 columns: eight 16-byte row pieces (a piece lies inside or outside a row), transposed in registers, one 16-byte LDS store
+// per column (the staging of dense_bf16.hip).  Else one thread per (column, 8 k): 2-byte loads, one 16-byte LDS store.
+__device__ __forceinline__ void stage_weight_bf16(__bf16 *wimg, int wpitch, int kp, const __bf16 *__restrict__ W, int K, int N)
+{
+    const unsigned short *Wu = reinterpret_cast<const unsigned short *>(W);
+    const int ncols = (N + 15) & ~15;
+    if ((N & 7) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0) {
+        const int nco = ncols >> 3;
+        for (int i = threadIdx.x; i < nco * (kp >> 3); i += blockDim.x) {
+            const int col = (i % nco) << 3, k = (i / nco) << 3;
+            unsigned q[8][4];   // q[j]: row k + j, columns col .. col + 7
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                uint4 t = make_uint4(0u, 0u, 0u, 0u);
+                if (k + j < K && col < N) t = *reinterpret_cast<const uint4 *>(Wu + (size_t)(k + j) * N + col);
+                q[j][0] = t.x; q[j][1] = t.y; q[j][2] = t.z; q[j][3] = t.w;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {   // column col + c: element c of every row, k pairs packed
+                unsigned v[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const unsigned a = q[2 * m][c >> 1], b = q[2 * m + 1][c >> 1];
+                    v[m] = (c & 1) ? ((a >> 16) | (b & 0xffff0000u)) : ((a & 0xffffu) | (b << 16));
+                }
+                *reinterpret_cast<uint4 *>(wimg + (size_t)(col + c) * wpitch + k) = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < ncols * (kp >> 3); i += blockDim.x) {
+        const int n = i % ncols, k = (i / ncols) << 3;
+        unsigned q[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[j] = (n < N && k + j < K) ? (unsigned)Wu[(size_t)(k + j) * N + n] : 0u;
+        *reinterpret_cast<uint4 *>(wimg + (size_t)n * wpitch + k) =
+            make_uint4(q[0] | (q[1] << 16), q[2] | (q[3] << 16), q[4] | (q[5] << 16), q[6] | (q[7] << 16));
+    }
+}
+
+// tile: [ROWS][pitch] bf16 in LDS, columns [K, kp) zero; tile_rows[ROWS] = output row or -1.  Holds the barrier that completes the tile
+// and the W image.  D layout: col = lane % 16, row = 4 * (lane / 16) + reg.  out: fp32, or bf16 with one round-to-nearest-even.
+template <int ROWS>
+__device__ __forceinline__ void tile_times_weight_bf16(const __bf16 *tile, int pitch, const int *tile_rows, const __bf16 *wimg, int wpitch,
+                                                       int kp, int N, void *out, int out_bf16)
+{
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int ncb = (N + 15) >> 4, kq = lane >> 4;
+    constexpr int RH = ROWS / 16;
+    __syncthreads();
+#pragma unroll 1
+    for (int st = wave; st < RH * ncb; st += (int)blockDim.x >> 6) {
+        const int rh = st % RH, cb = st / RH;
+        const int col = cb * 16 + (lane & 15);
+        const __bf16 *ap = tile + (rh * 16 + (lane & 15)) * pitch + 8 * kq;
+        const __bf16 *bp = wimg + (size_t)col * wpitch + 8 * kq;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int k0 = 0; k0 < kp; k0 += 32)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8 *>(ap + k0), *reinterpret_cast<const bf16x8 *>(bp + k0),
+                                                          acc, 0, 0, 0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int r = tile_rows[rh * 16 + 4 * kq + v];
+            if (r >= 0 && col < N) {
+                if (out_bf16) static_cast<__bf16 *>(out)[(size_t)r * N + col] = (__bf16)acc[v];
+                else static_cast<float *>(out)[(size_t)r * N + col] = acc[v];
+            }
+        }
+    }
+}
+
+// row_times_weight for the rows a bf16-product launch finishes one at a time: the same ascending-k fmaf chain over the row as Y stores it
+// (yrow: already rounded, round_to_bf16) and W widened -- the products are exact in fp32, K - 1 roundings of the sum, well inside 1e-5 * sum|y w|.
+__device__ __forceinline__ void row_times_weight_bf16(const float *yrow, int K, const __bf16 *__restrict__ W, int N, void *out, size_t out_off,
+                                                      int out_bf16, int tid, int nthreads)
+{
+    const unsigned short *Wu = reinterpret_cast<const unsigned short *>(W);
+    for (int j = tid; j < N; j += nthreads) {
+        float o = 0.0f;
+        int k = 0;
+        for (; k + 8 <= K; k += 8) {
+            float wv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) wv[u] = __uint_as_float((unsigned)Wu[(size_t)(k + u) * N + j] << 16);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) o = fmaf(yrow[k + u], wv[u], o);
+        }
+        for (; k < K; ++k) o = fmaf(yrow[k], __uint_as_float((unsigned)Wu[(size_t)k * N + j] << 16), o);
+        if (out_bf16) static_cast<__bf16 *>(out)[out_off + j] = (__bf16)o;
+        else static_cast<float *>(out)[out_off + j] = o;
+    }
+}
+
+// TX / TYPED (gnnagg_gcn_run_with_nn_typed), as in k_gcn_plan: X of type TX, Y stored through store_y_typed (a.y_bf16, a.yvec), and the
+// finished row goes through finish_gcn_row -- mean and ReLU -- BEFORE it is stored and staged: the product sees what Y holds.  YB: Y is
+// bf16 and so is the product (above); else the fp32 chain of tile_times_weight / row_times_weight.  The defaults are the fp32 kernel
+// without ReLU, instruction for instruction.
+template <int VEC, int GROUP, bool IS_MAX, typename TX = float, bool TYPED = false, bool YB = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArgs a, const NnArgs w)
 {
+    static_assert(TYPED || (std::is_same<TX, float>::value && !YB), "16-bit X / Y need the typed store");
     constexpr int GPB = block_of<GROUP>() / GROUP;
-    constexpr int ROWS = GPB > kNnRows ? GPB : kNnRows;  // rows of the tile
+    constexpr int ROWS = YB ? kNnRowsBf16 : GPB > kNnRows ? GPB : kNnRows;  // rows of the tile
+    static_assert(ROWS % 16 == 0 && ROWS % GPB == 0, "whole 16-row MFMA blocks, whole passes");
     constexpr int PITCH = GROUP * VEC + 4;  // rows stay 16-byte aligned; operand reads (row = lane % 16, k = lane / 16) fall 2 per bank
-    constexpr int kTile = ROWS * PITCH, kStage = kSegChunks * GROUP * VEC;
+    // YB: the tile in bf16, columns zero-padded to the MFMA's k block (KT), rows PITCHB elements apart
+    constexpr int KT = GROUP * VEC < 32 ? 32 : GROUP * VEC, PITCHB = KT + 8;
+    constexpr int kTile = YB ? ROWS * PITCHB / 2 : ROWS * PITCH, kStage = kSegChunks * GROUP * VEC;
     __shared__ float lds[kTile > kStage ? kTile : kStage];
     __shared__ int tile_rows[ROWS];
     const int F = a.feat;
@@ -467,7 +592,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
             for (int k = 0; k < VEC; ++k) acc[k] = IS_MAX ? -INFINITY : 0.0f;
             const int cb = d.x + c * a.chunk;
             const int ce = cb + a.chunk < d.y ? cb + a.chunk : d.y;
-            chain_edges<VEC, GROUP, IS_MAX>(acc, cb, ce, lane, col_ok, a.idx, a.val, a.x + col, F);
+            chain_edges<VEC, GROUP, IS_MAX, kUnroll, TX>(acc, cb, ce, lane, col_ok, a.idx, a.val, reinterpret_cast<const TX *>(a.x) + col, F);
             store_pack<VEC>(&lds[(c * GROUP + lane) * VEC], acc);
         }
         __syncthreads();
@@ -489,12 +614,21 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
                     }
                 }
             if (d.z >= 0) {
-                if (a.mean) {
-                    const float dg = (float)(d.y - d.x);
+                if constexpr (TYPED) {
+                    finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, d.z, nullptr, a.mean, 0, a.relu, nullptr);
+                    store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0, (size_t)d.z * F + col, acc);
+                    if constexpr (YB) {
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k] = acc[k] / dg;
+                        for (int k = 0; k < VEC; ++k) acc[k] = round_to_bf16(acc[k]);
+                    }
+                } else {
+                    if (a.mean) {
+                        const float dg = (float)(d.y - d.x);
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) acc[k] = acc[k] / dg;
+                    }
+                    store_pack<VEC>(a.y + (size_t)d.z * F + col, acc);
                 }
-                store_pack<VEC>(a.y + (size_t)d.z * F + col, acc);
                 store_pack<VEC>(&lds[col], acc);  // chunk 0's slot of this lane: read by nobody else
             } else if (a.hub_count == nullptr) {
                 store_pack<VEC>(a.partial + (size_t)(~d.z) * F + col, acc);
@@ -506,16 +640,27 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
         int row = d.z;
         if (d.z < 0) {  // a hub's segment
             if (a.hub_count == nullptr) return;  // k_combine finishes the row and multiplies it
-            if (!hub_arrive_and_fold<VEC, GROUP, IS_MAX>(a, d, 0, col, col_ok, grp, lane, hub_acc, lds, row)) return;
+            if (!hub_arrive_and_fold<VEC, GROUP, IS_MAX, TYPED>(a, d, 0, col, col_ok, grp, lane, hub_acc, lds, row)) return;
+            if constexpr (YB) {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) hub_acc[k] = round_to_bf16(hub_acc[k]);
+            }
             if (grp == 0 && col_ok) store_pack<VEC>(&lds[col], hub_acc);
         }
         __syncthreads();
         // the row is final: its product, one thread per output column
-        row_times_weight(lds, F, w.weight, w.n_out, w.out + (size_t)row * w.n_out, (int)threadIdx.x, block_of<GROUP>());
+        if constexpr (YB)
+            row_times_weight_bf16(lds, F, static_cast<const __bf16 *>(w.weight), w.n_out, w.out, (size_t)row * w.n_out, w.out_bf16, (int)threadIdx.x,
+                                  block_of<GROUP>());
+        else
+            row_times_weight(lds, F, static_cast<const float *>(w.weight), w.n_out, static_cast<float *>(w.out) + (size_t)row * w.n_out,
+                             (int)threadIdx.x, block_of<GROUP>());
         return;
     }
     const int b = logical_block((int)blockIdx.x - a.n1, a.nblocks0, 1, a.remap, a.xr);
     if (b < 0) return;
+    extern __shared__ __attribute__((aligned(16))) unsigned char nn_wimg[];   // YB: the W image (stage_weight_bf16)
+    if constexpr (YB) stage_weight_bf16(reinterpret_cast<__bf16 *>(nn_wimg), nn_wpitch(F), nn_kp(F), static_cast<const __bf16 *>(w.weight), F, w.n_out);
 #pragma unroll 1
     for (int pass = 0; pass < ROWS / GPB; ++pass) {
         const int slot = pass * GPB + grp;
@@ -530,15 +675,18 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
             if (d.x != d.y) {
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = IS_MAX ? -INFINITY : 0.0f;
-                chain_edges<VEC, GROUP, IS_MAX>(acc, d.x, d.y, lane, col_ok, a.idx, a.val, a.x + col, F);
-                if (a.mean) {
+                chain_edges<VEC, GROUP, IS_MAX, kUnroll, TX>(acc, d.x, d.y, lane, col_ok, a.idx, a.val, reinterpret_cast<const TX *>(a.x) + col, F);
+                if constexpr (TYPED) {
+                    finish_gcn_row<VEC, IS_MAX>(acc, d.y - d.x, row, nullptr, a.mean, 0, a.relu, nullptr);
+                } else if (a.mean) {
                     const float dg = (float)(d.y - d.x);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[k] = acc[k] / dg;
                 }
             }
             if (col_ok) {
-                if (a.wt) store_pack_wt<VEC>(a.y, a.ybytes, (size_t)row * F + col, acc);
+                if constexpr (TYPED) store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, a.wt, a.ybytes, (size_t)row * F + col, acc);
+                else if (a.wt) store_pack_wt<VEC>(a.y, a.ybytes, (size_t)row * F + col, acc);
                 else store_pack<VEC>(a.y + (size_t)row * F + col, acc);
             }
         }
@@ -546,10 +694,24 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan_nn(const PlanArg
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
         }
-        store_pack<VEC>(&lds[slot * PITCH + col], acc);
+        if constexpr (YB) {   // the row as Y stores it: the same conversion, aligned whole lanes
+            __bf16 *trow = reinterpret_cast<__bf16 *>(lds) + slot * PITCHB;
+            store_pack_bf16<VEC>(trow + col, acc, VEC);
+            if constexpr (GROUP * VEC < KT) {
+                const float z[VEC] = {};
+                store_pack_bf16<VEC>(trow + GROUP * VEC + col, z, VEC);
+            }
+        } else {
+            store_pack<VEC>(&lds[slot * PITCH + col], acc);
+        }
         if (lane == 0) tile_rows[slot] = row;
     }
-    tile_times_weight<(GROUP * VEC >= 128 ? 32 : GROUP * VEC / 4), ROWS>(lds, PITCH, tile_rows, w.weight, F, F, w.n_out, w.out);
+    if constexpr (YB)
+        tile_times_weight_bf16<ROWS>(reinterpret_cast<const __bf16 *>(lds), PITCHB, tile_rows, reinterpret_cast<const __bf16 *>(nn_wimg), nn_wpitch(F), nn_kp(F),
+                                     w.n_out, w.out, w.out_bf16);
+    else
+        tile_times_weight<(GROUP * VEC >= 128 ? 32 : GROUP * VEC / 4), ROWS>(lds, PITCH, tile_rows, static_cast<const float *>(w.weight), F, F, w.n_out,
+                                                                           static_cast<float *>(w.out));
 }
 
 // out[rows[i], :] = Y[rows[i], :] . W for a short list of rows (the rows-mode long rows, finished on the auxiliary
@@ -946,13 +1108,29 @@ static void launch_plan_geom(const PlanArgs &a, bool is_max, bool u4, int grid, 
     launch_plan_unroll<VEC, GROUP, PROBE, kUnroll, TX, TYPED>(a, is_max, grid, blk, stream);
 }
 
+// The typed forms of k_gcn_plan_nn (TYPED = true), where the launcher's rule can take them: groups of 16 lanes and more, and (bf16 product)
+// the 8 x 8-element groups of a bf16 row of 64.  yb: the bf16 product (lds_dyn = bytes of its W image).
+template <int VEC, int GROUP, typename TX>
+static void launch_plan_nn_typed(const PlanArgs &a, const NnArgs &w, bool is_max, bool yb, int grid, int blk, size_t lds_dyn, hipStream_t stream)
+{
+    if constexpr (GROUP >= 16 || VEC == 8) {
+        if (yb) {
+            if (is_max) hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, true, TX, true, true>), dim3(grid), dim3(blk), lds_dyn, stream, a, w);
+            else        hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, false, TX, true, true>), dim3(grid), dim3(blk), lds_dyn, stream, a, w);
+        } else if constexpr (GROUP >= 16) {
+            if (is_max) hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, true, TX, true, false>), dim3(grid), dim3(blk), 0, stream, a, w);
+            else        hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, false, TX, true, false>), dim3(grid), dim3(blk), 0, stream, a, w);
+        }
+    }
+}
+
 int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
     if (L.feat <= 0) return fail(GNNAGG_ERR_ARG, "feature length must be >= 1");
     if (L.tile.on && (L.n1 > 0 || L.accumulate)) return fail(GNNAGG_ERR_STATE, "internal: tiled launch with segments");
     const bool typed = L.x_dtype != GNNAGG_DTYPE_F32 || L.y_dtype != GNNAGG_DTYPE_F32;
-    if (typed && (L.tile.on || L.probe || L.nn_weight || L.t0_partials))
+    if (typed && (L.tile.on || L.probe || L.t0_partials))
         return fail(GNNAGG_ERR_STATE, "internal: typed launch on a path without 16-bit forms");
     const int xsize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     const Geometry g = L.tile.on ? tile_geometry(L.tile, L.feat)
@@ -987,11 +1165,33 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
     // dense combine fused as the epilogue when one lane group spans the row and the [32][K] tile fits LDS
     const bool want_nn = L.nn_weight != nullptr;
     // (8-lane groups, F <= 32: the GEMM is ~11 us on the arxiv-shaped input and the epilogue costs as much -- not fused)
-    const bool fuse_nn = want_nn && !L.tile.on && !L.probe && g.ntiles == 1 && g.group >= 16 && !L.accumulate && !L.relu && !L.t0_partials;
+    // nn_typed (gnnagg_gcn_run_with_nn_typed: 16-bit x / y, or the ReLU): the TYPED forms of the kernel.  Their rule adds, for the bf16
+    // product, the 8 x 8-element groups of a bf16 row of 64 (the same 128 bytes as the fp32 rule's narrowest row of 32), and leaves to the
+    // GEMM what those forms do not hold: hubs folded by k_combine, and a tile + W image beyond 64 KB of LDS.
+    // Measured on the arxiv-shaped input against run(relu) + matmul_NN, the pair this call replaces (profiles/nn_typed/bench_nn_typed.jsonl,
+    // the arms that lost: rule_measurements.txt beside it; fused / pair, us, with ReLU, the pair's own spread below 1 us):
+    //   fp32 product                          128 -> 32  97.0 / 108.0,  128 -> 64  110.8 / 123.7,  64 -> 32  57.5 / 61.1,  256 -> 64  209 / 271: fused
+    //   bf16 product, W image <= 8.5 KB       128 -> 32  65.3 / 68.6,  64 -> 32  44.5 / 45.6: fused
+    //   bf16 product, wider W                 128 -> 64  88 / 72 (17 KB),  256 -> 64  182 / 115 (33 KB): the image per 16 rows costs more than
+    //                                         the GEMM's second pass over y saves, and its LDS takes the gathers' occupancy -- NOT fused
+    //   bf16 x -> fp32 y (fp32 product)       128 -> 32  74.5 / 78.9,  128 -> 64  91.2 / 93.8,  256 -> 64  173 / 192: fused;  64 -> 32 on the 8 x 8
+    //                                         groups (one wavefront per workgroup multiplies the tile alone)  50.0 / 49.0 -- NOT fused
+    //   fp32 x -> bf16 y (bf16 product)       128 -> 32  86.4 / 97.6,  64 -> 32  52.6 / 57.6: fused
+    constexpr size_t kNnMaxWimg = (size_t)32 * nn_wpitch(128) * sizeof(__bf16);   // the 128 x 32 image: the widest one measured ahead
+    const bool nn_typed = want_nn && (typed || L.relu);
+    const bool nn_yb = nn_typed && L.y_dtype == GNNAGG_DTYPE_BF16;
+    const size_t nn_lds_dyn = nn_yb ? (size_t)((L.nn_cols + 15) & ~15) * nn_wpitch(L.feat) * sizeof(__bf16) : 0;
+    const size_t nn_lds_tile = nn_yb ? (size_t)kNnRowsBf16 * (std::max(32, g.group * g.vec) + 8) * sizeof(__bf16) : 0;
+    const bool fuse_typed = nn_typed && (g.group >= 16 || (g.vec == 8 && L.feat > 32 && nn_yb)) && (hubs_in_kernel || L.hubs.n_mrows == 0) &&
+                            nn_lds_dyn <= kNnMaxWimg &&
+                            std::max((size_t)kSegChunks * g.group * g.vec * sizeof(float) + 256, nn_lds_tile) + 1024 + nn_lds_dyn <= 64 * 1024;
+    const bool fuse_nn = want_nn && !L.tile.on && !L.probe && g.ntiles == 1 && !L.accumulate && !L.t0_partials &&
+                         (nn_typed ? fuse_typed : g.group >= 16);
+    if (L.nn_path) *L.nn_path = !want_nn ? 0 : fuse_nn ? 1 : 2;
     // 4 gathers per batch when the caller asks for it, where the geometry has that instantiation (launch_plan_geom)
     const bool u4 = L.unroll == 4 && !L.tile.on && !fuse_nn;
     const int blk = block_for(g.group);
-    const int gpb = fuse_nn ? std::max(kNnRows, blk / g.group) : blk / g.group;
+    const int gpb = !fuse_nn ? blk / g.group : nn_yb ? kNnRowsBf16 : std::max(kNnRows, blk / g.group);
     int grid = 0;
     if (int rc = plan_grid(a, g, gpb, L.tile, L.hubs.n_slots, L.t0_cost_prefix, &grid)) return rc;
     if (L.probe) {
@@ -1004,7 +1204,15 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
 #define CALL_PLAN_NN                                                                                                 \
         if (is_max) hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, true>), dim3(grid), dim3(blk), 0, stream, a, w);     \
         else        hipLaunchKernelGGL((k_gcn_plan_nn<VEC, GROUP, false>), dim3(grid), dim3(blk), 0, stream, a, w);
-        if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+        if (fuse_nn && nn_typed) {
+            NnArgs w;
+            w.weight = L.nn_weight; w.out = L.nn_out; w.n_out = L.nn_cols; w.out_bf16 = L.nn_t_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
+            if (L.x_dtype == GNNAGG_DTYPE_BF16) {
+                DISPATCH_GEOM_16BIT(g, (launch_plan_nn_typed<VEC, GROUP, __bf16>(a, w, is_max, nn_yb, grid, blk, nn_lds_dyn, stream)))
+            } else {
+                DISPATCH_GEOM(g, (launch_plan_nn_typed<VEC, GROUP, float>(a, w, is_max, nn_yb, grid, blk, nn_lds_dyn, stream)))
+            }
+        } else if (L.x_dtype == GNNAGG_DTYPE_BF16) {
             DISPATCH_GEOM_16BIT(g, CALL_PLAN(false, __bf16, true))
         } else if (typed) {
             DISPATCH_GEOM(g, CALL_PLAN(false, float, true))
@@ -1012,7 +1220,7 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
             DISPATCH_GEOM(g, CALL_PLAN(true, float, false))
         } else if (fuse_nn) {
             NnArgs w;
-            w.weight = L.nn_weight; w.out = L.nn_out; w.n_out = L.nn_cols;
+            w.weight = L.nn_weight; w.out = L.nn_out; w.n_out = L.nn_cols; w.out_bf16 = 0;
             DISPATCH_GEOM(g, CALL_PLAN_NN)
         } else {
             DISPATCH_GEOM(g, CALL_PLAN(false, float, false))
@@ -1034,14 +1242,17 @@ int launch_gcn_plan(const GcnPlanLaunch &L, void *stream_v)
         } else if (typed) {
             rc = launch_combine_gcn(C, pick_geometry(L.feat, L.partial, L.y, nullptr, L.feat), is_max, stream);
         } else if (fuse_nn) {
-            rc = launch_combine_gcn(C, g, is_max, stream, L.nn_weight, L.nn_out, L.nn_cols);  // hubs: product in the combine
+            rc = launch_combine_gcn(C, g, is_max, stream, static_cast<const float *>(L.nn_weight), static_cast<float *>(L.nn_out), L.nn_cols);  // hubs: product in the combine
         } else {
             rc = launch_combine_gcn(C, g, is_max, stream, nullptr, nullptr, 0, &L.tile);
         }
         if (rc) return rc;
     }
     if (!want_nn || fuse_nn) return GNNAGG_OK;
-    return launch_dense_nn(static_cast<const float *>(L.y), L.nn_weight, L.nn_out, L.num_rows, L.nn_cols, L.feat, stream);
+    if (L.y_dtype == GNNAGG_DTYPE_BF16)   // the stored y, as gnnagg_matmul_nn_typed multiplies it
+        return launch_dense_nn_bf16(L.y, L.nn_weight, L.nn_out, L.nn_t_dtype == GNNAGG_DTYPE_BF16, L.num_rows, L.nn_cols, L.feat, stream);
+    return launch_dense_nn(static_cast<const float *>(L.y), static_cast<const float *>(L.nn_weight), static_cast<float *>(L.nn_out), L.num_rows,
+                           L.nn_cols, L.feat, stream);
 }
 
 int launch_gcn_rows_long(const GcnRowsLongLaunch &L, void *stream_v)

@@ -1092,8 +1092,10 @@ int gcn_run(Ctx *c, const GcnRequest &r)
     const int feat = r.feat, reduce = r.reduce, flags = r.flags, probe = r.probe, relu = (r.flags & GNNAGG_FLAG_RELU) ? 1 : 0;
     const NnRequest *nn = r.nn;
     int mode = r.mode;
-    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32;
-    if (typed && (nn || probe)) return fail(GNNAGG_ERR_ARG, "16-bit features: run_with_nn and the gather probe are fp32 only");
+    // (a gnnagg_gcn_run_with_nn_typed request is dispatched like a typed run, fp32 x / y with the ReLU included: the plan kernel or an error)
+    const bool nn_typed = nn && nn->typed;
+    const bool typed = r.x_dtype != GNNAGG_DTYPE_F32 || r.y_dtype != GNNAGG_DTYPE_F32 || nn_typed;
+    if (typed && ((nn && !nn_typed) || probe)) return fail(GNNAGG_ERR_ARG, "16-bit features: run_with_nn and the gather probe are fp32 only");
     if ((flags & GNNAGG_FLAG_ACCUMULATE) && (mode != GNNAGG_MODE_BALANCED || (reduce != GNNAGG_REDUCE_SUM && !c->row_aux) || !c->use_plan))
         return fail(GNNAGG_ERR_ARG, "GNNAGG_FLAG_ACCUMULATE needs GNNAGG_MODE_BALANCED and GNNAGG_REDUCE_SUM (mean / max: gnnagg_set_row_aux first)");
     // a row_aux array changes what mean / max compute (the row-partitioned step's two passes): the chunked plan kernel implements it
@@ -1101,9 +1103,10 @@ int gcn_run(Ctx *c, const GcnRequest &r)
     if (aux_run && (mode != GNNAGG_MODE_BALANCED || !c->use_plan || nn || probe))
         return fail(GNNAGG_ERR_ARG, "gnnagg_set_row_aux applies to plain GNNAGG_MODE_BALANCED runs only");
     if (c->kind != Ctx::GCN) return fail(GNNAGG_ERR_ARG, "handle is not a GCN aggregator");
-    if ((flags & GNNAGG_FLAG_RELU) && nn) return fail(GNNAGG_ERR_ARG, "GNNAGG_FLAG_RELU is not available in run_with_nn");
+    if ((flags & GNNAGG_FLAG_RELU) && nn && !nn_typed) return fail(GNNAGG_ERR_ARG, "GNNAGG_FLAG_RELU is not available in run_with_nn");
     if (flags & ~(GNNAGG_FLAG_ACCUMULATE | GNNAGG_FLAG_RELU)) return fail(GNNAGG_ERR_ARG, "unknown flag bits");
     if (!x || !y) return fail(GNNAGG_ERR_ARG, "null feature pointer");
+    if (nn) c->last_nn_path = 2;   // (launch_gcn_plan reports the epilogue where it takes it)
     if (reduce < GNNAGG_REDUCE_SUM || reduce > GNNAGG_REDUCE_MAX) return fail(GNNAGG_ERR_ARG, "bad reduce");
     if (mode < GNNAGG_MODE_ROWS || mode > GNNAGG_MODE_BALANCED) return fail(GNNAGG_ERR_ARG, "bad mode");
     if (mode == GNNAGG_MODE_ROWS && c->fast_rows) mode = GNNAGG_MODE_BALANCED;
@@ -1130,7 +1133,8 @@ int gcn_run(Ctx *c, const GcnRequest &r)
         P.row_aux = aux_run ? c->row_aux : nullptr;
         P.num_rows = c->V;
         if (nn) {
-            P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols;
+            P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols; P.nn_w_dtype = nn->w_dtype; P.nn_t_dtype = nn->t_dtype;
+            P.nn_path = &c->last_nn_path;
         }
         P.probe = probe;
         return launch_gcn_plan(P, c->stream);
@@ -1163,7 +1167,7 @@ int gcn_run(Ctx *c, const GcnRequest &r)
         const float *xin;
         if ((rc = tiled_x(c, *s, tr, x, feat, &xin))) return rc;
         P.x = xin;
-        if (nn) { P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols; }
+        if (nn) { P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols; P.nn_path = &c->last_nn_path; }
         P.probe = probe;
         return launch_gcn_plan(P, c->stream);
     }
@@ -1182,7 +1186,7 @@ int gcn_run(Ctx *c, const GcnRequest &r)
         P.xcd_remap = c->xcd_remap; P.num_rows = c->V; P.relu = relu;
         const bool nn_rows_ok = nn && (p.n1 + p.n2 == 0 || feat <= 15000);
         if (nn_rows_ok) {  // short rows: epilogue of the plan kernel (or the GEMM right behind it)
-            P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols;
+            P.nn_weight = nn->weight; P.nn_out = nn->out; P.nn_cols = nn->cols; P.nn_path = &c->last_nn_path;
         }
         rc = launch_gcn_plan(P, c->stream);
         if (fork) {
@@ -1745,6 +1749,44 @@ int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const 
     if (!d_weight || !d_transformed || feat_out <= 0) return fail(GNNAGG_ERR_ARG, "bad run_with_nn arguments");
     const NnRequest nn = {d_weight, d_transformed, feat_out};
     return gcn_run(c, GcnRequest{d_x, d_y, feat_in, mode, GNNAGG_REDUCE_SUM, 0, &nn});
+}
+
+int gnnagg_gcn_run_with_nn_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, const void *d_weight, int w_dtype,
+                                 void *d_transformed, int t_dtype, int feat, int feat_out, int mode, int reduce, int flags)
+{
+    // dtypes, sizes and flags first: nothing here needs the handle, let alone a device
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(x_dtype) || !known(y_dtype) || !known(w_dtype) || !known(t_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed: unknown dtype code (x " + std::to_string(x_dtype) + ", y " + std::to_string(y_dtype) +
+                                        ", weight " + std::to_string(w_dtype) + ", transformed " + std::to_string(t_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    auto name = [](int t) { return t == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32"; };
+    const std::string combo = std::string("x ") + name(x_dtype) + ", y " + name(y_dtype) + ", weight " + name(w_dtype) + ", transformed " + name(t_dtype);
+    if (w_dtype != y_dtype || (y_dtype == GNNAGG_DTYPE_F32 && t_dtype != GNNAGG_DTYPE_F32))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed (" + combo + "): the product is taken from the row as y stores it -- a fp32 y with a "
+                                    "fp32 weight into a fp32 transformed, a bf16 y with a bf16 weight into a fp32 or bf16 transformed; nothing is converted");
+    if (!d_x || !d_y || !d_weight || !d_transformed || feat <= 0 || feat_out <= 0)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed (" + combo + "): bad arguments (a NULL operand, or feat / feat_out below 1)");
+    if (flags & GNNAGG_FLAG_ACCUMULATE)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed (" + combo + "): GNNAGG_FLAG_ACCUMULATE is not available in run_with_nn");
+    GET_CTX(h);
+    NnRequest nn = {static_cast<const float *>(d_weight), static_cast<float *>(d_transformed), feat_out};
+    const bool all_f32 = x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32;
+    if (all_f32 && !(flags & GNNAGG_FLAG_RELU))   // today's path, every order it covers
+        return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn});
+    if (c->kind == Ctx::GCN && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
+                                    "is fp32 without ReLU only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
+    nn.typed = 1; nn.w_dtype = w_dtype; nn.t_dtype = t_dtype;
+    return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn, 0, x_dtype, y_dtype});
+}
+
+int gnnagg_last_nn_path(gnnagg_handle h, int *path)
+{
+    GET_CTX(h);
+    if (!path) return fail(GNNAGG_ERR_ARG, "null path");
+    *path = c->last_nn_path;
+    return GNNAGG_OK;
 }
 
 int gnnagg_gcn_run_clock(gnnagg_handle h, const float *d_x, float *d_y, int feat, int mode, unsigned long long *d_timer,

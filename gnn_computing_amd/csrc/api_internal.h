@@ -196,6 +196,7 @@ struct Ctx {
         gnnagg_handle agg = 0;
     } tr;
 #endif
+    int last_nn_path = 0;      // gnnagg_last_nn_path: 0 no run_with_nn[_typed] yet, 1 epilogue of the aggregation kernel, 2 separate GEMM
     int avg_deg() const { return V > 0 ? (int)((long)E / V) : 0; }
 };
 
@@ -208,6 +209,10 @@ struct NnRequest {  // run_with_nn: transformed[V, cols] = y . weight[feat, cols
     const float *weight;
     float *out;
     int cols;
+    // gnnagg_gcn_run_with_nn_typed (typed = 1): weight / out hold elements of w_dtype / t_dtype, the ReLU is allowed, and the request runs
+    // where gnnagg_gcn_run_typed runs -- the plan kernel, or the typed run's refusal
+    int typed = 0;
+    int w_dtype = GNNAGG_DTYPE_F32, t_dtype = GNNAGG_DTYPE_F32;
 };
 // What the caller of a run asked for.  Built on the caller's stack by the entry points, passed by reference through the dispatch; a
 // re-dispatch (after a rebuild or a demotion of the handle's order) runs the same request again.

@@ -124,9 +124,13 @@ struct GcnPlanLaunch : PlanLaunch {
     int num_rows = 0;    // rows of y
     int t0_partials = 0; // short-row descriptors may carry scratch slots (dest < 0): source-partitioned order
     // dense combine as the epilogue (run_with_nn): nn_out[V, nn_cols] = y . nn_weight[feat, nn_cols]
-    const float *nn_weight = nullptr;
-    float *nn_out = nullptr;
+    // (gnnagg_gcn_run_with_nn_typed: weight / out hold elements of nn_w_dtype / nn_t_dtype -- fp32 . fp32 -> fp32 with a fp32 y, bf16 . bf16 ->
+    // fp32 or bf16 with a bf16 y; the entry point has validated the combination)
+    const void *nn_weight = nullptr;
+    void *nn_out = nullptr;
     int nn_cols = 0;
+    int nn_w_dtype = GNNAGG_DTYPE_F32, nn_t_dtype = GNNAGG_DTYPE_F32;
+    int *nn_path = nullptr;  // receives what the launcher decided: 1 the product ran as the kernel's epilogue, 2 as a GEMM behind it
     int probe = 0;  // 1: gather probe -- the same descriptors, id/value loads and feature gathers, no chain, no stores
 };
 

@@ -223,7 +223,8 @@ int gnnagg_gcn_run_ex(gnnagg_handle h, const float *d_x, float *d_y, int feat, i
  *   feat    any F >= 1; x / y at any 2-byte offset (narrower lanes)
  * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, ACCUMULATE
  * into a bf16 y, the canonical rows mode (fast_rows = 0), an order the item kernels run -- and nothing falls back to fp32.
- * gnnagg_gcn_run_with_nn is fp32 only; the fused GAT aggregation has its own typed call, gnnagg_gat_run_typed. */
+ * gnnagg_gcn_run_with_nn is fp32 only (its typed form: gnnagg_gcn_run_with_nn_typed); the fused GAT aggregation has its own typed
+ * call, gnnagg_gat_run_typed. */
 #define GNNAGG_DTYPE_F32 0
 #define GNNAGG_DTYPE_BF16 1
 int gnnagg_gcn_run_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int mode, int reduce,
@@ -277,7 +278,7 @@ int gnnagg_matmul_nn(const float *d_a, const float *d_b, float *d_c, int m, int 
  *   the same inputs give the same bits on every call; no allocation, synchronisation or memset: capturable in a HIP graph
  * Everything else returns GNNAGG_ERR_ARG with a gnnagg_last_error() text naming the combination -- an unknown dtype code, a and b of
  * different types, fp32 operands with a bf16 c -- nothing is converted and nothing falls back.  Arguments are checked before any
- * device call.  gnnagg_gcn_run_with_nn and its fused aggregation -> GEMM epilogue stay fp32 only. */
+ * device call.  gnnagg_gcn_run_with_nn stays fp32 only; gnnagg_gcn_run_with_nn_typed is the aggregation with this product behind it. */
 int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_dtype, void *d_c, int c_dtype,
                            int m, int n, int k, void *hip_stream);
 /* Aggregator_GCN::run_with_nn, aggr_gcn.h:491-499 (kernel aggr_gcn_nn :304-359): y = A.x, then
@@ -285,6 +286,33 @@ int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_
  * reference accumulates into whatever they held). */
 int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const float *d_weight, float *d_transformed,
                            int feat_in, int feat_out, int mode);
+/* gnnagg_gcn_run_with_nn with typed operands, every reduce and the fused ReLU (no reference counterpart): the aggregate -> ReLU -> next
+ * layer's combine of a GCN forward in one call.  One rule: THE PRODUCT IS TAKEN FROM THE ROW AS IT IS STORED IN y.
+ *   y            bit for bit what gnnagg_gcn_run_typed(h, d_x, x_dtype, d_y, y_dtype, feat, mode, reduce, flags) writes: fp32 chains, the
+ *                ReLU applied to the finished fp32 row, a bf16 y produced by one round-to-nearest-even
+ *   transformed  [V, feat_out] = y . weight[feat, feat_out], row-major
+ *   x            y      weight  transformed   product
+ *   f32 | bf16   f32    f32     f32           the ascending-k fp32 fmaf chain: bit-equal to gnnagg_matmul_nn(y, weight)
+ *   f32 | bf16   bf16   bf16    f32           bf16 MFMA, fp32 accumulation: the contract of gnnagg_matmul_nn_typed (exact where every partial
+ *                                             sum is an integer below 2^24, else within 1e-5 . sum|y w| of the float64 product of the stored y)
+ *   f32 | bf16   bf16   bf16    bf16          one round-to-nearest-even of what the row above computes on the same inputs
+ *   flags   GNNAGG_FLAG_RELU (NaN stays NaN); GNNAGG_FLAG_ACCUMULATE is refused;   reduce  sum, mean, max
+ *   weight / transformed at any element-aligned address; x / y as in gnnagg_gcn_run_typed
+ * Every other dtype combination, a NULL operand, feat / feat_out < 1 and ACCUMULATE return GNNAGG_ERR_ARG with a text naming the function
+ * and the four dtypes, before the handle is looked at.  An all-fp32 request without ReLU is gnnagg_gcn_run_with_nn's path (with `reduce`)
+ * on every order that covers; every other request runs where gnnagg_gcn_run_typed runs (the plan kernel) and is refused with that
+ * function's text elsewhere.  Where the launcher takes the product as the epilogue of the aggregation kernel (one lane group spans the
+ * row, groups of >= 16 lanes, hubs folded in the kernel; bf16 product: also a bf16 row of 64, and a weight of at most 128 x 32) the
+ * finished rows meet in LDS and never come back from memory: the bf16 product then runs on v_mfma_f32_16x16x32_bf16 from a bf16 tile that
+ * is the stored y bit for bit.  Elsewhere the typed aggregation is followed by the dense GEMM on the stored y; the contract is the same on
+ * both paths.  Which shapes take the epilogue is decided by measurement against the back-to-back pair (arxiv-shaped, profiles/nn_typed/:
+ * fp32 128 -> 32 with ReLU 97.0 against 108.0 us, 256 -> 64 209 against 271; bf16 128 -> 32 65.3 against 68.6, 64 -> 32 44.5 against 45.6; the
+ * bf16 epilogue with a wider weight lost -- 128 -> 64 88 against 72 us -- and is not taken). */
+int gnnagg_gcn_run_with_nn_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, const void *d_weight, int w_dtype,
+                                 void *d_transformed, int t_dtype, int feat, int feat_out, int mode, int reduce, int flags);
+/* Which way the last gnnagg_gcn_run_with_nn / gnnagg_gcn_run_with_nn_typed call on this handle took its product: 0 no such call yet,
+ * 1 epilogue of the aggregation kernel, 2 aggregation then separate GEMM.  (What the launcher decided, not a prediction.) */
+int gnnagg_last_nn_path(gnnagg_handle h, int *path);
 /* Input check the reference does not have (an out-of-range neighbor id is a silent out-of-bounds gather there):
  * *bad_rows = rows with ptr[r] > ptr[r+1], *bad_indices = neighbor ids outside [0, num_cols) (num_cols <= 0: num_v).
  * Synchronises the handle's stream. */
