@@ -28,7 +28,7 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False, fused_nn=False):
+                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -56,6 +56,21 @@ class Model:
         # (gnnagg_gcn_run_with_nn_typed): two dense launches fewer, and the activation is not read back for its product
         self.fused_nn = fused_nn
         self.feat2 = [torch.empty(self.num_v, DIMS[k + 1], device=dev, dtype=dtype) for k in range(1, 3)] if fused_nn else None
+        # fused_project (GAT): feat2 = feat . W and the attention terms in one call (gnnagg_gat_project) instead of two dense launches, with
+        # a_dst = w_lr[:, 0] (the centre term's vector) and a_src = w_lr[:, 1].  heads > 1 (through gat_project only): H heads of
+        # DIMS[k + 1] / H columns, attention vectors [H, D] drawn behind every other seeded tensor
+        if heads != 1 and not fused_project:
+            raise ValueError("heads > 1 runs through gat_project: pass fused_project=True")
+        self.fused_project, self.heads = fused_project, heads
+        if fused_project:
+            if heads == 1:
+                self.a_dst = [w[:, 0].contiguous() for w in self.weights_lr]
+                self.a_src = [w[:, 1].contiguous() for w in self.weights_lr]
+            else:
+                vec = lambda k: (torch.randn(heads, DIMS[k + 1] // heads, device=dev) / (DIMS[k + 1] // heads) ** 0.5).to(dtype)
+                self.a_dst, self.a_src = [vec(k) for k in range(3)], [vec(k) for k in range(3)]
+            self.feat2_gat = [torch.empty(self.num_v, DIMS[k + 1], device=dev, dtype=dtype) for k in range(3)]
+            self.att = [torch.empty(self.num_v, heads, 2, device=dev) for k in range(3)]
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -100,13 +115,27 @@ class Model:
             self.trace.append(dict(feat=feat, w=w, w_lr=w_lr, feat2=feat2, att=att_lr, out=out.clone()))
         return out
 
+    def gat_layer_project(self, feat, out, k):
+        """gat_layer with the projection and the attention terms in one call"""
+        w = self.weights[k]
+        feat2, att = gnc.gat_project(feat, w, self.a_dst[k], self.a_src[k], self.heads, feat=self.feat2_gat[k], att=self.att[k])
+        self.at_gat.run(feat2, att, out, 128, self.sched, heads=self.heads, stable=self.stable_softmax)
+        if self.trace is not None:
+            self.trace.append(dict(feat=feat, w=w, a_dst=self.a_dst[k], a_src=self.a_src[k], heads=self.heads, feat2=feat2.clone(),
+                                   att=att.clone(), out=out.clone(), path=gnc.last_project_path()))
+        return out
+
     def forward(self, model="our_GCN"):
         if self.fused_nn and model == "our_GCN":
             return self.forward_gcn_fused_nn()
         x = self.h
         for k in range(3):
-            x = (self.gcn_layer(x, self.outs[k], self.weights[k]) if model == "our_GCN"
-                 else self.gat_layer(x, self.outs[k], self.weights[k], self.weights_lr[k]))
+            if model == "our_GCN":
+                x = self.gcn_layer(x, self.outs[k], self.weights[k])
+            elif self.fused_project:
+                x = self.gat_layer_project(x, self.outs[k], k)
+            else:
+                x = self.gat_layer(x, self.outs[k], self.weights[k], self.weights_lr[k])
         return x
 
 
@@ -127,6 +156,11 @@ def main():
     ap.add_argument("--fused-nn", action="store_true",
                     help="GCN: aggregation, ReLU and the NEXT layer's dense combine in one call for layers 0 and 1 "
                          "(gnnagg_gcn_run_with_nn_typed; fp32 and bf16); ignored by the GAT model")
+    ap.add_argument("--fused-project", action="store_true",
+                    help="GAT: the projection and the attention terms of a layer in one call (gnnagg_gat_project) instead of two dense "
+                         "launches; ignored by the GCN model")
+    ap.add_argument("--heads", type=int, default=1,
+                    help="GAT: attention heads (dividing 128, 64 and 32); more than one runs through gat_project (implies --fused-project)")
     ap.add_argument("--dense", default="library", choices=["library", "torch"],
                     help="dense layers: the library's f32-MFMA GEMM (gnnagg_matmul_nn: bit-exact against the oracle, every stage of "
                          "the forward then is; 512 -> 128: 261 us vs rocBLAS 239 us) or torch.mm as the reference script uses")
@@ -148,7 +182,7 @@ def main():
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
-              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn)
+              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or args.heads != 1, heads=args.heads)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -179,7 +213,7 @@ def main():
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
     print(json.dumps({"model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
-                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "fused_nn": bool(args.fused_nn), "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
+                      "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "fused_nn": bool(args.fused_nn), "fused_project": bool(m.fused_project), "heads": args.heads, "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
 
 
 if __name__ == "__main__":

@@ -69,6 +69,8 @@ SIGNATURES = {
     "gnnagg_csr2edgelist": (c_int, [c_int64, c_void_p]),
     "gnnagg_matmul_nn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_matmul_nn_typed": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_gat_project": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, P_INT,
+                                   c_void_p]),
     "gnnagg_gcn_run_with_nn": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
     "gnnagg_gcn_run_with_nn_typed": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_int]),

@@ -461,6 +461,74 @@ def matmul_NN(A, B, C=None, out_dtype=None):
     return C
 
 
+_last_project_path = 0
+
+
+def gat_project(x, W, a_dst, a_src, heads=1, feat=None, att=None, out_dtype=None):
+    """gnnagg_gat_project: the front half of a GAT layer in one call.  Returns (feat, att):
+        feat [M, N] = x [M, K] @ W [K, N], N = heads * D -- bit for bit what matmul_NN(x, W, out_dtype=...) returns;
+        att [M, heads, 2] float32, what Aggregator_GAT.run(feat, att, ..., heads=heads) reads: att[r, h, 0] = sum_c feat[r, h D + c] a_dst[h, c]
+        (the centre term), att[r, h, 1] the same with a_src (the source term), taken from feat as stored, fp32 products and sums.
+    Device tensors, contiguous: x, W, a_dst, a_src all float32 (feat float32) or all bfloat16 (feat bfloat16, or float32 with
+    out_dtype=torch.float32 or a float32 `feat`); a_dst / a_src are [heads, D] (any shape of heads * D elements for heads = 1).  feat / att: optional
+    outputs to write into.  Runs on torch's current stream.  last_project_path() tells which way the call took."""
+    global _last_project_path
+    tx, tw = _feat_dtype(x, "x"), _feat_dtype(W, "W")
+    for t, name in ((a_dst, "a_dst"), (a_src, "a_src")):
+        if _feat_dtype(t, name) != tw:
+            raise TypeError("%s must have W's dtype %s, got %s" % (name, W.dtype, t.dtype))
+    if tx != tw:
+        raise TypeError("x (%s) and W (%s) must have the same dtype" % (x.dtype, W.dtype))
+    if feat is not None:
+        tf = _feat_dtype(feat, "feat")
+        if out_dtype is not None and out_dtype != feat.dtype:
+            raise TypeError("feat is %s but out_dtype is %s" % (feat.dtype, out_dtype))
+    else:
+        if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+            raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+        tf = FEATURE_DTYPES[x.dtype if out_dtype is None else out_dtype]
+    if tx == _lib.DTYPE_F32 and tf != _lib.DTYPE_F32:
+        raise TypeError("gat_project: float32 operands give a float32 feat (nothing is converted)")
+    if att is not None and (not isinstance(att, torch.Tensor) or att.dtype != torch.float32):
+        raise TypeError("att must be a torch.float32 tensor")
+    heads = int(heads)
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[0]:
+        raise ValueError("gat_project: x %s and W %s do not multiply" % (tuple(x.shape), tuple(W.shape)))
+    M, K = x.shape
+    N = W.shape[1]
+    if heads < 1 or N % heads != 0:
+        raise ValueError("gat_project: heads = %d does not divide W's %d columns" % (heads, N))
+    for t, name in ((a_dst, "a_dst"), (a_src, "a_src")):
+        if t.numel() != N or (heads > 1 and tuple(t.shape) != (heads, N // heads)):
+            raise ValueError("gat_project: %s %s is not [%d, %d]" % (name, tuple(t.shape), heads, N // heads))
+    if feat is None:
+        feat = torch.empty((M, N), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
+    elif tuple(feat.shape) != (M, N):
+        raise ValueError("gat_project: feat %s is not [%d, %d]" % (tuple(feat.shape), M, N))
+    if att is None:
+        att = torch.empty((M, heads, 2), dtype=torch.float32, device=x.device)
+    elif att.numel() != M * heads * 2:
+        raise ValueError("gat_project: att %s does not hold [%d, %d, 2]" % (tuple(att.shape), M, heads))
+    for t, name in ((x, "x"), (W, "W"), (a_dst, "a_dst"), (a_src, "a_src"), (feat, "feat"), (att, "att")):
+        if not t.is_cuda:
+            raise ValueError("%s must be a HIP device tensor" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    path = ctypes.c_int(0)
+    check(lib().gnnagg_gat_project(_dev_ptr(x, x.dtype, "x"), tx, _dev_ptr(W, W.dtype, "W"), tw, _dev_ptr(a_dst, W.dtype, "a_dst"),
+                                   _dev_ptr(a_src, W.dtype, "a_src"), _dev_ptr(feat, feat.dtype, "feat"), tf, _dev_ptr(att, torch.float32, "att"),
+                                   int(M), int(N), int(K), heads, ctypes.byref(path), stream))
+    _last_project_path = path.value
+    return feat, att
+
+
+def last_project_path():
+    """Which way the last gat_project call of this process took its attention terms: 0 none yet (or an empty call), 1 the epilogue of the
+    GEMM kernel, 2 a row-dot kernel behind the GEMM (gnnagg_gat_project's *path: what the launcher did, not a prediction)."""
+    return _last_project_path
+
+
 def load_graph_host(dset, reorder="", datadir="../data/", shuffle=True):
     """gnnagg_load_graph -> dict of numpy arrays (ptr, idx, rows, reverse_rows)."""
     L = lib()

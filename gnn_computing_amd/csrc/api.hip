@@ -1742,6 +1742,59 @@ int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_
     return launch_dense_nn_bf16(d_a, d_b, d_c, c_dtype == GNNAGG_DTYPE_BF16, m, n, k, hip_stream);
 }
 
+#pragma GCC visibility push(hidden)
+// The fuse rule of gnnagg_gat_project (bf16 operands), from profiles/gat_project/rule_measurements.txt: the epilogue wherever the kernel covers
+// the shape.  It wins with one head over N and with N <= 64; at N = 128 with several heads it ties GEMM + row-dot at 169 343 rows and loses
+// 0.3 .. 2.8 us below 16 384 rows -- kept on the epilogue (one launch, one graph node), the place to start when that loss matters.
+static bool project_fuses(int m, int n, int k, int heads) { return dense_nn_bf16_att_fuses(m, n, k, heads) != 0; }
+#pragma GCC visibility pop
+
+int gnnagg_gat_project(const void *d_x, int x_dtype, const void *d_w, int w_dtype, const void *d_a_dst, const void *d_a_src, void *d_feat,
+                       int feat_dtype, float *d_att, int m, int n, int k, int heads, int *path, void *hip_stream)
+{
+    // everything the host can decide first: no device call before the arguments stand
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (!known(x_dtype) || !known(w_dtype) || !known(feat_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_project: unknown dtype code (x " + std::to_string(x_dtype) + ", w " + std::to_string(w_dtype) +
+                                        ", feat " + std::to_string(feat_dtype) + "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    auto name = [](int t) { return t == GNNAGG_DTYPE_BF16 ? "bf16" : "fp32"; };
+    const std::string combo = std::string("x ") + name(x_dtype) + ", w " + name(w_dtype) + ", feat " + name(feat_dtype);
+    if (x_dtype != w_dtype || (x_dtype == GNNAGG_DTYPE_F32 && feat_dtype != GNNAGG_DTYPE_F32))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_project (" + combo + "): the projection runs fp32 . fp32 -> fp32 and bf16 . bf16 -> fp32 or bf16, with "
+                                    "a_dst / a_src in w's type; nothing is converted");
+    if (m < 0 || n < 0 || k < 0 || heads < 1 || n % heads != 0)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_project (" + combo + "): bad sizes (m " + std::to_string(m) + ", n " + std::to_string(n) + ", k " +
+                                        std::to_string(k) + ", heads " + std::to_string(heads) + "): m, n, k >= 0, heads >= 1, n % heads == 0");
+    if (m > 0 && (!d_att || (n > 0 && (!d_feat || !d_a_dst || !d_a_src || (k > 0 && (!d_x || !d_w))))))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gat_project (" + combo + "): a NULL operand");
+    if (path) *path = 0;
+    if (m == 0) return GNNAGG_OK;
+    const int bf = x_dtype == GNNAGG_DTYPE_BF16, feat_bf = feat_dtype == GNNAGG_DTYPE_BF16;
+    int rc;
+    if (n == 0 || k == 0) {   // empty sums: +0 in feat and att
+        if (path) *path = 2;
+        if (n > 0 && (rc = bf ? launch_dense_nn_bf16(d_x, d_w, d_feat, feat_bf, m, n, 0, hip_stream)
+                              : launch_dense_nn(static_cast<const float *>(d_x), static_cast<const float *>(d_w), static_cast<float *>(d_feat), m, n, 0,
+                                                hip_stream)))
+            return rc;
+        return launch_zero_words(d_att, (size_t)m * heads * 2, hip_stream);
+    }
+    // Path 1 where the bf16 kernel's epilogue covers the shape AND won against GEMM + row-dot (project_fuses); path 2: every fp32 call and every
+    // other bf16 shape.  GNNAGG_GAT_PROJECT_FUSE, read at every call, is the switch of that measurement (scripts/bench_gat_project.py): 0 = path 2
+    // everywhere, 1 = the epilogue wherever the kernel covers the shape.
+    const char *fuse_env = getenv("GNNAGG_GAT_PROJECT_FUSE");
+    const int force = fuse_env && (fuse_env[0] == '0' || fuse_env[0] == '1') ? fuse_env[0] - '0' : -1;
+    if (bf && force != 0 && (force == 1 ? dense_nn_bf16_att_fuses(m, n, k, heads) : project_fuses(m, n, k, heads))) {
+        if (path) *path = 1;
+        return launch_dense_nn_bf16_att(d_x, d_w, d_feat, feat_bf, d_a_dst, d_a_src, d_att, m, n, k, heads, hip_stream);
+    }
+    if (path) *path = 2;
+    if ((rc = bf ? launch_dense_nn_bf16(d_x, d_w, d_feat, feat_bf, m, n, k, hip_stream)
+                 : launch_dense_nn(static_cast<const float *>(d_x), static_cast<const float *>(d_w), static_cast<float *>(d_feat), m, n, k, hip_stream)))
+        return rc;
+    return launch_gat_rowdot(d_feat, feat_bf, d_a_dst, d_a_src, bf, d_att, m, n, heads, hip_stream);
+}
+
 int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const float *d_weight, float *d_transformed,
                            int feat_in, int feat_out, int mode)
 {

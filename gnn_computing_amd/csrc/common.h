@@ -293,6 +293,13 @@ int launch_dense_rows(const int *rows, int n_rows, const float *Y, const float *
 int launch_dense_nn(const float *A, const float *B, float *C, int M, int N, int K, void *stream);
 // bf16 A / B, fp32 accumulation on the bf16 MFMA; C fp32 or (c_bf16) one RNE rounding of it (dense_bf16.hip)
 int launch_dense_nn_bf16(const void *A, const void *B, void *C, int c_bf16, int M, int N, int K, void *stream);
+// gnnagg_gat_project.  Path 1: the same product with att[M, heads, 2] (from C as stored, a_dst / a_src bf16 [heads, N / heads]) as the epilogue of
+// the GEMM kernel, where dense_nn_bf16_att_fuses says the kernel covers the shape.  Path 2: att from a finished feat (gat_project.hip).
+int dense_nn_bf16_att_fuses(int M, int N, int K, int heads);
+int launch_dense_nn_bf16_att(const void *A, const void *B, void *C, int c_bf16, const void *a_dst, const void *a_src, float *att, int M, int N, int K,
+                             int heads, void *stream);
+int launch_gat_rowdot(const void *feat, int feat_bf16, const void *a_dst, const void *a_src, int a_bf16, float *att, int M, int N, int heads,
+                      void *stream);
 int launch_check_csr(const int *ptr, const int *idx, int V, int E, int num_cols, int *d_counts, void *stream);
 int launch_pack_rows(const float *x, const int *ids, int n, int feat, float *out, void *stream);
 int launch_pack_rows2(const float *x, const float *att, const int *ids, int n, int feat, int att_w, float *out, void *stream);

@@ -29,6 +29,14 @@
 //    loads).  Every class runs this kernel.  B is read in 16-byte pieces where N % 8 == 0 and its address allow, else in elements.  C is
 //    stored element by element: 32 consecutive columns of a row per half wavefront.
 //  * bf16 C: the same accumulators, one round-to-nearest-even conversion (v_cvt_pk_bf16_f32: NaN kept, overflow to inf) at the store.
+//  * EPI = G (gnnagg_gat_project, launch_dense_nn_bf16_att): the GAT attention terms att[row, head, 0 / 1] = sum over the head's columns of
+//    C AS STORED times a_dst / a_src, taken from the accumulators behind a tile's C stores.  One column block holds all of N; a_dst /
+//    a_src lie in LDS behind the image as fp32 (zeros in padded columns), not in registers across the loop.  A lane holds column 32 t + r
+//    of 16 rows: it adds the products of the tiles of one head (tph tiles where a head is wider than 32 columns), then the G = min(D, 32)
+//    lanes of the head add up -- a halving exchange (every step hands half of the lane's rows to its partner: v_permlane16_swap across
+//    the two 16-lane rows, then DPP row_mirror / row_half_mirror / quad_perm), 31 additions for 32 lanes x 32 values, a fixed order.  An even
+//    lane ends up with the finished (dst, src) pairs of 32 / G rows and stores them under the C store's row guard.  EPI = 0 is the kernel as
+//    it was: the same signature (the epilogue's arguments are a parameter pack, empty there) and the same instructions.
 #include "kernel_util.cuh"
 
 namespace gnnagg {
@@ -90,13 +98,77 @@ __device__ __forceinline__ uint4 fix_a_tail(uint4 v, int k, int K, bool ok)
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// ---- the attention-term epilogue (EPI != 0)
+struct AttEpi {
+    const __bf16 *a_dst, *a_src;   // [heads, D] = [N]
+    float *att;                    // [M, heads, 2]
+    int heads, tph;                // tph: tiles per head (EPI = 32; 1 otherwise)
+};
+struct __attribute__((aligned(4))) AttPair { float dst, src; };   // 8 bytes at a dword-aligned address
+template <class... EP>
+__device__ __forceinline__ const AttEpi &att_epi_of(const AttEpi &e, const EP &...) { return e; }
+template <int CTRL>
+__device__ __forceinline__ float att_dpp(float x)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
+}
+// one halving step over lane pairs (i, partner(i)) that differ in the lane bit `up` tests: the lane keeps the upper (up) or lower N / 2
+// of its N (dst, src) pairs and adds the partner's partial sums of the same ones
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+template <int N, int CTRL>
+__device__ __forceinline__ void att_halve(f32x2_t (&u)[16], bool up)
+{
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+        const f32x2_t keep = up ? u[j + N / 2] : u[j], send = up ? u[j] : u[j + N / 2];
+        u[j].x = keep.x + att_dpp<CTRL>(send.x);
+        u[j].y = keep.y + att_dpp<CTRL>(send.y);
+    }
+}
+// u[v]: this lane's partial (dst, src) sums for row row0 + (v & 3) + 8 * (v >> 2) + 4 * h.  The G lanes of a head (aligned to G) add up; the
+// even lane r then holds rows v = ((r >> 1) & (G / 2 - 1)) * (32 / G) + j, j < 32 / G, and stores them.
+template <int G>
+__device__ __forceinline__ void att_reduce_store(f32x2_t (&u)[16], int r, int h, long row0, long wrow1, int head, int heads, float *__restrict__ att)
+{
+    if constexpr (G == 32) {   // rows 8 .. 15 of the values to lanes 16 .. 31: odd 16-lane rows of lo <-> even ones of hi
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const auto d = __builtin_amdgcn_permlane16_swap(__float_as_uint(u[j].x), __float_as_uint(u[j + 8].x), false, false);
+            const auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(u[j].y), __float_as_uint(u[j + 8].y), false, false);
+            u[j].x = __uint_as_float(d[0]) + __uint_as_float(d[1]);
+            u[j].y = __uint_as_float(s[0]) + __uint_as_float(s[1]);
+        }
+    }
+    constexpr int N0 = G == 32 ? 8 : 16;
+    if constexpr (G >= 16) att_halve<N0, 0x140>(u, (r & 8) != 0);   // row_mirror: partner 15 - i
+    constexpr int N1 = G >= 16 ? N0 / 2 : N0;
+    att_halve<N1, 0x141>(u, (r & 4) != 0);      // row_half_mirror: partner i ^ 7
+    att_halve<N1 / 2, 0x1b>(u, (r & 2) != 0);   // quad_perm [3, 2, 1, 0]: partner i ^ 3
+    constexpr int NV = 32 / G;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {   // quad_perm [1, 0, 3, 2]: both lanes of a pair get the total
+        u[j].x += att_dpp<0xb1>(u[j].x);
+        u[j].y += att_dpp<0xb1>(u[j].y);
+    }
+    if ((r & 1) == 0 && head < heads) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int v = ((r >> 1) & (G / 2 - 1)) * NV + j;
+            const long row = row0 + (v & 3) + 8 * (v >> 2) + 4 * h;
+            if (row < wrow1) *reinterpret_cast<AttPair *>(att + ((size_t)row * heads + head) * 2) = AttPair{u[j].x, u[j].y};
+        }
+    }
+}
+
 // grid: gx persistent workgroups per column block, column block = blockIdx.x / gx (x-fastest: the column blocks of a row range start
 // together).  rpw = rows per wavefront; kimg = k of an LDS image (!MULTI: K rounded up to 8; MULTI: kBfChunk), pitch = its row pitch.
-template <int NT, int AV, bool MULTI>
+// EPI = 8, 16, 32: the lanes that hold one head's columns of a tile; ep is one AttEpi (the grid is one column block: col0 = 0).
+template <int NT, int AV, bool MULTI, int EPI = 0, class... EP>
 __global__ __launch_bounds__(kBfThreads) void k_dense_nn_bf16(const __bf16 *__restrict__ A, const __bf16 *__restrict__ B,
                                                                                void *__restrict__ C, int c_bf16, int M, int N, int K, int kimg,
-                                                                               int pitch, int rpw, int gx, int b_vec)
+                                                                               int pitch, int rpw, int gx, int b_vec, EP... ep)
 {
+    static_assert(EPI == 0 ? sizeof...(EP) == 0 : (sizeof...(EP) == 1 && !MULTI), "the epilogue takes one AttEpi and a single image");
     extern __shared__ __attribute__((aligned(16))) unsigned char bf16_lds[];
     __bf16 *bt = reinterpret_cast<__bf16 *>(bf16_lds);
     constexpr int NB = 32 * NT;
@@ -167,6 +239,14 @@ __global__ __launch_bounds__(kBfThreads) void k_dense_nn_bf16(const __bf16 *__re
     int c_it = 0, c_ss = 0, c_in = 0;   // the superstep the MFMAs are at; c_in = its index inside the LDS image
     if constexpr (!MULTI) {   // all of K in one image: staged once, behind the first requests for A
         stage(0);
+        if constexpr (EPI != 0) {   // behind the image: a_dst[0 .. NB), a_src[0 .. NB) as fp32, zeros beyond N
+            const AttEpi &e = att_epi_of(ep...);
+            float *al = reinterpret_cast<float *>(bf16_lds + (size_t)NB * pitch * sizeof(__bf16));
+            for (int i = threadIdx.x; i < 2 * NB; i += kBfThreads) {
+                const int c = i < NB ? i : i - NB;
+                al[i] = c < N ? (float)(i < NB ? e.a_dst : e.a_src)[c] : 0.0f;
+            }
+        }
         __syncthreads();
     }
     // One flat sequence of supersteps, tile after tile, so that every ring slot is a real request.  c_it, c_ss, c_in are
@@ -216,6 +296,35 @@ __global__ __launch_bounds__(kBfThreads) void k_dense_nn_bf16(const __bf16 *__re
                         }
                     }
                 }
+                if constexpr (EPI != 0) {   // the attention terms of the tile's rows, from C as stored; stores, so ahead of the request below
+                    const AttEpi &e = att_epi_of(ep...);
+                    const float *al = reinterpret_cast<const float *>(bf16_lds + (size_t)NB * pitch * sizeof(__bf16));
+                    f32x2_t u[16] = {};
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        // (wave-uniform, like every branch here) nothing to do for a phantom tile beyond the wavefront's rows, nor for a
+                        // tile of padded columns, which holds no head
+                        if (row0 >= wrow1 || 32 * t >= N) continue;
+                        const f32x2_t a2 = {al[32 * t + r], al[NB + 32 * t + r]};
+                        // one head over several tiles (EPI = 32): its padded columns share the sum, and a NaN row has left NaN there
+                        const bool pad = EPI == 32 && 32 * t + r >= N;
+                        if (EPI < 32 || t % e.tph == 0) {
+#pragma unroll
+                            for (int v = 0; v < 16; ++v) {
+                                const float c = c_bf16 ? (float)(__bf16)acc[t][v] : acc[t][v];
+                                u[v] = a2 * (pad ? 0.0f : c);
+                            }
+                        } else {
+#pragma unroll
+                            for (int v = 0; v < 16; ++v) {
+                                const float c = c_bf16 ? (float)(__bf16)acc[t][v] : acc[t][v];
+                                u[v] += a2 * (pad ? 0.0f : c);
+                            }
+                        }
+                        if (EPI < 32 || (t + 1) % e.tph == 0 || 32 * (t + 1) >= N)   // the head's last tile
+                            att_reduce_store<EPI>(u, r, h, row0, wrow1, EPI == 32 ? t / e.tph : (32 * t + r) / EPI, e.heads, e.att);
+                    }
+                }
             }
             if (++c_in == spc) c_in = 0;
             if (++c_ss == nss) { c_ss = 0; c_in = 0; ++c_it; }
@@ -237,27 +346,76 @@ __global__ __launch_bounds__(256) void k_zero_bf16(unsigned short *__restrict__ 
 // row pitch of an image of kext elements (kext % 8 == 0): at least one octet more, and an odd number of 16-byte units
 static long image_pitch(long kext) { return kext + 8 + ((kext / 8) % 2 ? 8 : 0); }
 
-template <int NT, int AV, bool MULTI>
+template <int NT, int AV, bool MULTI, int EPI = 0, class... EP>
 int call_dense_nn_bf16(const __bf16 *A, const __bf16 *B, void *C, int c_bf16, int M, int N, int K, int kimg, int pitch, int rpw, int gx, int ncolb,
-                       size_t lds, int b_vec, hipStream_t stream)
+                       size_t lds, int b_vec, hipStream_t stream, EP... ep)
 {
     static OncePerDevice attr_ok;   // > 64 KB of dynamic LDS needs the attribute: once per instantiation and device
     if (attr_ok.first()) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dense_nn_bf16<NT, AV, MULTI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kBfLdsBytes));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dense_nn_bf16<NT, AV, MULTI, EPI, EP...>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, kBfLdsBytes));
         attr_ok.done();
     }
-    hipLaunchKernelGGL((k_dense_nn_bf16<NT, AV, MULTI>), dim3((unsigned)gx * ncolb), dim3(kBfThreads), lds, stream, A, B, C, c_bf16, M, N, K, kimg,
-                       pitch, rpw, gx, b_vec);
+    hipLaunchKernelGGL((k_dense_nn_bf16<NT, AV, MULTI, EPI, EP...>), dim3((unsigned)gx * ncolb), dim3(kBfThreads), lds, stream, A, B, C, c_bf16, M, N,
+                       K, kimg, pitch, rpw, gx, b_vec, ep...);
     HIP_TRY(hipGetLastError());
     return GNNAGG_OK;
 }
 
+// the launch geometry of (M, N, K): one rule for the plain product and the one with the attention epilogue, so both write the same C
+struct BfGeometry {
+    int nt, multi, kimg, pitch, ncolb, gx, rpw;
+    size_t lds;
+};
+BfGeometry bf16_geometry(int M, int N, int K)
+{
+    BfGeometry g;
+    const long k8 = ((long)K + 7) / 8 * 8;
+    // the widest column block whose LDS image holds all of K (A is read once per column block); none at NT = 1: K in chunks
+    g.nt = N > 64 ? 4 : N > 32 ? 2 : 1;
+    while (g.nt > 1 && 32 * g.nt * image_pitch(k8) * (long)sizeof(__bf16) > kBfLdsBytes) g.nt >>= 1;
+    g.multi = 32 * g.nt * image_pitch(k8) * (long)sizeof(__bf16) > kBfLdsBytes;   // (only at nt = 1)
+    g.kimg = g.multi ? kBfChunk : (int)k8;
+    g.pitch = (int)image_pitch(g.kimg);
+    g.lds = (size_t)32 * g.nt * g.pitch * sizeof(__bf16);
+    g.ncolb = ceil_div(N, 32 * g.nt);
+    // persistent: what the chip holds at a time, shared by the column blocks -- one workgroup per CU (two wavefronts per SIMD: the ring and
+    // the accumulators take 150 .. 170 registers; capped at 128 for a second workgroup the narrow kernels spill); every wavefront takes
+    // the same number of rows
+    g.gx = std::min(ceil_div(ceil_div(M, 32), kBfWaves), std::max(1, device_cu_count() / g.ncolb));
+    g.rpw = ceil_div(M, (long)g.gx * kBfWaves);
+    return g;
+}
+
+// the lane map of the epilogue for (N, heads) in a column block of nt tiles: false where it has none
+bool att_lane_map(int N, int heads, int nt, int *gsz, int *tph)
+{
+    if (heads == 1) { *gsz = 32; *tph = nt; return true; }
+    const int d = N / heads;
+    if (d != 8 && d != 16 && d != 32 && d != 64) return false;
+    *gsz = std::min(d, 32);
+    *tph = std::max(d / 32, 1);
+    return *tph <= nt;
+}
+
 }  // namespace
 
-int launch_dense_nn_bf16(const void *A_v, const void *B_v, void *C, int c_bf16, int M, int N, int K, void *stream_v)
+// Whether launch_dense_nn_bf16_att takes the attention terms of (M, N, K, heads) in the GEMM's epilogue.  What the kernel can do: all of N
+// in one column block with all of K in its image (N <= 128 and K not beyond the 128-column image: 602 at N = 128), room for a_dst / a_src
+// behind the image, and a head layout the lane map reduces (one head, or D = 8, 16, 32, 64).
+int dense_nn_bf16_att_fuses(int M, int N, int K, int heads)
 {
-    hipStream_t stream = (hipStream_t)stream_v;
+    if (M <= 0 || N <= 0 || K <= 0 || heads < 1 || N % heads != 0) return 0;
+    const long k8 = ((long)K + 7) / 8 * 8;
+    int nt = N > 64 ? 4 : N > 32 ? 2 : 1, gsz, tph;
+    if (N > 32 * nt) return 0;
+    if (32 * nt * image_pitch(k8) * (long)sizeof(__bf16) + 2 * 32 * nt * (long)sizeof(float) > kBfLdsBytes) return 0;
+    return att_lane_map(N, heads, nt, &gsz, &tph);
+}
+
+// epi = NULL: C = A . B.  epi != NULL (dense_nn_bf16_att_fuses holds): the same launch with the attention epilogue behind every tile.
+static int dense_nn_bf16(const void *A_v, const void *B_v, void *C, int c_bf16, int M, int N, int K, const AttEpi *epi, hipStream_t stream)
+{
     if (M <= 0 || N <= 0) return GNNAGG_OK;
     if (K <= 0) {
         if (!c_bf16) return launch_zero_words(C, (size_t)M * N, stream);
@@ -267,40 +425,64 @@ int launch_dense_nn_bf16(const void *A_v, const void *B_v, void *C, int c_bf16, 
         return GNNAGG_OK;
     }
     const __bf16 *A = static_cast<const __bf16 *>(A_v), *B = static_cast<const __bf16 *>(B_v);
-    const long k8 = ((long)K + 7) / 8 * 8;
-    // the widest column block whose LDS image holds all of K (A is read once per column block); none at NT = 1: K in chunks
-    int nt = N > 64 ? 4 : N > 32 ? 2 : 1;
-    while (nt > 1 && 32 * nt * image_pitch(k8) * (long)sizeof(__bf16) > kBfLdsBytes) nt >>= 1;
-    const bool multi = 32 * nt * image_pitch(k8) * (long)sizeof(__bf16) > kBfLdsBytes;   // (only at nt = 1)
-    const int kimg = multi ? kBfChunk : (int)k8, pitch = (int)image_pitch(kimg);
-    const size_t lds = (size_t)32 * nt * pitch * sizeof(__bf16);
-    const int ncolb = ceil_div(N, 32 * nt);
-    // persistent: what the chip holds at a time, shared by the column blocks -- one workgroup per CU (two wavefronts per SIMD: the ring and
-    // the accumulators take 150 .. 170 registers; capped at 128 for a second workgroup the narrow kernels spill); every wavefront takes
-    // the same number of rows
-    const int gx = std::min(ceil_div(ceil_div(M, 32), kBfWaves), std::max(1, device_cu_count() / ncolb));
-    const int rpw = ceil_div(M, (long)gx * kBfWaves);
+    const BfGeometry g = bf16_geometry(M, N, K);
+    const int nt = g.nt, multi = g.multi, kimg = g.kimg, pitch = g.pitch, ncolb = g.ncolb, gx = g.gx, rpw = g.rpw;
+    const size_t lds = g.lds;
     int av = align_class(K, A, (int)sizeof(__bf16), 8);
     if (av == 4) av = 2;            // 4-byte aligned rows: dword-aligned 16-byte loads
     if (av == 2 && K < 8) av = 1;   // (an octet of the row to fall back on)
     const int b_vec = align_class(N, B, (int)sizeof(__bf16), 8) == 8;
 #define BF16_CALL(NT_, AV_, MULTI_) \
     return call_dense_nn_bf16<NT_, AV_, MULTI_>(A, B, C, c_bf16, M, N, K, kimg, pitch, rpw, gx, ncolb, lds, b_vec, stream);
-#define BF16_CALL_NT(NT_, MULTI_)              \
-    switch (av) {                              \
-        case 8: BF16_CALL(NT_, 8, MULTI_)      \
-        case 2: BF16_CALL(NT_, 2, MULTI_)      \
-        default: BF16_CALL(NT_, 1, MULTI_)     \
+#define BF16_CALL_ATT(NT_, AV_, G_)                                                                                                          \
+    if (gsz == G_)                                                                                                                           \
+        return call_dense_nn_bf16<NT_, AV_, false, G_, AttEpi>(A, B, C, c_bf16, M, N, K, kimg, pitch, rpw, gx, ncolb, lds_att, b_vec, stream, e);
+#define BF16_CALL_ATT_G(NT_, AV_, MULTI_) BF16_CALL_ATT(NT_, AV_, 32) BF16_CALL_ATT(NT_, AV_, 16) BF16_CALL_ATT(NT_, AV_, 8) break;
+#define BF16_CALL_NT(CALL_, NT_, MULTI_)   \
+    switch (av) {                          \
+        case 8: CALL_(NT_, 8, MULTI_)      \
+        case 2: CALL_(NT_, 2, MULTI_)      \
+        default: CALL_(NT_, 1, MULTI_)     \
+    }
+    if (epi) {
+        AttEpi e = *epi;
+        int gsz = 0;
+        const size_t lds_att = lds + (size_t)2 * 32 * nt * sizeof(float);
+        if (multi || ncolb != 1 || lds_att > (size_t)kBfLdsBytes || !att_lane_map(N, e.heads, nt, &gsz, &e.tph))
+            return fail(GNNAGG_ERR_STATE, "internal: attention epilogue on a shape it does not cover");
+        switch (nt) {
+            case 4: BF16_CALL_NT(BF16_CALL_ATT_G, 4, false) break;
+            case 2: BF16_CALL_NT(BF16_CALL_ATT_G, 2, false) break;
+            default: BF16_CALL_NT(BF16_CALL_ATT_G, 1, false) break;
+        }
+        return fail(GNNAGG_ERR_STATE, "internal: attention epilogue without a lane map");
     }
     switch (nt) {
-        case 4: BF16_CALL_NT(4, false)
-        case 2: BF16_CALL_NT(2, false)
+        case 4: BF16_CALL_NT(BF16_CALL, 4, false)
+        case 2: BF16_CALL_NT(BF16_CALL, 2, false)
         default:
-            if (multi) BF16_CALL_NT(1, true)
-            BF16_CALL_NT(1, false)
+            if (multi) BF16_CALL_NT(BF16_CALL, 1, true)
+            BF16_CALL_NT(BF16_CALL, 1, false)
     }
 #undef BF16_CALL_NT
+#undef BF16_CALL_ATT_G
+#undef BF16_CALL_ATT
 #undef BF16_CALL
+}
+
+int launch_dense_nn_bf16(const void *A, const void *B, void *C, int c_bf16, int M, int N, int K, void *stream)
+{
+    return dense_nn_bf16(A, B, C, c_bf16, M, N, K, nullptr, (hipStream_t)stream);
+}
+
+// C = A . B as launch_dense_nn_bf16 writes it, and att[M, heads, 2] from C as stored (a_dst, a_src: bf16 [heads, N / heads]) in the same kernel.
+// Only where dense_nn_bf16_att_fuses(M, N, K, heads) holds.
+int launch_dense_nn_bf16_att(const void *A, const void *B, void *C, int c_bf16, const void *a_dst, const void *a_src, float *att, int M, int N, int K,
+                             int heads, void *stream)
+{
+    if (!dense_nn_bf16_att_fuses(M, N, K, heads)) return fail(GNNAGG_ERR_STATE, "internal: attention epilogue on a shape it does not cover");
+    const AttEpi e = {static_cast<const __bf16 *>(a_dst), static_cast<const __bf16 *>(a_src), att, heads, 0};
+    return dense_nn_bf16(A, B, C, c_bf16, M, N, K, &e, (hipStream_t)stream);
 }
 
 }  // namespace gnnagg

@@ -281,6 +281,26 @@ int gnnagg_matmul_nn(const float *d_a, const float *d_b, float *d_c, int m, int 
  * device call.  gnnagg_gcn_run_with_nn stays fp32 only; gnnagg_gcn_run_with_nn_typed is the aggregation with this product behind it. */
 int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_dtype, void *d_c, int c_dtype,
                            int m, int n, int k, void *hip_stream);
+/* The front half of a GAT layer in one call (no reference counterpart; Figure7/our.py:179-188 takes two dense launches for it):
+ *   feat[m, n] = x[m, k] . w[k, n], n = heads . D, and att[m, heads, 2] fp32, the array gnnagg_gat_run reads:
+ *   att[r, h, 0] = sum_c feat[r, h D + c] . a_dst[h, c] (the centre term),  att[r, h, 1] = the same sum with a_src (the source term).
+ *   feat    bit for bit what gnnagg_matmul_nn / gnnagg_matmul_nn_typed writes for the same operands and feat_dtype (the same kernels)
+ *   att     taken from feat AS STORED (a bf16 feat is widened); products and sums in fp32, in an order that is fixed but unspecified:
+ *           |att - att64| <= 1e-5 . sum_c |feat . a| against float64 on the stored feat, exact where every partial sum is an integer below 2^24
+ *   types   (x, w and a_dst / a_src, feat): (F32, F32, F32), (BF16, BF16, F32), (BF16, BF16, BF16); att is always fp32
+ *   sizes   m == 0: nothing is done; k == 0 (or n == 0): +0 in feat and att.  Every operand at any element-aligned address.  Nothing behind an
+ *           operand is read, nothing outside feat[m . n] and att[m . heads . 2] is written; a NaN / inf in row r of x reaches row r only
+ *   *path   (may be NULL; written on the host) 1: the attention terms came out of the GEMM kernel's epilogue -- bf16 operands, n <= 128 with
+ *           all of k in one LDS image (k <= 602 at n = 128), one head or D = 8, 16, 32, 64; 2: a row-dot kernel behind the GEMM read feat back
+ *           (every fp32 call, every other bf16 shape, and the zero fill of k == 0); 0: m == 0.  Measured: profiles/gat_project/
+ *           (the environment variable GNNAGG_GAT_PROJECT_FUSE=0, read at every call, sends every call down path 2: the measurement's switch)
+ *   Asynchronous on hip_stream; no allocation, no synchronisation: a warm call can be captured in a HIP graph.
+ * Everything else -- an unknown dtype code, another type combination, heads < 1, n % heads != 0, a negative size, a NULL operand with
+ * m, n > 0 -- returns GNNAGG_ERR_ARG with a text naming the function and the combination, before any device call. */
+int gnnagg_gat_project(const void *d_x, int x_dtype, const void *d_w, int w_dtype,
+                       const void *d_a_dst, const void *d_a_src,      /* [heads, D], w_dtype */
+                       void *d_feat, int feat_dtype, float *d_att,    /* [M, N], [M, heads, 2] fp32 */
+                       int m, int n, int k, int heads, int *path, void *hip_stream);
 /* Aggregator_GCN::run_with_nn, aggr_gcn.h:491-499 (kernel aggr_gcn_nn :304-359): y = A.x, then
  * transformed[V,feat_out] = y . weight[feat_in,feat_out].  Both outputs are fully overwritten (the
  * reference accumulates into whatever they held). */
