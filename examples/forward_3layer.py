@@ -28,7 +28,7 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1):
+                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -59,7 +59,7 @@ class Model:
         # fused_project (GAT): feat2 = feat . W and the attention terms in one call (gnnagg_gat_project) instead of two dense launches, with
         # a_dst = w_lr[:, 0] (the centre term's vector) and a_src = w_lr[:, 1].  heads > 1 (through gat_project only): H heads of
         # DIMS[k + 1] / H columns, attention vectors [H, D] drawn behind every other seeded tensor
-        if heads != 1 and not fused_project:
+        if heads != 1 and not fused_project and not gatv2:
             raise ValueError("heads > 1 runs through gat_project: pass fused_project=True")
         self.fused_project, self.heads = fused_project, heads
         if fused_project:
@@ -71,6 +71,10 @@ class Model:
                 self.a_dst, self.a_src = [vec(k) for k in range(3)], [vec(k) for k in range(3)]
             self.feat2_gat = [torch.empty(self.num_v, DIMS[k + 1], device=dev, dtype=dtype) for k in range(3)]
             self.att = [torch.empty(self.num_v, heads, 2, device=dev) for k in range(3)]
+        # gatv2 (model "our_GATv2"): a layer is feat2 = feat . W and GATv2 attention over feat2 on both sides (Aggregator_GAT.run_v2, the
+        # shared-weight form); the attention vectors a_k [heads, D] are fp32 and drawn behind every other seeded tensor
+        if gatv2:
+            self.a_v2 = [torch.randn(heads, DIMS[k + 1] // heads, device=dev) / (DIMS[k + 1] // heads) ** 0.5 for k in range(3)]
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -125,6 +129,13 @@ class Model:
                                    att=att.clone(), out=out.clone(), path=gnc.last_project_path()))
         return out
 
+    def gatv2_layer(self, feat, out, k):
+        feat2 = self.dense(feat, self.weights[k])
+        self.at_gat.run_v2(feat2, feat2, self.a_v2[k], out, heads=self.heads)
+        if self.trace is not None:
+            self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, out=out.clone()))
+        return out
+
     def forward(self, model="our_GCN"):
         if self.fused_nn and model == "our_GCN":
             return self.forward_gcn_fused_nn()
@@ -132,6 +143,8 @@ class Model:
         for k in range(3):
             if model == "our_GCN":
                 x = self.gcn_layer(x, self.outs[k], self.weights[k])
+            elif model == "our_GATv2":
+                x = self.gatv2_layer(x, self.outs[k], k)
             elif self.fused_project:
                 x = self.gat_layer_project(x, self.outs[k], k)
             else:
@@ -141,7 +154,8 @@ class Model:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT"])
+    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT", "our_GATv2"],
+                    help="our_GATv2: GATv2 attention (Aggregator_GAT.run_v2) on the projected features; honours --dtype, --heads, --hip-graph")
     ap.add_argument("--dataset", default="arxiv")
     ap.add_argument("--datadir", default=None)
     ap.add_argument("--reorder", default="")
@@ -182,7 +196,8 @@ def main():
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
-              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or args.heads != 1, heads=args.heads)
+              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or (args.heads != 1 and args.model != "our_GATv2"), heads=args.heads,
+              gatv2=args.model == "our_GATv2")
     num_v, num_e = m.num_v, m.num_e
 
     def forward():

@@ -373,6 +373,38 @@ class Aggregator_GAT(Aggregator):
                                              ctypes.c_float(slope), _mode(scheduled), _dev_ptr(newval, torch.float32, "newval")))
         return 0.0
 
+    # k_gatv2 as built (csrc/common.h: kGatv2Batch, the id windows of the 8- to 64-lane groups, kGatv2LongEdges, kGatv2SegEdges): the row
+    # lengths at which the walk of a row changes -- edges per batch, ids per window, the longest row one lane group walks, the edges of a
+    # segment (above it: several workgroups and the ordered merge)
+    GATV2_THRESHOLDS = (4, 8, 16, 32, 64, 128, 512)
+    GATV2_MAX_FEAT = 1024
+
+    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2):
+        """gnnagg_gatv2_run (extension): GATv2 attention, e_ij = a[h] . leaky(xd[i] + xs[j]) per head, max-shifted edge softmax over each row's
+        edges and the weighted sum of the xs rows, in one call.  xs [n_src, F], xd [>= V, F]: both float32 or both bfloat16 (xd may be xs);
+        a: float32, heads * D elements ([heads, D]); vout [>= V, F] float32 or bfloat16 (one rounding of the fp32 result).  Rows without edges
+        are +0.  Everything is checked here before the library is reached."""
+        xt, yt = _feat_dtype(xs, "xs"), _feat_dtype(vout, "vout")
+        if _feat_dtype(xd, "xd") != xt:
+            raise TypeError("xd (%s) must have xs's dtype %s" % (xd.dtype, xs.dtype))
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32:
+            raise TypeError("a must be a torch.float32 tensor")
+        heads = int(heads)
+        if xs.dim() != 2:
+            raise ValueError("xs must be [n_src, F], got %s" % (tuple(xs.shape),))
+        feat = int(xs.shape[1])
+        if heads < 1 or feat < 1 or feat % heads != 0:
+            raise ValueError("run_v2: heads = %d does not divide F = %d" % (heads, feat))
+        if a.numel() != feat:
+            raise ValueError("run_v2: a %s does not hold [heads = %d, D = %d]" % (tuple(a.shape), heads, feat // heads))
+        if xd.numel() < self.num_v * feat:
+            raise ValueError("xd must hold at least V*F elements")
+        if vout.numel() < self.num_v * feat:
+            raise ValueError("vout must hold at least V*F elements")
+        self._use_current_stream()
+        check(lib().gnnagg_gatv2_run(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt, _dev_ptr(a, torch.float32, "a"),
+                                     _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads, ctypes.c_float(slope)))
+
     def run_part(self, vin, vatt, vout, den_io, part, heads=1, slope=0.2):
         """gnnagg_gat_run_part: the fused aggregation in two passes over disjoint edge sets of the same rows.  part=1: vout
         receives the numerators, den_io [V, heads] the denominators; part=2: both are added to and the rows divided."""
@@ -592,6 +624,11 @@ def gat_init(ptrs, idxs):
 def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
     """Figure7/kernel.cpp's gat_run; stable=True (extension): the overflow-safe edge softmax (Aggregator_GAT.run_with_feat)."""
     at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]), stable=stable)
+
+
+def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2):
+    """Aggregator_GAT.run_v2 as a flat function (extension: the reference has no GATv2)."""
+    at.run_v2(xs, xd, a, out, heads=heads, slope=slope)
 
 
 def gat_schedule(at, neighbor_num):

@@ -1,0 +1,391 @@
+// agg_gatv2.hip -- GATv2 ("dynamic attention"): edge score, online edge softmax and weighted aggregation in one pass over the gathered rows.
+//
+//     e_j = sum_c a[h, c] * leaky(xd[r, hD + c] + xs[j, hD + c]),   y[r] = sum_j softmax_j(e_j) * xs[j]          (gnnagg_gatv2_run)
+//
+// The score needs the gathered source row itself (the non-linearity sits inside the dot product), so the softmax runs ONLINE: every lane
+// keeps a running (m, den, acc) per column fragment and one gather feeds both the score and the sum.
+//
+// Geometry (gatv2_geometry: a function of (F, heads, element size) only, never of a pointer):
+//   * segmented: D * elemsize is a multiple of 16 bytes and a head spans a power-of-two number (<= 64) of 16-byte lanes.  A lane group of
+//     8 .. 64 lanes covers the row, NF = 1, 2 or 4 fragments per lane when F / VEC > 64; the per-head reduction is an xor butterfly over the
+//     head's lanes (every lane of the head ends with the same bits).
+//   * general: any other (heads, D).  One-element lanes, 64-lane groups, NF = ceil(F / 64) fragments per lane; one masked 64-lane
+//     reduction per head.  Slower, and covers heads narrower than a lane and D that no lane width divides.
+// Where X is not 16-byte aligned the segmented geometry stays and a lane loads its elements one by one: same arithmetic, same bits.
+//
+// Order of a row (DESIGN.md "GATv2"): edges in CSR order in batches of kGatv2Batch.  Per batch and fragment: the scores; if the batch
+// maximum exceeds m, ONE rescale of (den, acc) by expf(m - new m) (skipped as 0 while m = -inf: no inf - inf); then, edge by edge,
+// w = expf(e - m), den += w, acc = fma(x, w, acc).  Rows above kGatv2LongEdges edges are cut into segments of kGatv2SegEdges edges, one
+// workgroup each: its lane groups walk contiguous chunks, and group 0 folds the (m, den, acc) triples through LDS in ascending chunk order
+// (M = max m; den = sum den_g * expf(m_g - M)).  A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds
+// them the same way, ascending.  No atomics; the same bits on every call.
+#include "kernel_util.cuh"
+
+namespace gnnagg {
+
+struct Gatv2Args {
+    const int *ptr, *idx;
+    const int4 *seg;    // {beg, end, row, slot}: slot < 0 = the row's only segment (stored directly)
+    const int4 *mrow;   // {row, first slot, end slot, -} per row of several segments
+    const void *xs, *xd;
+    const float *a;
+    void *y;
+    float *scratch;     // [n_slots][m: NF * GROUP | den: NF * GROUP | acc: NF * GROUP * VEC]
+    int V, n_seg, n_mrows, nblocks_short, feat, heads, dhead, lph, y_bf16, yvec, x_aligned, slot_stride;
+    float slope;
+};
+
+// VEC elements of a row at p: one 16-byte (or narrower) load, or element by element where the row is not aligned for it
+template <int VEC, typename TX>
+__device__ __forceinline__ Pack<VEC, TX> gatv2_load(const TX *p, int aligned)
+{
+    if constexpr (VEC == 1) {
+        return load_pack<1, TX>(p);
+    } else {
+        if (aligned) return load_pack<VEC, TX>(p);
+        Pack<VEC, TX> r;
+        if constexpr (std::is_same<TX, __bf16>::value) {
+            const unsigned short *q = reinterpret_cast<const unsigned short *>(p);
+#pragma unroll
+            for (int k = 0; k < VEC / 2; ++k) r.w[k] = (unsigned)q[2 * k] | ((unsigned)q[2 * k + 1] << 16);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r.v[k] = p[k];
+        }
+        return r;
+    }
+}
+
+// The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+__device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
+                                           const float (&av)[NF][VEC], const int (&hf)[NF], float (&m)[NF], float (&den)[NF],
+                                           float (&acc)[NF][VEC])
+{
+    constexpr int U = kGatv2Batch;
+    const int F = a.feat;
+    const TX *__restrict__ xs = static_cast<const TX *>(a.xs) + lane * VEC;
+    const int *__restrict__ idx = a.idx;
+    int my_s = 0;
+    if (beg + lane < end) my_s = idx[beg + lane];
+    for (int cb = beg; cb < end; cb += GROUP) {
+        int nx_s = 0;
+        if (cb + GROUP + lane < end) nx_s = idx[cb + GROUP + lane];
+        const int n = end - cb < GROUP ? end - cb : GROUP;
+        for (int j = 0; j < n; j += U) {
+            int s[U];
+            Pack<VEC, TX> xv[U][NF];
+            float e[U][NF];
+#pragma unroll
+            for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (j + u < n) {
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+                        if ((f * GROUP + lane) * VEC < F) xv[u][f] = gatv2_load<VEC, TX>(xs + (size_t)s[u] * F + f * GROUP * VEC, a.x_aligned);
+                }
+            // this lane's part of every score
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    float p = 0.0f;
+                    if (j + u < n && (f * GROUP + lane) * VEC < F) {
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) {
+                            const float z = xdv[f][k] + xv[u][f].at(k);
+                            const float zs = z * a.slope;
+                            p = __builtin_fmaf(av[f][k], z > zs ? z : zs, p);
+                        }
+                    }
+                    e[u][f] = p;
+                }
+            // ... summed over the lanes (and fragments) of its head
+            if constexpr (SEGRED) {
+                const int lph = a.lph;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) {
+                        float v = e[u][f];
+                        if (lph > 1) v += __shfl_xor(v, 1, GROUP);
+                        if (lph > 2) v += __shfl_xor(v, 2, GROUP);
+                        if (lph > 4) v += __shfl_xor(v, 4, GROUP);
+                        if constexpr (GROUP > 8) { if (lph > 8) v += __shfl_xor(v, 8, GROUP); }
+                        if constexpr (GROUP > 16) { if (lph > 16) v += __shfl_xor(v, 16, GROUP); }
+                        if constexpr (GROUP > 32) { if (lph > 32) v += __shfl_xor(v, 32, GROUP); }
+                        e[u][f] = v;
+                    }
+            } else {
+                for (int h = 0; h < a.heads; ++h) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        float t = 0.0f;
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) t += hf[f] == h ? e[u][f] : 0.0f;
+                        t = group_sum<GROUP>(t);
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            if (hf[f] == h) e[u][f] = t;   // (a fragment belongs to one head: nothing read later was overwritten)
+                    }
+                }
+            }
+            // online softmax: at most one rescale per batch, then the batch's edges in CSR order
+#pragma unroll
+            for (int f = 0; f < NF; ++f) {
+                if ((f * GROUP + lane) * VEC >= F) continue;
+                float bm = e[0][f];
+#pragma unroll
+                for (int u = 1; u < U; ++u)
+                    if (j + u < n) bm = fmaxf(bm, e[u][f]);
+                if (bm > m[f]) {
+                    const float sc = m[f] == -INFINITY ? 0.0f : expf(m[f] - bm);   // first batch: nothing to rescale, and no -inf - -inf
+                    den[f] *= sc;
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[f][k] *= sc;
+                    m[f] = bm;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < n) {
+                        const float w = expf(e[u][f] - m[f]);
+                        den[f] += w;
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(xv[u][f].at(k), w, acc[f][k]);
+                    }
+            }
+        }
+        my_s = nx_s;
+    }
+}
+
+// acc / den of a finished row piece, stored in Y's type
+template <int VEC>
+__device__ __forceinline__ void gatv2_store(const Gatv2Args &a, size_t off, const float (&acc)[VEC], float den, bool has_edges)
+{
+    float o[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o[k] = has_edges ? acc[k] / den : 0.0f;
+    store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0u, off, o);
+}
+
+// Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
+{
+    constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
+    __shared__ float s_m[BLOCK * NF], s_den[BLOCK * NF], s_acc[BLOCK * NF * VEC];
+    const int F = a.feat;
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int grp = (int)threadIdx.x / GROUP;
+    const bool seg_block = (int)blockIdx.x < a.n_seg;   // workgroup-uniform
+    int beg, end, row, slot = -1;
+    if (seg_block) {
+        const int4 d = a.seg[blockIdx.x];
+        row = d.z; slot = d.w;
+        int chunk = (d.y - d.x + GPB - 1) / GPB;
+        chunk = (chunk + kGatv2Batch - 1) / kGatv2Batch * kGatv2Batch;
+        beg = d.x + grp * chunk < d.y ? d.x + grp * chunk : d.y;
+        end = beg + chunk < d.y ? beg + chunk : d.y;
+    } else {
+        int b = (int)blockIdx.x - a.n_seg;
+        if (a.nblocks_short >= 64) b = xcd_remap(b, a.nblocks_short);
+        row = b * GPB + grp;
+        if (row >= a.V) return;
+        beg = a.ptr[row]; end = a.ptr[row + 1];
+        if (end - beg > kGatv2LongEdges) return;   // a long row: the segment workgroups' work
+    }
+    float xdv[NF][VEC], av[NF][VEC], m[NF], den[NF], acc[NF][VEC];
+    int hf[NF];
+    const TX *__restrict__ xd = static_cast<const TX *>(a.xd) + (size_t)row * F + lane * VEC;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int col = (f * GROUP + lane) * VEC;
+        const bool ok = col < F;
+        hf[f] = ok ? col / a.dhead : -1;
+        m[f] = -INFINITY;
+        den[f] = 0.0f;
+        Pack<VEC, TX> xr;
+        if (ok && beg < end) xr = gatv2_load<VEC, TX>(xd + f * GROUP * VEC, a.x_aligned);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            acc[f][k] = 0.0f;
+            xdv[f][k] = ok && beg < end ? xr.at(k) : 0.0f;
+            av[f][k] = ok ? a.a[col + k] : 0.0f;   // a is [heads, D]: element (h, c) sits at column h D + c
+        }
+    }
+    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED>(a, beg, end, lane, xdv, av, hf, m, den, acc);
+    if (!seg_block) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const int col = (f * GROUP + lane) * VEC;
+            if (col < F) gatv2_store<VEC>(a, (size_t)row * F + col, acc[f], den[f], beg < end);
+        }
+        return;
+    }
+    // fold of the lane groups' triples, ascending chunk order, by group 0
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int i = (grp * NF + f) * GROUP + lane;
+        s_m[i] = m[f];
+        s_den[i] = den[f];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) s_acc[i * VEC + k] = acc[f][k];
+    }
+    __syncthreads();
+    if (grp != 0) return;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int col = (f * GROUP + lane) * VEC;
+        if (col >= F) continue;
+        float M = -INFINITY;
+        for (int g = 0; g < GPB; ++g) M = fmaxf(M, s_m[(g * NF + f) * GROUP + lane]);
+        float d = 0.0f, o[VEC] = {};
+        for (int g = 0; g < GPB; ++g) {
+            const int i = (g * NF + f) * GROUP + lane;
+            const float mg = s_m[i];
+            const float sc = mg == -INFINITY ? 0.0f : expf(mg - M);   // a chunk without edges
+            d = __builtin_fmaf(s_den[i], sc, d);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(s_acc[i * VEC + k], sc, o[k]);
+        }
+        if (slot < 0) {
+            gatv2_store<VEC>(a, (size_t)row * F + col, o, d, true);
+        } else {
+            float *sl = a.scratch + (size_t)slot * a.slot_stride;
+            const int i = f * GROUP + lane;
+            sl[i] = M;
+            sl[NF * GROUP + i] = d;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) sl[2 * NF * GROUP + i * VEC + k] = o[k];
+        }
+    }
+}
+
+// Rows of several segments: one lane group folds the row's triples in ascending slot order.
+template <int VEC, int GROUP, int NF>
+__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2_merge(const Gatv2Args a)
+{
+    constexpr int GPB = block_of<GROUP>() / GROUP;
+    const int F = a.feat;
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int mi = blockIdx.x * GPB + (int)threadIdx.x / GROUP;
+    if (mi >= a.n_mrows) return;
+    const int4 d = a.mrow[mi];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int col = (f * GROUP + lane) * VEC;
+        if (col >= F) continue;
+        const int i = f * GROUP + lane;
+        float M = -INFINITY;
+        for (int s = d.y; s < d.z; ++s) M = fmaxf(M, a.scratch[(size_t)s * a.slot_stride + i]);
+        float dn = 0.0f, o[VEC] = {};
+        for (int s = d.y; s < d.z; ++s) {
+            const float *sl = a.scratch + (size_t)s * a.slot_stride;
+            const float sc = expf(sl[i] - M);   // (every segment has edges: its m is a score)
+            dn = __builtin_fmaf(sl[NF * GROUP + i], sc, dn);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(sl[2 * NF * GROUP + i * VEC + k], sc, o[k]);
+        }
+        gatv2_store<VEC>(a, (size_t)d.x * F + col, o, dn, true);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ geometry and launch
+struct Gatv2Geom {
+    int vec, group, nf, lph;
+    bool segred;
+};
+
+static bool gatv2_geometry(int F, int heads, int esize, Gatv2Geom &g)
+{
+    if (F < 1 || heads < 1 || F % heads != 0 || F > kGatv2MaxFeat) return false;
+    const int D = F / heads, vec = 16 / esize;
+    if (D % vec == 0) {
+        const int lph = D / vec;
+        if ((lph & (lph - 1)) == 0 && lph <= 64) {
+            const int lanes = F / vec;
+            int group = 8;
+            while (group < 64 && group < lanes) group <<= 1;
+            const int nf = (lanes + group - 1) / group;
+            g = {vec, group, nf <= 1 ? 1 : nf <= 2 ? 2 : 4, lph, true};   // (F <= 1024: at most 256 16-byte lanes)
+            return true;
+        }
+    }
+    const int nf = (F + 63) / 64;
+    g = {1, 64, nf <= 1 ? 1 : nf <= 2 ? 2 : nf <= 4 ? 4 : nf <= 10 ? 10 : 16, 0, false};
+    return true;
+}
+
+size_t gatv2_slot_floats(int feat, int heads, int x_dtype)
+{
+    Gatv2Geom g;
+    if (!gatv2_geometry(feat, heads, x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, g)) return 0;
+    return (size_t)g.nf * g.group * (g.vec + 2);
+}
+
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+static int launch_gatv2_inst(const Gatv2Args &a, hipStream_t stream)
+{
+    constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
+    const int grid = a.n_seg + a.nblocks_short;
+    if (grid > 0) {
+        hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (a.n_mrows > 0) {
+        hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return GNNAGG_OK;
+}
+
+template <int VEC, typename TX>
+static int launch_gatv2_typed(Gatv2Args &a, const Gatv2Geom &g, hipStream_t stream)
+{
+    a.nblocks_short = ceil_div(a.V, block_for(g.group) / g.group);
+    if (g.segred) {
+        switch (g.group * 10 + g.nf) {
+            case 81:  return launch_gatv2_inst<VEC, 8, 1, TX, true>(a, stream);
+            case 161: return launch_gatv2_inst<VEC, 16, 1, TX, true>(a, stream);
+            case 321: return launch_gatv2_inst<VEC, 32, 1, TX, true>(a, stream);
+            case 641: return launch_gatv2_inst<VEC, 64, 1, TX, true>(a, stream);
+            case 642: return launch_gatv2_inst<VEC, 64, 2, TX, true>(a, stream);
+            case 644:
+                if constexpr (VEC == 4) return launch_gatv2_inst<VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
+                break;
+        }
+    } else {
+        switch (g.nf) {
+            case 1:  return launch_gatv2_inst<1, 64, 1, TX, false>(a, stream);
+            case 2:  return launch_gatv2_inst<1, 64, 2, TX, false>(a, stream);
+            case 4:  return launch_gatv2_inst<1, 64, 4, TX, false>(a, stream);
+            case 10: return launch_gatv2_inst<1, 64, 10, TX, false>(a, stream);
+            case 16: return launch_gatv2_inst<1, 64, 16, TX, false>(a, stream);
+        }
+    }
+    return fail(GNNAGG_ERR_STATE, "internal: GATv2 lane geometry without an instantiation");
+}
+
+int launch_gatv2(const Gatv2Launch &L, void *stream_v)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
+    Gatv2Geom g;
+    if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: GATv2 launch outside the kernel's shapes");
+    if (L.V <= 0) return GNNAGG_OK;
+    Gatv2Args a;
+    a.ptr = L.ptr; a.idx = L.idx; a.seg = reinterpret_cast<const int4 *>(L.seg); a.mrow = reinterpret_cast<const int4 *>(L.mrow);
+    a.xs = L.xs; a.xd = L.xd; a.a = L.a; a.y = L.y; a.scratch = L.scratch;
+    a.V = L.V; a.n_seg = L.n_seg; a.n_mrows = L.n_mrows; a.nblocks_short = 0; a.feat = L.feat; a.heads = L.heads; a.dhead = L.feat / L.heads;
+    a.lph = g.lph; a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
+    a.yvec = align_class(L.feat, L.y, ysize, g.vec);
+    a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0) ? 1 : 0;   // (segmented: F * esize is a multiple of 16)
+    a.slot_stride = g.nf * g.group * (g.vec + 2);
+    a.slope = L.slope;
+    if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_gatv2_typed<8, __bf16>(a, g, stream);
+    return launch_gatv2_typed<4, float>(a, g, stream);
+}
+
+}  // namespace gnnagg

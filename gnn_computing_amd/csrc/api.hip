@@ -2010,6 +2010,63 @@ int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const 
     return gat_run(c, r);
 }
 
+// The segments of the long rows (common.h: Gatv2Launch), from the host mirror of ptr: read behind the handle's stream like every plan.
+static int gatv2_build_plan(Ctx *c)
+{
+    if (int rc = fetch_host_ptr(c)) return rc;
+    std::vector<int> seg, mrow;
+    int n_slots = 0;
+    for (int r = 0; r < c->V; ++r) {
+        const int beg = c->h_ptr[r], end = c->h_ptr[r + 1];
+        if (end - beg <= kGatv2LongEdges) continue;
+        const bool multi = end - beg > kGatv2SegEdges;
+        const int first = n_slots;
+        for (int b = beg; b < end; b += kGatv2SegEdges) {
+            const int e = std::min(b + kGatv2SegEdges, end);
+            seg.insert(seg.end(), {b, e, r, multi ? n_slots++ : -1});
+        }
+        if (multi) mrow.insert(mrow.end(), {r, first, n_slots, 0});
+    }
+    Ctx::Gatv2Plan &p = c->gatv2;
+    if (int rc = p.seg.upload(seg)) return rc;
+    if (int rc = p.mrow.upload(mrow)) return rc;
+    p.n_seg = (int)seg.size() / 4; p.n_mrows = (int)mrow.size() / 4; p.n_slots = n_slots;
+    p.valid = true;
+    return GNNAGG_OK;
+}
+
+int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
+                     int heads, float slope)
+{
+    GET_CTX(h);
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: handle is not a GAT aggregator");
+    if (!d_xs || !d_xd || !d_a || !d_y)
+        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gatv2_run: null pointer (") + (!d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : "d_y") + ")");
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (feat < 1 || heads < 1 || feat % heads != 0)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
+                                        ": needs feat >= 1, heads >= 1 and feat % heads == 0");
+    if (!(slope >= 0.0f && slope <= 1.0f))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: slope = " + std::to_string(slope) + " is outside [0, 1] (the leaky form max(z, z * slope))");
+    if (feat > kGatv2MaxFeat)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: feat = " + std::to_string(feat) + " is above the kernel's limit of " +
+                                        std::to_string(kGatv2MaxFeat) + " columns");
+    if (c->V == 0) return GNNAGG_OK;
+    Ctx::Gatv2Plan &p = c->gatv2;
+    if (!p.valid)
+        if (int rc = gatv2_build_plan(c)) return rc;
+    if (p.n_slots > 0)
+        if (int rc = p.scratch.reserve((size_t)p.n_slots * gatv2_slot_floats(feat, heads, x_dtype))) return rc;
+    Gatv2Launch L;
+    L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
+    L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.y = d_y; L.scratch = p.scratch.p; L.x_dtype = x_dtype; L.y_dtype = y_dtype;
+    L.V = c->V; L.feat = feat; L.heads = heads; L.slope = slope;
+    return launch_gatv2(L, c->stream);
+}
+
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,
                         float *d_den_io)
 {

@@ -144,6 +144,14 @@ struct Ctx {
     DevBuf<float> den;       // [V,heads] row sums of run_att
     DevBuf<float> partial, partial_den;
     DevBuf<float> shift;   // gnnagg_gat_run_shifted without a caller's array: V * heads row maxima of the leaky logits
+    // gnnagg_gatv2_run: the segments of the rows above kGatv2LongEdges edges, built from the CSR on the first call; the scratch holds one
+    // (m, den, acc) triple per segment of a multi-segment row and grows only when a call's (feat, heads, dtype) needs more
+    struct Gatv2Plan {
+        bool valid = false;
+        int n_seg = 0, n_mrows = 0, n_slots = 0;
+        DevBuf<int> seg, mrow;
+        DevBuf<float> scratch;
+    } gatv2;
     DevBuf<float> xt;      // 2-D blocked mode: column-tiled image of X, rebuilt by every run (k_tile_x)
     DevBuf<float> att_t;   // 2-D blocked GAT: compact source / centre attention terms per head group, rebuilt by every run (k_tile_att)
 #ifdef GNNAGG_EXTRAS   // older forms kept for A/B parity tests (second tier): run-time switches there, constants in the default build

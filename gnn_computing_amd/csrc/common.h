@@ -263,6 +263,25 @@ int launch_gat_plan(const GatPlanLaunch &a, void *stream);
 // up to kShiftHubEdges edges run on kShiftGroup-lane groups, longer ones on their whole workgroup; heads in blocks of kShiftHeads.
 constexpr int kShiftGroup = 8, kShiftHeads = 4, kShiftHubEdges = 1024;
 int launch_gat_row_shift(const int *ptr, const int *idx, const float *att, float *shift, int V, int heads, float slope, void *stream);
+// GATv2 (agg_gatv2.hip, gnnagg_gatv2_run): score, online softmax and aggregation from one gather.  Edges go in batches of kGatv2Batch;
+// a row above kGatv2LongEdges edges is cut into segments of kGatv2SegEdges edges, one workgroup each (seg: int4 {beg, end, row, slot},
+// slot < 0 = the row's only segment); rows of several segments leave one (m, den, acc) triple per segment in scratch, folded in ascending
+// order (mrow: int4 {row, first slot, end slot, -}).  feat <= kGatv2MaxFeat.
+constexpr int kGatv2Batch = 4, kGatv2LongEdges = 128, kGatv2SegEdges = 512, kGatv2MaxFeat = 1024;
+struct Gatv2Launch {
+    const int *ptr = nullptr, *idx = nullptr;
+    const void *seg = nullptr, *mrow = nullptr;
+    int n_seg = 0, n_mrows = 0;
+    const void *xs = nullptr, *xd = nullptr;   // elements of x_dtype
+    const float *a = nullptr;                  // [heads, feat / heads]
+    void *y = nullptr;                         // elements of y_dtype
+    float *scratch = nullptr;                  // n_slots * gatv2_slot_floats(feat, heads, x_dtype) floats
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+    int V = 0, feat = 0, heads = 1;
+    float slope = 0.2f;
+};
+size_t gatv2_slot_floats(int feat, int heads, int x_dtype);   // 0: a shape the kernel does not cover
+int launch_gatv2(const Gatv2Launch &a, void *stream);
 // Backward of the single-head fused GAT aggregation (k_rowdot + k_gat_bwd_edges); wl = chunked edge work items.
 struct GatBwdLaunch {
     WorkList wl;

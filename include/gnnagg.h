@@ -420,6 +420,28 @@ int gnnagg_gat_row_shift(gnnagg_handle h, const float *d_att, int heads, float s
  * (tests/test_gpu_gat_shift.py, tests/test_gat_shift_host.py) */
 int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const float *d_att, const float *d_shift,
                            void *d_y, int y_dtype, int feat, int heads, float slope, int mode);
+/* GATv2, the "dynamic attention" form (no reference counterpart; what DGL's GATv2Conv and PyG's GATv2Conv aggregate with): score,
+ * edge softmax and aggregation in one call, one gather per edge.  For row r, head h (D = feat / heads) and every edge j of the row, in
+ * CSR order:
+ *     z_jc = xd[r, hD + c] + xs[j, hD + c]         l_jc = z_jc > z_jc * slope ? z_jc : z_jc * slope
+ *     e_j  = sum_c a[h, c] * l_jc                  alpha_j = exp(e_j - max_k e_k) / sum_k exp(e_k - max_k e_k)
+ *     y[r, hD + c] = sum_j alpha_j * xs[j, hD + c]
+ *   operands     d_xs [n_src, feat] and d_xd [num_v, feat] hold x_dtype elements (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16, the same type for both;
+ *                bf16 is widened exactly); d_a [heads, D] is fp32; d_y [num_v, feat] holds y_dtype elements.  d_xd == d_xs is the shared-weight
+ *                form.  d_y aliases neither input.  Column ids may exceed num_v (d_xs has that many rows).  x / y at any element offset.
+ *   arithmetic   fp32 throughout; the softmax is always max-shifted (online, one rescale per batch of 4 edges at most), so finite inputs with
+ *                finite scores give finite results whatever the scores' magnitude.  A bf16 y is ONE round-to-nearest-even of the fp32 result.
+ *                A row without edges is +0.  No self loops are added; a duplicate edge counts twice.
+ *   order        a row's result depends on its edges in CSR order and on the lane geometry of (feat, heads, x_dtype) only -- never on a
+ *                pointer's alignment or on other rows; no atomics; the same bits on every call (DESIGN.md "GATv2").
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, d_y untouched: a handle that is not a GAT aggregator, a null pointer, an unknown
+ *                dtype code, feat < 1, feat % heads != 0, slope outside [0, 1], feat > 1024 (the kernel's limit).
+ *   streams      on the handle's stream.  The first call builds the list of long rows (one read of ptr, ordered behind the stream) and a call
+ *                allocates only while the handle's scratch is smaller than its (feat, heads, x_dtype) needs; any later call of such a shape
+ *                allocates and synchronises nothing and can be captured in a HIP graph.
+ * (tests/test_gpu_gatv2.py, tests/test_gatv2_host.py) */
+int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
+                     int heads, float slope);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns.
