@@ -1405,6 +1405,10 @@ int edge_launch(Ctx *c, EdgeItemLaunch &L, int heads)
 int do_schedule(Ctx *c, int kind, const int *param, int total_v)
 {
     if (!param) return fail(GNNAGG_ERR_ARG, "null schedule parameter array");
+    // a refused call leaves the handle as it was: the parameters are checked before the schedule in force (sched[0], plan_sched) is touched
+    if (kind == GNNAGG_SCHED_NEIGHBOR_GROUPING && param[0] <= 0) return fail(GNNAGG_ERR_ARG, "neighbor group size must be >= 1");
+    if ((kind == GNNAGG_SCHED_LOCALITY || kind == GNNAGG_SCHED_LOCALITY_NEIGHBOR_GROUPING) && param[0] <= 0)
+        return fail(GNNAGG_ERR_ARG, "locality partition count must be >= 1");
     switch (kind) {
         case GNNAGG_SCHED_NEIGHBOR_GROUPING: {
             int rc = build_grouping(c, c->sched[0], param[0], kind);
@@ -1504,7 +1508,15 @@ int gnnagg_destroy(gnnagg_handle h)
         if (!g_live.count(c)) return fail(GNNAGG_ERR_ARG, "invalid or destroyed handle");
         g_live.erase(c);
     }
-    (void)hipStreamSynchronize(c->stream);
+    // A handle may die while a call on ANOTHER handle is being captured into a HIP graph (a garbage collector picks the moment).  The
+    // synchronisations and frees below are not capturable, and under the global capture mode they would invalidate that capture without
+    // an error anybody sees: this thread makes them in the relaxed mode, which leaves a capture they are no part of alone
+    // (a capture on a non-blocking stream, as torch's are: the wait for the null stream below is a wait for every BLOCKING stream; gnnagg.h).
+    hipStreamCaptureMode capture_mode = hipStreamCaptureModeRelaxed;
+    const bool exchanged = hipThreadExchangeStreamCaptureMode(&capture_mode) == hipSuccess;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (c->stream && hipStreamIsCapturing(c->stream, &capturing) != hipSuccess) capturing = hipStreamCaptureStatusNone;
+    if (capturing == hipStreamCaptureStatusNone) (void)hipStreamSynchronize(c->stream);   // (captured work is not running: nothing to wait for)
 #ifdef GNNAGG_EXTRAS
     if (c->tr.agg) (void)gnnagg_destroy(c->tr.agg);
 #endif
@@ -1515,6 +1527,7 @@ int gnnagg_destroy(gnnagg_handle h)
         (void)hipEventDestroy(c->ev_join);
     }
     delete c;
+    if (exchanged) (void)hipThreadExchangeStreamCaptureMode(&capture_mode);
     return GNNAGG_OK;
 }
 
@@ -1795,13 +1808,22 @@ int gnnagg_gat_project(const void *d_x, int x_dtype, const void *d_w, int w_dtyp
     return launch_gat_rowdot(d_feat, feat_bf, d_a_dst, d_a_src, bf, d_att, m, n, heads, hip_stream);
 }
 
+// gnnagg_last_nn_path describes the last run_with_nn[_typed] call that RAN: a refused one leaves it as it was
+static int nn_run(Ctx *c, const GcnRequest &r)
+{
+    const int before = c->last_nn_path;
+    const int rc = gcn_run(c, r);
+    if (rc) c->last_nn_path = before;
+    return rc;
+}
+
 int gnnagg_gcn_run_with_nn(gnnagg_handle h, const float *d_x, float *d_y, const float *d_weight, float *d_transformed,
                            int feat_in, int feat_out, int mode)
 {
     GET_CTX(h);
     if (!d_weight || !d_transformed || feat_out <= 0) return fail(GNNAGG_ERR_ARG, "bad run_with_nn arguments");
     const NnRequest nn = {d_weight, d_transformed, feat_out};
-    return gcn_run(c, GcnRequest{d_x, d_y, feat_in, mode, GNNAGG_REDUCE_SUM, 0, &nn});
+    return nn_run(c, GcnRequest{d_x, d_y, feat_in, mode, GNNAGG_REDUCE_SUM, 0, &nn});
 }
 
 int gnnagg_gcn_run_with_nn_typed(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, const void *d_weight, int w_dtype,
@@ -1826,12 +1848,12 @@ int gnnagg_gcn_run_with_nn_typed(gnnagg_handle h, const void *d_x, int x_dtype, 
     NnRequest nn = {static_cast<const float *>(d_weight), static_cast<float *>(d_transformed), feat_out};
     const bool all_f32 = x_dtype == GNNAGG_DTYPE_F32 && y_dtype == GNNAGG_DTYPE_F32;
     if (all_f32 && !(flags & GNNAGG_FLAG_RELU))   // today's path, every order it covers
-        return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn});
+        return nn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn});
     if (c->kind == Ctx::GCN && mode == GNNAGG_MODE_ROWS && !c->fast_rows)
         return fail(GNNAGG_ERR_ARG, "gnnagg_gcn_run_with_nn_typed (" + combo + "): GNNAGG_MODE_ROWS with the canonical CSR-order chains (\"fast_rows\" = 0) "
                                     "is fp32 without ReLU only -- use GNNAGG_MODE_BALANCED, or set \"fast_rows\" = 1");
     nn.typed = 1; nn.w_dtype = w_dtype; nn.t_dtype = t_dtype;
-    return gcn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn, 0, x_dtype, y_dtype});
+    return nn_run(c, GcnRequest{static_cast<const float *>(d_x), static_cast<float *>(d_y), feat, mode, reduce, flags, &nn, 0, x_dtype, y_dtype});
 }
 
 int gnnagg_last_nn_path(gnnagg_handle h, int *path)

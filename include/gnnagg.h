@@ -91,7 +91,12 @@ int gnnagg_gcn_create(const int *d_ptr, const int *d_idx, const float *d_val, in
                       gnnagg_handle *out);
 /* Aggregator_GAT ctor, aggr_gat.h:302-313 */
 int gnnagg_gat_create(const int *d_ptr, const int *d_idx, int num_v, int num_e, gnnagg_handle *out);
-/* Frees what the handle allocated (schedules, scratch).  Never frees caller pointers. */
+/* Frees what the handle allocated (schedules, scratch).  Never frees caller pointers.  Waits for the handle's stream first.  May be called
+ * while a call on ANOTHER handle is being captured into a HIP graph (a garbage collector frees handles where it finds them): the frees
+ * and waits are made in the relaxed capture mode and leave that capture valid -- provided that the capturing stream is a NON-BLOCKING one (hipStreamNonBlocking,
+ * as torch's are) or the dying handle's stream is not the null stream: the wait for the legacy null stream is a wait for every blocking
+ * stream, and a blocking stream that is capturing is still invalidated by it.  A handle whose own call is being captured, or is held by
+ * a capture that will still be replayed, must outlive it. */
 int gnnagg_destroy(gnnagg_handle h);
 /* hipStream_t as void*; NULL = default stream.  Work of later calls is enqueued there, and whatever the library reads of the caller's
  * arrays on the HOST (the CSR, when a schedule or plan is built) is copied on that stream and waited for -- i.e. ordered behind the
@@ -140,7 +145,15 @@ int gnnagg_set_stream(gnnagg_handle h, void *hip_stream);
  * environment-only measurement switch.  libgnnagg_extras.so (-DGNNAGG_EXTRAS, Section E) additionally knows "partition_min_degree",
  * the older forms "retile", "tiled", "spans", "inkernel_combine", "host_plan" and [GNNAGG_PLAN]: second-tier A / B material, constants in
  * the shipped library.
- * Options that change the library-chosen order drop it; it is rebuilt on the next use. */
+ * Options that change the library-chosen order drop it; it is rebuilt on the next use.
+ * History is not visible: a handle that has run, been re-scheduled and had options moved and moved back computes bit for bit, and reports
+ * through every query, what a new handle with the same configuration calls does (tests/test_gpu_handle_lifetime.py) -- with the one
+ * exception stated above, the move to the chunked plan "for good" under "scratch_limit_mb", which lasts until "partitions" is set again.
+ * A call that is refused for its arguments (GNNAGG_ERR_ARG, GNNAGG_ERR_STATE) leaves the handle as it was: the schedule in force, the plans
+ * and gnnagg_last_nn_path are unchanged.  (A call that fails on an allocation or another HIP error may have dropped what it was rebuilding.)
+ * Captured HIP graphs: a captured call holds the handle's scratch and plan pointers, so any later call on the handle that grows scratch (a
+ * wider feat, more heads, another dtype) or drops a plan (one of the options that change the order, gnnagg_schedule,
+ * gnnagg_schedule_balanced) invalidates the capture, which must be captured again before it is replayed. */
 int gnnagg_set_option(gnnagg_handle h, const char *name, int value);
 /* What the library-chosen blocked order cost to build and holds (the reference prints its schedule time, graph_schedule.h:125-127):
  * wall seconds of the last construction of the balanced mode's 2-D blocked order (0: the handle runs the chunked plan, built in O(V))
@@ -189,7 +202,9 @@ int gnnagg_balanced_partitions(gnnagg_handle h, int *partitions, int *total_cols
 /* GNNAGG_MODE_ROWS of a GCN handle: *ranges = the number of source ranges when the canonical chains run on the 2-D blocked order
  * (option "rows_blocked", default 1: graphs of average degree >= "partition_min_degree" whose rows list their neighbors in ascending
  * order -- range after range is then the CSR order, and every (row, column) stays the reference's one sequential chain,
- * aggr_gcn.h:13-35, with the gathers served by the L2; sum / mean, feature widths above 32), 0 when the row kernels run. */
+ * aggr_gcn.h:13-35, with the gathers served by the L2; sum / mean, feature widths above 32), 0 when the row kernels run.  The count is the
+ * chain plan's, which is cut on first use for the width of the run (or, by this query, for 256 columns): it may differ between two handles with
+ * the same options, the results of their runs do not. */
 int gnnagg_rows_blocked_ranges(gnnagg_handle h, int *ranges);
 /* Aggregator::num_target (aggregator.h:126), and the scheduled arrays copied to host buffers
  * (any may be NULL): ptr_s[num_target+1], idx_s[ptr_s[num_target]], target[num_target], val_s. */
@@ -294,7 +309,8 @@ int gnnagg_matmul_nn_typed(const void *d_a, int a_dtype, const void *d_b, int b_
  *           all of k in one LDS image (k <= 602 at n = 128), one head or D = 8, 16, 32, 64; 2: a row-dot kernel behind the GEMM read feat back
  *           (every fp32 call, every other bf16 shape, and the zero fill of k == 0); 0: m == 0.  Measured: profiles/gat_project/
  *           (the environment variable GNNAGG_GAT_PROJECT_FUSE=0, read at every call, sends every call down path 2: the measurement's switch)
- *   Asynchronous on hip_stream; no allocation, no synchronisation: a warm call can be captured in a HIP graph.
+ *   Asynchronous on hip_stream; no allocation, no synchronisation: a warm call can be captured in a HIP graph (it has no handle and no
+ *           scratch: nothing a later call could invalidate -- unlike the captures of handle calls, see gnnagg_set_option).
  * Everything else -- an unknown dtype code, another type combination, heads < 1, n % heads != 0, a negative size, a NULL operand with
  * m, n > 0 -- returns GNNAGG_ERR_ARG with a text naming the function and the combination, before any device call. */
 int gnnagg_gat_project(const void *d_x, int x_dtype, const void *d_w, int w_dtype,
@@ -414,7 +430,9 @@ int gnnagg_gat_row_shift(gnnagg_handle h, const float *d_att, int heads, float s
  *                is bit-equal to the run without the change; a -Inf logit is a weight of +0; a (row, head) whose logits are all -Inf is
  *                NaN.
  *   streams      asynchronous on the handle's stream; nothing is synchronised or allocated once the handle's scratch (V * heads floats
- *                more when d_shift == NULL) exists, and a warm call can be captured in a HIP graph.
+ *                more when d_shift == NULL) exists, and a warm call can be captured in a HIP graph.  The capture holds the handle's scratch
+ *                and plan pointers: a later call that grows scratch (wider feat, more heads, another dtype) or drops a plan (a replan option,
+ *                gnnagg_schedule*) invalidates it, and it must be captured again (gnnagg_set_option).
  * Unshifted still: gnnagg_gat_run / _typed themselves, gnnagg_gat_run_att and the three-step adapter below, the span kernels of the 2-D
  * blocked order, the canonical rows mode, gnnagg_gat_run_part, the distributed step and the backward extras.
  * (tests/test_gpu_gat_shift.py, tests/test_gat_shift_host.py) */
@@ -438,13 +456,14 @@ int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const 
  *                dtype code, feat < 1, feat % heads != 0, slope outside [0, 1], feat > 1024 (the kernel's limit).
  *   streams      on the handle's stream.  The first call builds the list of long rows (one read of ptr, ordered behind the stream) and a call
  *                allocates only while the handle's scratch is smaller than its (feat, heads, x_dtype) needs; any later call of such a shape
- *                allocates and synchronises nothing and can be captured in a HIP graph.
+ *                allocates and synchronises nothing and can be captured in a HIP graph -- until a call of a shape that needs more scratch
+ *                (wider feat, more heads, another dtype) reallocates it: the capture must then be made again (gnnagg_set_option).
  * (tests/test_gpu_gatv2.py, tests/test_gatv2_host.py) */
 int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
                      int heads, float slope);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
- * the chunked plan; 16-byte aligned rows of at most 256 columns.
+ * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
  *   part = 1  d_y[row, :] receives the NUMERATOR sum_e w_e x_e and d_den_io[row, h] the denominator sum_e w_e; no division
  *   part = 2  both are added to what part 1 left (old + new, one fp32 add per element), then the row is divided
  *             (scaleArray, aggr_gat.h:207-213); rows this handle has no edges for are divided all the same
@@ -586,7 +605,8 @@ int gnnagg_unpack_rows2(const float *d_in, int n, int feat, int att_width, float
 /* The whole row-partitioned step behind ONE host call (pack -> grouped send / recv on a communication stream ->
  * local-source pass -> event wait -> halo-source pass).  Asynchronous: stream operations only (fork / join of the caller's stream
  * and the step's own communication stream through events), nothing allocated per step, so a warm step can be captured into a HIP
- * graph.  A rank without peers (comm = 0 or world 1) or without halo rows never creates the second stream.
+ * graph (the capture holds the aggregators' scratch and plan pointers: a later call on them that grows scratch or drops a plan -- a wider
+ * feat, more heads, another dtype, a replan option, gnnagg_schedule* -- invalidates it; capture again, gnnagg_set_option).  A rank without peers (comm = 0 or world 1) or without halo rows never creates the second stream.
  *   gnnagg_dist_step_create   comm (0: single rank); agg_local = aggregator over the edges whose source is an owned row, agg_remote
  *                             = aggregator over the halo-source edges (0: none); d_send_ids / h_send_rows / h_recv_rows = the plan
  *                             of gnnagg_dist_halo_exchange (the counts are copied)
