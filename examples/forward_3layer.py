@@ -28,7 +28,7 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False):
+                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False, transformer=False):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -59,7 +59,7 @@ class Model:
         # fused_project (GAT): feat2 = feat . W and the attention terms in one call (gnnagg_gat_project) instead of two dense launches, with
         # a_dst = w_lr[:, 0] (the centre term's vector) and a_src = w_lr[:, 1].  heads > 1 (through gat_project only): H heads of
         # DIMS[k + 1] / H columns, attention vectors [H, D] drawn behind every other seeded tensor
-        if heads != 1 and not fused_project and not gatv2:
+        if heads != 1 and not fused_project and not gatv2 and not transformer:
             raise ValueError("heads > 1 runs through gat_project: pass fused_project=True")
         self.fused_project, self.heads = fused_project, heads
         if fused_project:
@@ -75,6 +75,11 @@ class Model:
         # shared-weight form); the attention vectors a_k [heads, D] are fp32 and drawn behind every other seeded tensor
         if gatv2:
             self.a_v2 = [torch.randn(heads, DIMS[k + 1] // heads, device=dev) / (DIMS[k + 1] // heads) ** 0.5 for k in range(3)]
+        # transformer (model "our_Transformer"): a layer is ONE projection qkv = feat . [Wq | Wk | Wv] (in x 3 out) and scaled dot-product
+        # attention over the edges on its three column views (Aggregator_GAT.run_dot: no copies), scale = 1 / sqrt(D); the packed weights
+        # are drawn behind every other seeded tensor
+        if transformer:
+            self.w_qkv = [(torch.randn(DIMS[k], 3 * DIMS[k + 1], device=dev) / DIMS[k] ** 0.5).to(dtype) for k in range(3)]
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -136,6 +141,14 @@ class Model:
             self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, out=out.clone()))
         return out
 
+    def transformer_layer(self, feat, out, k):
+        n = DIMS[k + 1]
+        qkv = self.dense(feat, self.w_qkv[k])
+        self.at_gat.run_dot(qkv[:, :n], qkv[:, n:2 * n], qkv[:, 2 * n:], out, heads=self.heads)
+        if self.trace is not None:
+            self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, out=out.clone()))
+        return out
+
     def forward(self, model="our_GCN"):
         if self.fused_nn and model == "our_GCN":
             return self.forward_gcn_fused_nn()
@@ -145,6 +158,8 @@ class Model:
                 x = self.gcn_layer(x, self.outs[k], self.weights[k])
             elif model == "our_GATv2":
                 x = self.gatv2_layer(x, self.outs[k], k)
+            elif model == "our_Transformer":
+                x = self.transformer_layer(x, self.outs[k], k)
             elif self.fused_project:
                 x = self.gat_layer_project(x, self.outs[k], k)
             else:
@@ -154,8 +169,10 @@ class Model:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT", "our_GATv2"],
-                    help="our_GATv2: GATv2 attention (Aggregator_GAT.run_v2) on the projected features; honours --dtype, --heads, --hip-graph")
+    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT", "our_GATv2", "our_Transformer"],
+                    help="our_GATv2: GATv2 attention (Aggregator_GAT.run_v2) on the projected features; our_Transformer: one [Wq | Wk | Wv] "
+                         "projection and scaled dot-product attention on its column views (Aggregator_GAT.run_dot); both honour --dtype, "
+                         "--heads, --hip-graph")
     ap.add_argument("--dataset", default="arxiv")
     ap.add_argument("--datadir", default=None)
     ap.add_argument("--reorder", default="")
@@ -196,8 +213,8 @@ def main():
         ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
-              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or (args.heads != 1 and args.model != "our_GATv2"), heads=args.heads,
-              gatv2=args.model == "our_GATv2")
+              stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or (args.heads != 1 and args.model not in ("our_GATv2", "our_Transformer")), heads=args.heads,
+              gatv2=args.model == "our_GATv2", transformer=args.model == "our_Transformer")
     num_v, num_e = m.num_v, m.num_e
 
     def forward():

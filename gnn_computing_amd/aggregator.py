@@ -13,6 +13,7 @@ allocator / stream provider here; all compute happens in the hand-written HIP ke
 """
 import ctypes
 import enum
+import math
 
 import numpy as np
 import torch
@@ -55,6 +56,24 @@ def _dev_ptr(t, dtype, name):
     if t.dtype != dtype:
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _dev_ptr_rows(t, dtype, name):
+    """_dev_ptr for a row-pitched 2-D view (unit column stride, rows stride(0) elements apart): (pointer, pitch in elements); never a copy"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if t.dim() != 2:
+        raise ValueError("%s must be 2-D [rows, F], got %s" % (name, tuple(t.shape)))
+    if t.shape[1] != 1 and t.stride(1) != 1:
+        raise ValueError("%s must have stride(1) == 1 (a column view of a row-major tensor), got strides %s" % (name, tuple(t.stride())))
+    pitch = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+    if pitch < t.shape[1]:
+        raise ValueError("%s: row pitch stride(0) = %d is below its %d columns" % (name, pitch, t.shape[1]))
+    if not t.is_cuda:
+        raise ValueError("%s must be a HIP device tensor (kernel.cpp:71 CHECK_CUDA)" % name)
+    return ctypes.c_void_p(t.data_ptr()), pitch
 
 
 def _need_extras(what):
@@ -405,6 +424,47 @@ class Aggregator_GAT(Aggregator):
         check(lib().gnnagg_gatv2_run(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt, _dev_ptr(a, torch.float32, "a"),
                                      _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads, ctypes.c_float(slope)))
 
+    def run_dot(self, q, k, v, vout, heads=1, scale=None):
+        """gnnagg_dot_attn_run (extension): scaled dot-product attention over the edges, e_ij = scale * q[i] . k[j] per head (D = F / heads
+        columns), max-shifted edge softmax over each row's edges and the weighted sum of the v rows, in one call.  q [>= V, F], k and v
+        [n_src, F]: all float32 or all bfloat16, row-pitched views allowed (stride(1) == 1; k and v share stride(0)) -- the column views
+        of one [n, 3F] projection are taken as they are, never copied; q, k and v may be one tensor.  vout [>= V, F] float32 or bfloat16
+        (one rounding of the fp32 result), contiguous.  scale=None is 1 / sqrt(D).  Rows without edges are +0.  Everything is checked here
+        before the library is reached."""
+        xt, yt = _feat_dtype(q, "q"), _feat_dtype(vout, "vout")
+        if _feat_dtype(k, "k") != xt or _feat_dtype(v, "v") != xt:
+            raise TypeError("k (%s) and v (%s) must have q's dtype %s" % (k.dtype, v.dtype, q.dtype))
+        heads = int(heads)
+        for t, name in ((q, "q"), (k, "k"), (v, "v")):
+            if t.dim() != 2:
+                raise ValueError("%s must be [rows, F], got %s" % (name, tuple(t.shape)))
+        feat = int(q.shape[1])
+        if heads < 1 or feat < 1 or feat % heads != 0:
+            raise ValueError("run_dot: heads = %d does not divide F = %d" % (heads, feat))
+        if tuple(k.shape) != tuple(v.shape):
+            raise ValueError("run_dot: k %s and v %s must have one shape" % (tuple(k.shape), tuple(v.shape)))
+        if int(k.shape[1]) != feat:
+            raise ValueError("run_dot: k and v have %d columns, q has %d" % (k.shape[1], feat))
+        if q.shape[0] < self.num_v:
+            raise ValueError("q must hold at least V = %d rows" % self.num_v)
+        if vout.numel() < self.num_v * feat:
+            raise ValueError("vout must hold at least V*F elements")
+        scale = 1.0 / math.sqrt(feat // heads) if scale is None else float(scale)
+        if not math.isfinite(scale) or not math.isfinite(ctypes.c_float(scale).value):
+            raise ValueError("run_dot: scale = %r is not finite (in fp32)" % (scale,))
+        for t, name in ((q, "q"), (k, "k"), (v, "v")):
+            if t.shape[1] != 1 and t.stride(1) != 1:
+                raise ValueError("%s must have stride(1) == 1 (a column view of a row-major tensor), got strides %s" % (name, tuple(t.stride())))
+        if k.shape[0] > 1 and k.stride(0) != v.stride(0):
+            raise ValueError("run_dot: k and v must share one row pitch, got stride(0) = %d and %d" % (k.stride(0), v.stride(0)))
+        for t, name in ((q, "q"), (k, "k")):
+            if t.shape[0] > 1 and t.stride(0) < feat:
+                raise ValueError("%s: row pitch stride(0) = %d is below F = %d" % (name, t.stride(0), feat))
+        self._use_current_stream()
+        (pq, q_pitch), (pk, kv_pitch), (pv, _) = _dev_ptr_rows(q, q.dtype, "q"), _dev_ptr_rows(k, k.dtype, "k"), _dev_ptr_rows(v, v.dtype, "v")
+        py = _dev_ptr(vout, vout.dtype, "vout")
+        check(lib().gnnagg_dot_attn_run(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale)))
+
     def run_part(self, vin, vatt, vout, den_io, part, heads=1, slope=0.2):
         """gnnagg_gat_run_part: the fused aggregation in two passes over disjoint edge sets of the same rows.  part=1: vout
         receives the numerators, den_io [V, heads] the denominators; part=2: both are added to and the rows divided."""
@@ -629,6 +689,11 @@ def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
 def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2):
     """Aggregator_GAT.run_v2 as a flat function (extension: the reference has no GATv2)."""
     at.run_v2(xs, xd, a, out, heads=heads, slope=slope)
+
+
+def dot_attn_run(at, q, k, v, out, heads=1, scale=None):
+    """Aggregator_GAT.run_dot as a flat function (extension: the reference has the unnormalised score only, aggr_sddmm.h)."""
+    at.run_dot(q, k, v, out, heads=heads, scale=scale)
 
 
 def gat_schedule(at, neighbor_num):

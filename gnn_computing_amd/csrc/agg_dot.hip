@@ -1,37 +1,49 @@
-// agg_gatv2.hip -- GATv2 ("dynamic attention"): edge score, online edge softmax and weighted aggregation in one pass over the gathered rows.
+// agg_dot.hip -- scaled dot-product attention over a graph's edges (graph-transformer attention): score, online edge softmax and weighted
+// aggregation in one pass over two gathered rows per edge.
 //
-//     e_j = sum_c a[h, c] * leaky(xd[r, hD + c] + xs[j, hD + c]),   y[r] = sum_j softmax_j(e_j) * xs[j]          (gnnagg_gatv2_run)
+//     e_j = scale * sum_c q[r, hD + c] * k[j, hD + c],   y[r] = sum_j softmax_j(e_j) * v[j]          (gnnagg_dot_attn_run)
 //
-// The score needs the gathered source row itself (the non-linearity sits inside the dot product), so the softmax runs ONLINE: every lane
-// keeps a running (m, den, acc) per column fragment and one gather feeds both the score and the sum.
+// A sibling of k_gatv2 (agg_gatv2.hip) on the same frame (gatv2_shared.cuh): the lane geometry of (F, heads, element size), the batches
+// of edges with one guarded rescale, the segments of long rows folded in ascending order through LDS and, for rows of several segments,
+// through scratch by k_gatv2_merge.  What differs is the walk: a lane group keeps its row's q fragments in registers, MULTIPLIED BY scale
+// ONCE (so the score is the fp32 FMA chain over (scale * q) and k; a power-of-two scale commutes with every rounding), and every batch
+// gathers the k fragments (scored) and the v fragments (summed) of its edges; the v loads are issued before the score reduction.
 //
-// Geometry (gatv2_geometry: a function of (F, heads, element size) only, never of a pointer):
-//   * segmented: D * elemsize is a multiple of 16 bytes and a head spans a power-of-two number (<= 64) of 16-byte lanes.  A lane group of
-//     8 .. 64 lanes covers the row, NF = 1, 2 or 4 fragments per lane when F / VEC > 64; the per-head reduction is an xor butterfly over the
-//     head's lanes (every lane of the head ends with the same bits).
-//   * general: any other (heads, D).  One-element lanes, 64-lane groups, NF = ceil(F / 64) fragments per lane; one masked 64-lane
-//     reduction per head.  Slower, and covers heads narrower than a lane and D that no lane width divides.
-// Where X is not 16-byte aligned the segmented geometry stays and a lane loads its elements one by one: same arithmetic, same bits.
+// Batch (dot_batch): kGatv2Batch edges, halved where a lane holds 2 or more fragments -- a batch holds k AND v fragments, twice GATv2's
+// gather registers; measured against batches of 4 and of 1 (DESIGN.md "Dot-product attention", profiles/dot_attn/batch_ab.jsonl).
 //
-// Order of a row (DESIGN.md "GATv2"): edges in CSR order in batches of kGatv2Batch.  Per batch and fragment: the scores; if the batch
-// maximum exceeds m, ONE rescale of (den, acc) by expf(m - new m) (skipped as 0 while m = -inf: no inf - inf); then, edge by edge,
-// w = expf(e - m), den += w, acc = fma(x, w, acc).  Rows above kGatv2LongEdges edges are cut into segments of kGatv2SegEdges edges, one
-// workgroup each: its lane groups walk contiguous chunks, and group 0 folds the (m, den, acc) triples through LDS in ascending chunk order
-// (M = max m; den = sum den_g * expf(m_g - M)).  A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds
-// them the same way, ascending.  No atomics; the same bits on every call.
+// q rows are q_pitch elements apart, k and v rows kv_pitch: column views of one [n, 3F] projection serve as the three operands.  Where a
+// pointer or a pitch is not 16-byte aligned the geometry stays and a lane loads its elements one by one: same arithmetic, same bits.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
 
+struct DotArgs : Gatv2Args {   // q is xd, k is xs (a and slope are unused); what the merge and the store read is the base
+    const void *v;
+    long long q_pitch, kv_pitch;
+    float scale;
+};
+
+#ifndef GNNAGG_DOT_WIDE_BATCH   // A/B switches (measurement builds only): the batch of the geometries with GNNAGG_DOT_WIDE_NF or more fragments per lane
+#define GNNAGG_DOT_WIDE_BATCH (kGatv2Batch / 2)
+#endif
+#ifndef GNNAGG_DOT_WIDE_NF
+#define GNNAGG_DOT_WIDE_NF 2
+#endif
+template <int NF>
+constexpr int dot_batch() { return NF >= GNNAGG_DOT_WIDE_NF ? GNNAGG_DOT_WIDE_BATCH : kGatv2Batch; }
+static_assert(kGatv2Batch % dot_batch<GNNAGG_DOT_WIDE_NF>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
+
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
 template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
-__device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
-                                           const float (&av)[NF][VEC], const int (&hf)[NF], float (&m)[NF], float (&den)[NF],
-                                           float (&acc)[NF][VEC])
+__device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int lane, const float (&qv)[NF][VEC], const int (&hf)[NF],
+                                         float (&m)[NF], float (&den)[NF], float (&acc)[NF][VEC])
 {
-    constexpr int U = kGatv2Batch;
+    constexpr int U = dot_batch<NF>();
     const int F = a.feat;
-    const TX *__restrict__ xs = static_cast<const TX *>(a.xs) + lane * VEC;
+    const size_t pitch = (size_t)a.kv_pitch;
+    const TX *__restrict__ kp = static_cast<const TX *>(a.xs) + lane * VEC;
+    const TX *__restrict__ vp = static_cast<const TX *>(a.v) + lane * VEC;
     const int *__restrict__ idx = a.idx;
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
@@ -41,7 +53,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
         const int n = end - cb < GROUP ? end - cb : GROUP;
         for (int j = 0; j < n; j += U) {
             int s[U];
-            Pack<VEC, TX> xv[U][NF];
+            Pack<VEC, TX> kx[U][NF], vx[U][NF];
             float e[U][NF];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
@@ -50,7 +62,15 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                 if (j + u < n) {
 #pragma unroll
                     for (int f = 0; f < NF; ++f)
-                        if ((f * GROUP + lane) * VEC < F) xv[u][f] = gatv2_load<VEC, TX>(xs + (size_t)s[u] * F + f * GROUP * VEC, a.x_aligned);
+                        if ((f * GROUP + lane) * VEC < F) kx[u][f] = gatv2_load<VEC, TX>(kp + (size_t)s[u] * pitch + f * GROUP * VEC, a.x_aligned);
+                }
+            // the rows to sum: in flight under the score and its reduction
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (j + u < n) {
+#pragma unroll
+                    for (int f = 0; f < NF; ++f)
+                        if ((f * GROUP + lane) * VEC < F) vx[u][f] = gatv2_load<VEC, TX>(vp + (size_t)s[u] * pitch + f * GROUP * VEC, a.x_aligned);
                 }
             // this lane's part of every score
 #pragma unroll
@@ -60,11 +80,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     float p = 0.0f;
                     if (j + u < n && (f * GROUP + lane) * VEC < F) {
 #pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            const float z = xdv[f][k] + xv[u][f].at(k);
-                            const float zs = z * a.slope;
-                            p = __builtin_fmaf(av[f][k], z > zs ? z : zs, p);
-                        }
+                        for (int k = 0; k < VEC; ++k) p = __builtin_fmaf(qv[f][k], kx[u][f].at(k), p);
                     }
                     e[u][f] = p;
                 }
@@ -119,7 +135,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                         const float w = expf(e[u][f] - m[f]);
                         den[f] += w;
 #pragma unroll
-                        for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(xv[u][f].at(k), w, acc[f][k]);
+                        for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(vx[u][f].at(k), w, acc[f][k]);
                     }
             }
         }
@@ -129,7 +145,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
 template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
-__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
+__global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     __shared__ float s_m[BLOCK * NF], s_den[BLOCK * NF], s_acc[BLOCK * NF * VEC];
@@ -153,9 +169,9 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
         beg = a.ptr[row]; end = a.ptr[row + 1];
         if (end - beg > kGatv2LongEdges) return;   // a long row: the segment workgroups' work
     }
-    float xdv[NF][VEC], av[NF][VEC], m[NF], den[NF], acc[NF][VEC];
+    float qv[NF][VEC], m[NF], den[NF], acc[NF][VEC];
     int hf[NF];
-    const TX *__restrict__ xd = static_cast<const TX *>(a.xd) + (size_t)row * F + lane * VEC;
+    const TX *__restrict__ q = static_cast<const TX *>(a.xd) + (size_t)row * (size_t)a.q_pitch + lane * VEC;
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const int col = (f * GROUP + lane) * VEC;
@@ -163,16 +179,15 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
         hf[f] = ok ? col / a.dhead : -1;
         m[f] = -INFINITY;
         den[f] = 0.0f;
-        Pack<VEC, TX> xr;
-        if (ok && beg < end) xr = gatv2_load<VEC, TX>(xd + f * GROUP * VEC, a.x_aligned);
+        Pack<VEC, TX> qr;
+        if (ok && beg < end) qr = gatv2_load<VEC, TX>(q + f * GROUP * VEC, a.x_aligned);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             acc[f][k] = 0.0f;
-            xdv[f][k] = ok && beg < end ? xr.at(k) : 0.0f;
-            av[f][k] = ok ? a.a[col + k] : 0.0f;   // a is [heads, D]: element (h, c) sits at column h D + c
+            qv[f][k] = ok && beg < end ? qr.at(k) * a.scale : 0.0f;   // the scale goes on q, once per row
         }
     }
-    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED>(a, beg, end, lane, xdv, av, hf, m, den, acc);
+    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED>(a, beg, end, lane, qv, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -220,75 +235,72 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
     }
 }
 
-// ------------------------------------------------------------------------------------------------ geometry and launch
-size_t gatv2_slot_floats(int feat, int heads, int x_dtype)
-{
-    Gatv2Geom g;
-    if (!gatv2_geometry(feat, heads, x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, g)) return 0;
-    return (size_t)g.nf * g.group * (g.vec + 2);
-}
-
+// ------------------------------------------------------------------------------------------------ launch
 template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
-static int launch_gatv2_inst(const Gatv2Args &a, hipStream_t stream)
+static int launch_dot_inst(const DotArgs &a, hipStream_t stream)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     const int grid = a.n_seg + a.nblocks_short;
     if (grid > 0) {
-        hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED>), dim3(grid), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     if (a.n_mrows > 0) {
-        hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
+        const Gatv2Args &base = a;
+        hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
         HIP_TRY(hipGetLastError());
     }
     return GNNAGG_OK;
 }
 
 template <int VEC, typename TX>
-static int launch_gatv2_typed(Gatv2Args &a, const Gatv2Geom &g, hipStream_t stream)
+static int launch_dot_typed(DotArgs &a, const Gatv2Geom &g, hipStream_t stream)
 {
     a.nblocks_short = ceil_div(a.V, block_for(g.group) / g.group);
     if (g.segred) {
         switch (g.group * 10 + g.nf) {
-            case 81:  return launch_gatv2_inst<VEC, 8, 1, TX, true>(a, stream);
-            case 161: return launch_gatv2_inst<VEC, 16, 1, TX, true>(a, stream);
-            case 321: return launch_gatv2_inst<VEC, 32, 1, TX, true>(a, stream);
-            case 641: return launch_gatv2_inst<VEC, 64, 1, TX, true>(a, stream);
-            case 642: return launch_gatv2_inst<VEC, 64, 2, TX, true>(a, stream);
+            case 81:  return launch_dot_inst<VEC, 8, 1, TX, true>(a, stream);
+            case 161: return launch_dot_inst<VEC, 16, 1, TX, true>(a, stream);
+            case 321: return launch_dot_inst<VEC, 32, 1, TX, true>(a, stream);
+            case 641: return launch_dot_inst<VEC, 64, 1, TX, true>(a, stream);
+            case 642: return launch_dot_inst<VEC, 64, 2, TX, true>(a, stream);
             case 644:
-                if constexpr (VEC == 4) return launch_gatv2_inst<VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
+                if constexpr (VEC == 4) return launch_dot_inst<VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
                 break;
         }
     } else {
         switch (g.nf) {
-            case 1:  return launch_gatv2_inst<1, 64, 1, TX, false>(a, stream);
-            case 2:  return launch_gatv2_inst<1, 64, 2, TX, false>(a, stream);
-            case 4:  return launch_gatv2_inst<1, 64, 4, TX, false>(a, stream);
-            case 10: return launch_gatv2_inst<1, 64, 10, TX, false>(a, stream);
-            case 16: return launch_gatv2_inst<1, 64, 16, TX, false>(a, stream);
+            case 1:  return launch_dot_inst<1, 64, 1, TX, false>(a, stream);
+            case 2:  return launch_dot_inst<1, 64, 2, TX, false>(a, stream);
+            case 4:  return launch_dot_inst<1, 64, 4, TX, false>(a, stream);
+            case 10: return launch_dot_inst<1, 64, 10, TX, false>(a, stream);
+            case 16: return launch_dot_inst<1, 64, 16, TX, false>(a, stream);
         }
     }
-    return fail(GNNAGG_ERR_STATE, "internal: GATv2 lane geometry without an instantiation");
+    return fail(GNNAGG_ERR_STATE, "internal: dot-product attention lane geometry without an instantiation");
 }
 
-int launch_gatv2(const Gatv2Launch &L, void *stream_v)
+int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
     const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     Gatv2Geom g;
-    if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: GATv2 launch outside the kernel's shapes");
+    if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: dot-product attention launch outside the kernel's shapes");
     if (L.V <= 0) return GNNAGG_OK;
-    Gatv2Args a;
+    DotArgs a;
     a.ptr = L.ptr; a.idx = L.idx; a.seg = reinterpret_cast<const int4 *>(L.seg); a.mrow = reinterpret_cast<const int4 *>(L.mrow);
-    a.xs = L.xs; a.xd = L.xd; a.a = L.a; a.y = L.y; a.scratch = L.scratch;
+    a.xs = L.k; a.xd = L.q; a.a = nullptr; a.y = L.y; a.scratch = L.scratch;
     a.V = L.V; a.n_seg = L.n_seg; a.n_mrows = L.n_mrows; a.nblocks_short = 0; a.feat = L.feat; a.heads = L.heads; a.dhead = L.feat / L.heads;
     a.lph = g.lph; a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
     a.yvec = align_class(L.feat, L.y, ysize, g.vec);
-    a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0) ? 1 : 0;   // (segmented: F * esize is a multiple of 16)
+    // (segmented: F * esize is a multiple of 16, so a lane's 16 bytes are aligned exactly when the base and the row pitch are)
+    a.x_aligned = ((uintptr_t)L.q % 16 == 0 && (uintptr_t)L.k % 16 == 0 && (uintptr_t)L.v % 16 == 0 && (L.q_pitch * esize) % 16 == 0 &&
+                   (L.kv_pitch * esize) % 16 == 0) ? 1 : 0;
     a.slot_stride = g.nf * g.group * (g.vec + 2);
-    a.slope = L.slope;
-    if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_gatv2_typed<8, __bf16>(a, g, stream);
-    return launch_gatv2_typed<4, float>(a, g, stream);
+    a.slope = 0.0f;
+    a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
+    if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_dot_typed<8, __bf16>(a, g, stream);
+    return launch_dot_typed<4, float>(a, g, stream);
 }
 
 }  // namespace gnnagg

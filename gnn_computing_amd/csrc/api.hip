@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2087,6 +2088,41 @@ int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_
     L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.y = d_y; L.scratch = p.scratch.p; L.x_dtype = x_dtype; L.y_dtype = y_dtype;
     L.V = c->V; L.feat = feat; L.heads = heads; L.slope = slope;
     return launch_gatv2(L, c->stream);
+}
+
+int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                        int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale)
+{
+    GET_CTX(h);
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: handle is not a GAT aggregator");
+    if (!d_q || !d_k || !d_v || !d_y)
+        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_dot_attn_run: null pointer (") + (!d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : "d_y") + ")");
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (feat < 1 || heads < 1 || feat % heads != 0)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
+                                        ": needs feat >= 1, heads >= 1 and feat % heads == 0");
+    if (q_pitch < feat || kv_pitch < feat)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: q_pitch = " + std::to_string(q_pitch) + ", kv_pitch = " + std::to_string(kv_pitch) +
+                                        ": a row pitch (in elements) is at least feat = " + std::to_string(feat));
+    if (!std::isfinite(scale))
+        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: scale = " + std::to_string(scale) + " is not finite");
+    if (feat > kGatv2MaxFeat)
+        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: feat = " + std::to_string(feat) + " is above the kernel's limit of " +
+                                        std::to_string(kGatv2MaxFeat) + " columns");
+    if (c->V == 0) return GNNAGG_OK;
+    Ctx::Gatv2Plan &p = c->gatv2;   // the segments, slots and scratch are GATv2's: the same rows are long, and a slot is as large
+    if (!p.valid)
+        if (int rc = gatv2_build_plan(c)) return rc;
+    if (p.n_slots > 0)
+        if (int rc = p.scratch.reserve((size_t)p.n_slots * gatv2_slot_floats(feat, heads, x_dtype))) return rc;
+    DotAttnLaunch L;
+    L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
+    L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.y = d_y; L.scratch = p.scratch.p;
+    L.x_dtype = x_dtype; L.y_dtype = y_dtype; L.V = c->V; L.feat = feat; L.heads = heads; L.scale = scale;
+    return launch_dot_attn(L, c->stream);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

@@ -282,6 +282,21 @@ struct Gatv2Launch {
 };
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype);   // 0: a shape the kernel does not cover
 int launch_gatv2(const Gatv2Launch &a, void *stream);
+// Scaled dot-product attention over the edges (agg_dot.hip, gnnagg_dot_attn_run): GATv2's frame -- the same geometry, segments, scratch
+// slots (gatv2_slot_floats) and merge -- with the score scale * q[r] . k[j] and the sum over a second gathered row v[j].  Pitches in elements.
+struct DotAttnLaunch {
+    const int *ptr = nullptr, *idx = nullptr;
+    const void *seg = nullptr, *mrow = nullptr;
+    int n_seg = 0, n_mrows = 0;
+    const void *q = nullptr, *k = nullptr, *v = nullptr;   // elements of x_dtype; row i of q at i * q_pitch, row j of k / v at j * kv_pitch
+    long long q_pitch = 0, kv_pitch = 0;
+    void *y = nullptr;                                     // dense [V, feat], elements of y_dtype
+    float *scratch = nullptr;
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+    int V = 0, feat = 0, heads = 1;
+    float scale = 1.0f;
+};
+int launch_dot_attn(const DotAttnLaunch &a, void *stream);
 // Backward of the single-head fused GAT aggregation (k_rowdot + k_gat_bwd_edges); wl = chunked edge work items.
 struct GatBwdLaunch {
     WorkList wl;

@@ -1,0 +1,105 @@
+// gatv2_shared.cuh -- what the two online-softmax attention kernels share (agg_gatv2.hip: GATv2; agg_dot.hip: scaled dot-product): the kernel
+// arguments, the row-fragment load and the typed store, the lane geometry and the ordered merge of a long row's segments.
+#pragma once
+#include "kernel_util.cuh"
+
+namespace gnnagg {
+
+struct Gatv2Args {
+    const int *ptr, *idx;
+    const int4 *seg;    // {beg, end, row, slot}: slot < 0 = the row's only segment (stored directly)
+    const int4 *mrow;   // {row, first slot, end slot, -} per row of several segments
+    const void *xs, *xd;
+    const float *a;
+    void *y;
+    float *scratch;     // [n_slots][m: NF * GROUP | den: NF * GROUP | acc: NF * GROUP * VEC]
+    int V, n_seg, n_mrows, nblocks_short, feat, heads, dhead, lph, y_bf16, yvec, x_aligned, slot_stride;
+    float slope;
+};
+
+// VEC elements of a row at p: one 16-byte (or narrower) load, or element by element where the row is not aligned for it
+template <int VEC, typename TX>
+__device__ __forceinline__ Pack<VEC, TX> gatv2_load(const TX *p, int aligned)
+{
+    if constexpr (VEC == 1) {
+        return load_pack<1, TX>(p);
+    } else {
+        if (aligned) return load_pack<VEC, TX>(p);
+        Pack<VEC, TX> r;
+        if constexpr (std::is_same<TX, __bf16>::value) {
+            const unsigned short *q = reinterpret_cast<const unsigned short *>(p);
+#pragma unroll
+            for (int k = 0; k < VEC / 2; ++k) r.w[k] = (unsigned)q[2 * k] | ((unsigned)q[2 * k + 1] << 16);
+        } else {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r.v[k] = p[k];
+        }
+        return r;
+    }
+}
+
+// acc / den of a finished row piece, stored in Y's type
+template <int VEC>
+__device__ __forceinline__ void gatv2_store(const Gatv2Args &a, size_t off, const float (&acc)[VEC], float den, bool has_edges)
+{
+    float o[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o[k] = has_edges ? acc[k] / den : 0.0f;
+    store_y_typed<VEC>(a.y, a.y_bf16, a.yvec, 0, 0u, off, o);
+}
+
+// Rows of several segments: one lane group folds the row's triples in ascending slot order.
+template <int VEC, int GROUP, int NF>
+__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2_merge(const Gatv2Args a)
+{
+    constexpr int GPB = block_of<GROUP>() / GROUP;
+    const int F = a.feat;
+    const int lane = threadIdx.x & (GROUP - 1);
+    const int mi = blockIdx.x * GPB + (int)threadIdx.x / GROUP;
+    if (mi >= a.n_mrows) return;
+    const int4 d = a.mrow[mi];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int col = (f * GROUP + lane) * VEC;
+        if (col >= F) continue;
+        const int i = f * GROUP + lane;
+        float M = -INFINITY;
+        for (int s = d.y; s < d.z; ++s) M = fmaxf(M, a.scratch[(size_t)s * a.slot_stride + i]);
+        float dn = 0.0f, o[VEC] = {};
+        for (int s = d.y; s < d.z; ++s) {
+            const float *sl = a.scratch + (size_t)s * a.slot_stride;
+            const float sc = expf(sl[i] - M);   // (every segment has edges: its m is a score)
+            dn = __builtin_fmaf(sl[NF * GROUP + i], sc, dn);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(sl[2 * NF * GROUP + i * VEC + k], sc, o[k]);
+        }
+        gatv2_store<VEC>(a, (size_t)d.x * F + col, o, dn, true);
+    }
+}
+
+struct Gatv2Geom {
+    int vec, group, nf, lph;
+    bool segred;
+};
+
+static bool gatv2_geometry(int F, int heads, int esize, Gatv2Geom &g)
+{
+    if (F < 1 || heads < 1 || F % heads != 0 || F > kGatv2MaxFeat) return false;
+    const int D = F / heads, vec = 16 / esize;
+    if (D % vec == 0) {
+        const int lph = D / vec;
+        if ((lph & (lph - 1)) == 0 && lph <= 64) {
+            const int lanes = F / vec;
+            int group = 8;
+            while (group < 64 && group < lanes) group <<= 1;
+            const int nf = (lanes + group - 1) / group;
+            g = {vec, group, nf <= 1 ? 1 : nf <= 2 ? 2 : 4, lph, true};   // (F <= 1024: at most 256 16-byte lanes)
+            return true;
+        }
+    }
+    const int nf = (F + 63) / 64;
+    g = {1, 64, nf <= 1 ? 1 : nf <= 2 ? 2 : nf <= 4 ? 4 : nf <= 10 ? 10 : 16, 0, false};
+    return true;
+}
+
+}  // namespace gnnagg

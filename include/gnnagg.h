@@ -461,6 +461,36 @@ int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const 
  * (tests/test_gpu_gatv2.py, tests/test_gatv2_host.py) */
 int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
                      int heads, float slope);
+/* Scaled dot-product attention over the graph's edges (no reference counterpart beyond the unnormalised score of its aggr_sddmm.h; what
+ * PyG's TransformerConv aggregates with, DGL's u_dot_v + edge_softmax + u_mul_e_sum, the sparse attention of graph transformers): score,
+ * edge softmax and aggregation in one call, two gathers per edge.  For row r, head h (D = feat / heads) and every edge j of the row, in
+ * CSR order:
+ *     e_j = sum_c (scale * q[r, hD + c]) * k[j, hD + c]          alpha_j = exp(e_j - max_k e_k) / sum_k exp(e_k - max_k e_k)
+ *     y[r, hD + c] = sum_j alpha_j * v[j, hD + c]
+ *   operands     d_q has at least num_v rows, row i at element i * q_pitch; d_k and d_v have n_src rows (any size the largest column id
+ *                needs), row j at element j * kv_pitch for both.  Pitches are in elements and >= feat, so the column views of one
+ *                [n, 3 * feat] projection x . [Wq | Wk | Wv] serve as the three operands without a copy.  q, k and v hold x_dtype elements
+ *                (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16; bf16 is widened exactly); d_y is dense [num_v, feat] of y_dtype elements.  d_q, d_k
+ *                and d_v may be one pointer.  d_y aliases no input.  Any element offset, any pitch >= feat.
+ *   arithmetic   fp32 throughout.  scale (finite, either sign) is multiplied into the row's q elements ONCE, and a score is the fp32 FMA
+ *                chain of (scale * q) and k: a power-of-two scale gives the bits of the call with q scaled beforehand.  The softmax is
+ *                always max-shifted (online, at most one rescale per batch of edges; never an exp of an unshifted score), so finite
+ *                inputs with finite scores give finite results whatever the scores' magnitude.  A bf16 y is ONE round-to-nearest-even of
+ *                the fp32 result.  A row without edges is +0.  No self loops are added; a duplicate edge counts twice.
+ *   order        a row's result depends on its edges in CSR order and on the lane geometry of (feat, heads, x_dtype) only -- never on a
+ *                pointer's alignment, a pitch or other rows; no atomics; the same bits on every call (DESIGN.md "Dot-product attention").
+ *   error        against the float64 formulas, |y - ref|[r, hD + c] <= 1e-5 * (1 + L[r, h]) * S[r, hD + c] with
+ *                L[r, h] = max_j |scale| * sum_c |q k| and S[r] = sum_j alpha_j |v_j| (the 1e-5 bar widened by the score's condition number).
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, nothing launched, d_y untouched: a handle that is not a GAT aggregator, a
+ *                null pointer, an unknown dtype code, feat < 1, feat % heads != 0, a pitch below feat, a non-finite scale, feat > 1024
+ *                (the kernel's limit, GATv2's).
+ *   streams      on the handle's stream.  The list of long rows and the scratch are those of gnnagg_gatv2_run (built by the first call of
+ *                either kind; the scratch grows to whichever call needs more), so one handle serves both calls in any order.  A call
+ *                whose shape the scratch already covers allocates and synchronises nothing and can be captured in a HIP graph -- until a
+ *                call of either kind reallocates the scratch: the capture must then be made again (gnnagg_set_option).
+ * (tests/test_gpu_dot_attn.py, tests/test_dot_attn_host.py) */
+int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                        int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
