@@ -129,10 +129,13 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                     for (int k = 0; k < VEC; ++k) acc[f][k] *= sc;
                     m[f] = bm;
                 }
+                // m still -inf: every score so far was -inf (or NaN).  The shift is then 0, not m: expf(-inf - 0) is the weight +0 of a
+                // masked edge where -inf - -inf would be NaN.  Any other m is the shift itself: finite rows keep their bits.
+                const float ms = m[f] == -INFINITY ? 0.0f : m[f];
 #pragma unroll
                 for (int u = 0; u < U; ++u)
                     if (j + u < n) {
-                        const float w = expf(e[u][f] - m[f]);
+                        const float w = expf(e[u][f] - ms);
                         den[f] += w;
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(vx[u][f].at(k), w, acc[f][k]);
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
         for (int g = 0; g < GPB; ++g) {
             const int i = (g * NF + f) * GROUP + lane;
             const float mg = s_m[i];
-            const float sc = mg == -INFINITY ? 0.0f : expf(mg - M);   // a chunk without edges
+            const float sc = mg == -INFINITY ? 0.0f : expf(mg - M);   // a chunk without edges, or all masked (M = -inf too)
             d = __builtin_fmaf(s_den[i], sc, d);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(s_acc[i * VEC + k], sc, o[k]);

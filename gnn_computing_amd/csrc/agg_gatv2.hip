@@ -15,10 +15,12 @@
 //
 // Order of a row (DESIGN.md "GATv2"): edges in CSR order in batches of kGatv2Batch.  Per batch and fragment: the scores; if the batch
 // maximum exceeds m, ONE rescale of (den, acc) by expf(m - new m) (skipped as 0 while m = -inf: no inf - inf); then, edge by edge,
-// w = expf(e - m), den += w, acc = fma(x, w, acc).  Rows above kGatv2LongEdges edges are cut into segments of kGatv2SegEdges edges, one
-// workgroup each: its lane groups walk contiguous chunks, and group 0 folds the (m, den, acc) triples through LDS in ascending chunk order
-// (M = max m; den = sum den_g * expf(m_g - M)).  A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds
-// them the same way, ascending.  No atomics; the same bits on every call.
+// w = expf(e - m), den += w, acc = fma(x, w, acc) -- with 0 for m while m is still -inf, so that a -inf score (a masked edge) is a
+// weight of +0 wherever it stands and an all-masked chunk leaves (-inf, 0, 0) (gnnagg.h "non-finite").
+// Rows above kGatv2LongEdges edges are cut into segments of kGatv2SegEdges edges, one workgroup each: its lane groups walk contiguous
+// chunks, and group 0 folds the (m, den, acc) triples through LDS in ascending chunk order (M = max m; den = sum den_g * expf(m_g - M)).
+// A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds them the same way, ascending.  No atomics;
+// the same bits on every call.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
@@ -113,10 +115,13 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     for (int k = 0; k < VEC; ++k) acc[f][k] *= sc;
                     m[f] = bm;
                 }
+                // m still -inf: every score so far was -inf (or NaN).  The shift is then 0, not m: expf(-inf - 0) is the weight +0 of a
+                // masked edge where -inf - -inf would be NaN.  Any other m is the shift itself: finite rows keep their bits.
+                const float ms = m[f] == -INFINITY ? 0.0f : m[f];
 #pragma unroll
                 for (int u = 0; u < U; ++u)
                     if (j + u < n) {
-                        const float w = expf(e[u][f] - m[f]);
+                        const float w = expf(e[u][f] - ms);
                         den[f] += w;
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(xv[u][f].at(k), w, acc[f][k]);
@@ -202,7 +207,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
         for (int g = 0; g < GPB; ++g) {
             const int i = (g * NF + f) * GROUP + lane;
             const float mg = s_m[i];
-            const float sc = mg == -INFINITY ? 0.0f : expf(mg - M);   // a chunk without edges
+            const float sc = mg == -INFINITY ? 0.0f : expf(mg - M);   // a chunk without edges, or all masked (M = -inf too)
             d = __builtin_fmaf(s_den[i], sc, d);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(s_acc[i * VEC + k], sc, o[k]);

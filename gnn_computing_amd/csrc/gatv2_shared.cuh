@@ -68,7 +68,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2_merge(const Gatv2Ar
         float dn = 0.0f, o[VEC] = {};
         for (int s = d.y; s < d.z; ++s) {
             const float *sl = a.scratch + (size_t)s * a.slot_stride;
-            const float sc = expf(sl[i] - M);   // (every segment has edges: its m is a score)
+            const float sc = expf(sl[i] - M);   // (every segment has edges: its m is a score, or -inf with den = acc = 0)
             dn = __builtin_fmaf(sl[NF * GROUP + i], sc, dn);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(sl[2 * NF * GROUP + i * VEC + k], sc, o[k]);

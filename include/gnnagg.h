@@ -452,6 +452,14 @@ int gnnagg_gat_run_shifted(gnnagg_handle h, const void *d_x, int x_dtype, const 
  *                A row without edges is +0.  No self loops are added; a duplicate edge counts twice.
  *   order        a row's result depends on its edges in CSR order and on the lane geometry of (feat, heads, x_dtype) only -- never on a
  *                pointer's alignment or on other rows; no atomics; the same bits on every call (DESIGN.md "GATv2").
+ *   non-finite   plain IEEE: the result has the class map (finite / +Inf / -Inf / NaN, element for element) of the two-pass float64 formulas
+ *                above, as long as the finite scores of a (row, head) lie within 60 of each other (no fp32 weight is 0 where float64's is
+ *                not).  A -Inf score is a weight of exactly +0 wherever it stands in the row; a (row, head) whose scores are all -Inf is NaN
+ *                (0 / 0); a (row, head) with a +Inf or NaN score is NaN in that head's columns (Inf - Inf); every (row, head) the non-finite
+ *                value does not reach is bit-equal to the run without it.  The scored row is the summed row: a -Inf in xs[j, c] that masks
+ *                edge j makes column c of that (row, head) NaN (0 * -Inf) and leaves the head's other columns finite.  A row without edges
+ *                is +0 whatever its xd row holds; a source row that no edge names is never read into a result; a bf16 y is one rounding of
+ *                the fp32 y (NaN kept).  (tests/test_gpu_attn_nonfinite.py, tests/test_attn_nonfinite_host.py)
  *   refusals     GNNAGG_ERR_ARG with a text naming the argument, d_y untouched: a handle that is not a GAT aggregator, a null pointer, an unknown
  *                dtype code, feat < 1, feat % heads != 0, slope outside [0, 1], feat > 1024 (the kernel's limit).
  *   streams      on the handle's stream.  The first call builds the list of long rows (one read of ptr, ordered behind the stream) and a call
@@ -481,6 +489,15 @@ int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_
  *                pointer's alignment, a pitch or other rows; no atomics; the same bits on every call (DESIGN.md "Dot-product attention").
  *   error        against the float64 formulas, |y - ref|[r, hD + c] <= 1e-5 * (1 + L[r, h]) * S[r, hD + c] with
  *                L[r, h] = max_j |scale| * sum_c |q k| and S[r] = sum_j alpha_j |v_j| (the 1e-5 bar widened by the score's condition number).
+ *   non-finite   plain IEEE: the result has the class map (finite / +Inf / -Inf / NaN, element for element) of the two-pass float64 formulas
+ *                above, as long as the finite scores of a (row, head) lie within 60 of each other (no fp32 weight is 0 where float64's is
+ *                not).  A -Inf score -- the mask of attention callers, a -Inf in k -- is a weight of exactly +0 wherever it stands in the
+ *                row, and the finite elements keep the error bound, taken over the edges that are left; a (row, head) whose scores are all
+ *                -Inf is NaN (0 / 0); a (row, head) with a +Inf or NaN score is NaN in that head's columns (Inf - Inf); every (row, head) the
+ *                non-finite value does not reach is bit-equal to the run without it.  A +Inf in v[:, c] is +Inf in column c of every row that
+ *                gathers it (weights are positive), never NaN.  A row without edges is +0 whatever its q row holds; a source row that no
+ *                edge names is never read into a result; a bf16 y is one rounding of the fp32 y (NaN kept).
+ *                (tests/test_gpu_attn_nonfinite.py, tests/test_attn_nonfinite_host.py)
  *   refusals     GNNAGG_ERR_ARG with a text naming the argument, nothing launched, d_y untouched: a handle that is not a GAT aggregator, a
  *                null pointer, an unknown dtype code, feat < 1, feat % heads != 0, a pitch below feat, a non-finite scale, feat > 1024
  *                (the kernel's limit, GATv2's).
