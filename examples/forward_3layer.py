@@ -28,7 +28,7 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False, transformer=False):
+                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False, transformer=False, edge_bias=False):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -80,6 +80,17 @@ class Model:
         # are drawn behind every other seeded tensor
         if transformer:
             self.w_qkv = [(torch.randn(DIMS[k], 3 * DIMS[k + 1], device=dev) / DIMS[k] ** 0.5).to(dtype) for k in range(3)]
+        # edge_bias (--edge-bias, the two attention models): a Graphormer-style encoding added to every edge's score, looked up ONCE here:
+        # bias[p, h] = table[h, bucket(p)] with a seeded [heads, 8] fp32 table (a generator of its own: every other tensor keeps its
+        # values) and bucket(p) = min(7, floor(log2(1 + degree of edge p's source))); [num_e, heads] fp32, the same for the three layers
+        self.edge_bias = None
+        if edge_bias:
+            if not (gatv2 or transformer):
+                raise ValueError("edge_bias belongs to the attention models our_GATv2 and our_Transformer")
+            self.bias_table = torch.randn(heads, 8, generator=torch.Generator().manual_seed(seed + 1)).to(dev)
+            deg = (ptrs[1:] - ptrs[:-1]).to(torch.float64)
+            bucket = (torch.frexp(1.0 + deg[idxs.long()])[1] - 1).clamp(max=7).long()   # floor(log2(x)), exact: x = m * 2^e, m in [0.5, 1)
+            self.edge_bias = self.bias_table.t()[bucket].contiguous()
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -136,17 +147,17 @@ class Model:
 
     def gatv2_layer(self, feat, out, k):
         feat2 = self.dense(feat, self.weights[k])
-        self.at_gat.run_v2(feat2, feat2, self.a_v2[k], out, heads=self.heads)
+        self.at_gat.run_v2(feat2, feat2, self.a_v2[k], out, heads=self.heads, bias=self.edge_bias)
         if self.trace is not None:
-            self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, out=out.clone()))
+            self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, bias=self.edge_bias, out=out.clone()))
         return out
 
     def transformer_layer(self, feat, out, k):
         n = DIMS[k + 1]
         qkv = self.dense(feat, self.w_qkv[k])
-        self.at_gat.run_dot(qkv[:, :n], qkv[:, n:2 * n], qkv[:, 2 * n:], out, heads=self.heads)
+        self.at_gat.run_dot(qkv[:, :n], qkv[:, n:2 * n], qkv[:, 2 * n:], out, heads=self.heads, bias=self.edge_bias)
         if self.trace is not None:
-            self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, out=out.clone()))
+            self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, bias=self.edge_bias, out=out.clone()))
         return out
 
     def forward(self, model="our_GCN"):
@@ -201,10 +212,15 @@ def main():
     ap.add_argument("--stable-softmax", action="store_true",
                     help="GAT: subtract every row's maximal leaky logit before the exp (gnnagg_gat_run_shifted, stable=True): no overflow "
                          "whatever the scale of the weights")
+    ap.add_argument("--edge-bias", action="store_true",
+                    help="our_GATv2 / our_Transformer: add a per-edge, per-head score bias (run_v2 / run_dot bias=): a seeded [heads, 8] table "
+                         "looked up once by min(7, floor(log2(1 + degree of the edge's source)))")
     ap.add_argument("--hip-graph", action="store_true",
                     help="capture one forward in a HIP graph and replay it (the 9-12 launches of a forward are short "
                          "enough on the arxiv-sized graph for launch gaps to show)")
     args = ap.parse_args()
+    if args.edge_bias and args.model not in ("our_GATv2", "our_Transformer"):
+        ap.error("--edge-bias needs --model our_GATv2 or our_Transformer")
     dev = torch.device("cuda", args.gpu)
 
     if args.datadir:
@@ -214,7 +230,7 @@ def main():
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
               stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or (args.heads != 1 and args.model not in ("our_GATv2", "our_Transformer")), heads=args.heads,
-              gatv2=args.model == "our_GATv2", transformer=args.model == "our_Transformer")
+              gatv2=args.model == "our_GATv2", transformer=args.model == "our_Transformer", edge_bias=args.edge_bias)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -244,7 +260,8 @@ def main():
     y = forward()
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
-    print(json.dumps({"model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
+    extra = {"edge_bias": True} if args.edge_bias else {}
+    print(json.dumps({**extra, "model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
                       "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "fused_nn": bool(args.fused_nn), "fused_project": bool(m.fused_project), "heads": args.heads, "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
 
 

@@ -89,6 +89,23 @@ def _mode(scheduled):
     return _lib.MODE_SCHEDULED if scheduled else _lib.MODE_ROWS
 
 
+def _bias_heads(bias, num_e, heads, like, who):
+    """bias_heads of the score bias of run_v2 / run_dot: a contiguous float32 [num_e], [num_e, 1] (one value per edge for every head)
+    or [num_e, heads] tensor on `like`'s device; raises before any device work"""
+    if not isinstance(bias, torch.Tensor):
+        raise TypeError("%s: bias must be a torch.Tensor or None" % who)
+    if bias.dtype != torch.float32:
+        raise TypeError("%s: bias must be torch.float32, got %s" % (who, bias.dtype))
+    shape = tuple(bias.shape)
+    if shape not in ((num_e,), (num_e, 1), (num_e, heads)):
+        raise ValueError("%s: bias must be [num_e = %d], [num_e, 1] or [num_e, heads = %d], got %s" % (who, num_e, heads, shape))
+    if not bias.is_contiguous():
+        raise ValueError("%s: bias must be contiguous, got strides %s" % (who, tuple(bias.stride())))
+    if bias.device != like.device:
+        raise ValueError("%s: bias is on %s, the operands on %s" % (who, bias.device, like.device))
+    return 1 if bias.dim() == 1 else int(shape[1])
+
+
 class Aggregator:
     """reference include/aggregator.h:25-151.  Holds the device CSR (borrowed tensors are kept
     alive by this object) and the scheduled work lists."""
@@ -398,11 +415,13 @@ class Aggregator_GAT(Aggregator):
     GATV2_THRESHOLDS = (4, 8, 16, 32, 64, 128, 512)
     GATV2_MAX_FEAT = 1024
 
-    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2):
+    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2, bias=None):
         """gnnagg_gatv2_run (extension): GATv2 attention, e_ij = a[h] . leaky(xd[i] + xs[j]) per head, max-shifted edge softmax over each row's
         edges and the weighted sum of the xs rows, in one call.  xs [n_src, F], xd [>= V, F]: both float32 or both bfloat16 (xd may be xs);
         a: float32, heads * D elements ([heads, D]); vout [>= V, F] float32 or bfloat16 (one rounding of the fp32 result).  Rows without edges
-        are +0.  Everything is checked here before the library is reached."""
+        are +0.  bias (gnnagg_gatv2_run_bias): float32 [num_e], [num_e, 1] or [num_e, heads], contiguous, added to the score of the edge at
+        that position of the CSR (and head) before the softmax; -inf masks the edge.  None is the call without a bias.  Everything is
+        checked here before the library is reached."""
         xt, yt = _feat_dtype(xs, "xs"), _feat_dtype(vout, "vout")
         if _feat_dtype(xd, "xd") != xt:
             raise TypeError("xd (%s) must have xs's dtype %s" % (xd.dtype, xs.dtype))
@@ -420,17 +439,24 @@ class Aggregator_GAT(Aggregator):
             raise ValueError("xd must hold at least V*F elements")
         if vout.numel() < self.num_v * feat:
             raise ValueError("vout must hold at least V*F elements")
+        bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, xs, "run_v2")
         self._use_current_stream()
-        check(lib().gnnagg_gatv2_run(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt, _dev_ptr(a, torch.float32, "a"),
-                                     _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads, ctypes.c_float(slope)))
+        if bias is None:
+            check(lib().gnnagg_gatv2_run(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt, _dev_ptr(a, torch.float32, "a"),
+                                         _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads, ctypes.c_float(slope)))
+        else:
+            check(lib().gnnagg_gatv2_run_bias(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt,
+                                              _dev_ptr(a, torch.float32, "a"), _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
+                                              ctypes.c_float(slope), _dev_ptr(bias, torch.float32, "bias"), bias_heads))
 
-    def run_dot(self, q, k, v, vout, heads=1, scale=None):
+    def run_dot(self, q, k, v, vout, heads=1, scale=None, bias=None):
         """gnnagg_dot_attn_run (extension): scaled dot-product attention over the edges, e_ij = scale * q[i] . k[j] per head (D = F / heads
         columns), max-shifted edge softmax over each row's edges and the weighted sum of the v rows, in one call.  q [>= V, F], k and v
         [n_src, F]: all float32 or all bfloat16, row-pitched views allowed (stride(1) == 1; k and v share stride(0)) -- the column views
         of one [n, 3F] projection are taken as they are, never copied; q, k and v may be one tensor.  vout [>= V, F] float32 or bfloat16
-        (one rounding of the fp32 result), contiguous.  scale=None is 1 / sqrt(D).  Rows without edges are +0.  Everything is checked here
-        before the library is reached."""
+        (one rounding of the fp32 result), contiguous.  scale=None is 1 / sqrt(D).  Rows without edges are +0.  bias
+        (gnnagg_dot_attn_run_bias): as run_v2's -- float32 [num_e], [num_e, 1] or [num_e, heads], added to the score; -inf masks the edge;
+        None is the call without a bias.  Everything is checked here before the library is reached."""
         xt, yt = _feat_dtype(q, "q"), _feat_dtype(vout, "vout")
         if _feat_dtype(k, "k") != xt or _feat_dtype(v, "v") != xt:
             raise TypeError("k (%s) and v (%s) must have q's dtype %s" % (k.dtype, v.dtype, q.dtype))
@@ -460,10 +486,15 @@ class Aggregator_GAT(Aggregator):
         for t, name in ((q, "q"), (k, "k")):
             if t.shape[0] > 1 and t.stride(0) < feat:
                 raise ValueError("%s: row pitch stride(0) = %d is below F = %d" % (name, t.stride(0), feat))
+        bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, q, "run_dot")
         self._use_current_stream()
         (pq, q_pitch), (pk, kv_pitch), (pv, _) = _dev_ptr_rows(q, q.dtype, "q"), _dev_ptr_rows(k, k.dtype, "k"), _dev_ptr_rows(v, v.dtype, "v")
         py = _dev_ptr(vout, vout.dtype, "vout")
-        check(lib().gnnagg_dot_attn_run(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale)))
+        if bias is None:
+            check(lib().gnnagg_dot_attn_run(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale)))
+        else:
+            check(lib().gnnagg_dot_attn_run_bias(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale),
+                                                 _dev_ptr(bias, torch.float32, "bias"), bias_heads))
 
     def run_part(self, vin, vatt, vout, den_io, part, heads=1, slope=0.2):
         """gnnagg_gat_run_part: the fused aggregation in two passes over disjoint edge sets of the same rows.  part=1: vout
@@ -686,14 +717,14 @@ def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
     at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]), stable=stable)
 
 
-def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2):
+def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2, bias=None):
     """Aggregator_GAT.run_v2 as a flat function (extension: the reference has no GATv2)."""
-    at.run_v2(xs, xd, a, out, heads=heads, slope=slope)
+    at.run_v2(xs, xd, a, out, heads=heads, slope=slope, bias=bias)
 
 
-def dot_attn_run(at, q, k, v, out, heads=1, scale=None):
+def dot_attn_run(at, q, k, v, out, heads=1, scale=None, bias=None):
     """Aggregator_GAT.run_dot as a flat function (extension: the reference has the unnormalised score only, aggr_sddmm.h)."""
-    at.run_dot(q, k, v, out, heads=heads, scale=scale)
+    at.run_dot(q, k, v, out, heads=heads, scale=scale, bias=bias)
 
 
 def gat_schedule(at, neighbor_num):

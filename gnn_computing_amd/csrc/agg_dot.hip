@@ -14,6 +14,8 @@
 //
 // q rows are q_pitch elements apart, k and v rows kv_pitch: column views of one [n, 3F] projection serve as the three operands.  Where a
 // pointer or a pitch is not 16-byte aligned the geometry stays and a lane loads its elements one by one: same arithmetic, same bits.
+//
+// Score bias (gnnagg_dot_attn_run_bias): the BIAS arm of dot_walk / k_dot_attn, as in agg_gatv2.hip -- one fp32 add to the finished score.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
@@ -35,7 +37,7 @@ constexpr int dot_batch() { return NF >= GNNAGG_DOT_WIDE_NF ? GNNAGG_DOT_WIDE_BA
 static_assert(kGatv2Batch % dot_batch<GNNAGG_DOT_WIDE_NF>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
 
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
 __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int lane, const float (&qv)[NF][VEC], const int (&hf)[NF],
                                          float (&m)[NF], float (&den)[NF], float (&acc)[NF][VEC])
 {
@@ -45,16 +47,27 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
     const TX *__restrict__ kp = static_cast<const TX *>(a.xs) + lane * VEC;
     const TX *__restrict__ vp = static_cast<const TX *>(a.v) + lane * VEC;
     const int *__restrict__ idx = a.idx;
+    // BIAS, as in gatv2_walk: per (edge, head) loaded with the batch's rows, per edge (bias_heads == 1) read as a window beside the ids
+    [[maybe_unused]] const bool per_edge = BIAS && a.bias_heads == 1;   // (group-uniform)
+    [[maybe_unused]] float my_b = 0.0f;
+    if constexpr (BIAS) {
+        if (per_edge && beg + lane < end) my_b = a.bias[beg + lane];
+    }
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
     for (int cb = beg; cb < end; cb += GROUP) {
         int nx_s = 0;
         if (cb + GROUP + lane < end) nx_s = idx[cb + GROUP + lane];
+        [[maybe_unused]] float nx_b = 0.0f;
+        if constexpr (BIAS) {
+            if (per_edge && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
+        }
         const int n = end - cb < GROUP ? end - cb : GROUP;
         for (int j = 0; j < n; j += U) {
             int s[U];
             Pack<VEC, TX> kx[U][NF], vx[U][NF];
             float e[U][NF];
+            [[maybe_unused]] float bv[U][NF];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
 #pragma unroll
@@ -72,6 +85,14 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                     for (int f = 0; f < NF; ++f)
                         if ((f * GROUP + lane) * VEC < F) vx[u][f] = gatv2_load<VEC, TX>(vp + (size_t)s[u] * pitch + f * GROUP * VEC, a.x_aligned);
                 }
+            // the batch's biases, one per (edge, head): in flight with the rows (one per edge: already in the window)
+            if constexpr (BIAS) {
+                if (!per_edge) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) gatv2_load_bias<NF>(a, cb + j + u, hf, bv[u]);
+                }
+            }
             // this lane's part of every score
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -114,6 +135,27 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                     }
                 }
             }
+            // the bias: one fp32 add to the finished score (-inf: a masked edge)
+            if constexpr (BIAS) {
+                if (per_edge) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) {
+                            const float b = __shfl(my_b, j + u, GROUP);
+#pragma unroll
+                            for (int f = 0; f < NF; ++f)
+                                if (hf[f] >= 0) e[u][f] += b;
+                        }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) {
+#pragma unroll
+                            for (int f = 0; f < NF; ++f)
+                                if (hf[f] >= 0) e[u][f] += bv[u][f];
+                        }
+                }
+            }
             // online softmax: at most one rescale per batch, then the batch's edges in CSR order
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -143,11 +185,12 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
             }
         }
         my_s = nx_s;
+        if constexpr (BIAS) my_b = nx_b;
     }
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
@@ -190,7 +233,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
             qv[f][k] = ok && beg < end ? qr.at(k) * a.scale : 0.0f;   // the scale goes on q, once per row
         }
     }
-    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED>(a, beg, end, lane, qv, hf, m, den, acc);
+    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED, BIAS>(a, beg, end, lane, qv, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -245,7 +288,9 @@ static int launch_dot_inst(const DotArgs &a, hipStream_t stream)
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     const int grid = a.n_seg + a.nblocks_short;
     if (grid > 0) {
-        hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
+        if (a.bias) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     if (a.n_mrows > 0) {
@@ -301,6 +346,7 @@ int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
                    (L.kv_pitch * esize) % 16 == 0) ? 1 : 0;
     a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = 0.0f;
+    a.bias = L.bias; a.bias_heads = L.bias_heads;
     a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_dot_typed<8, __bf16>(a, g, stream);
     return launch_dot_typed<4, float>(a, g, stream);

@@ -21,12 +21,16 @@
 // chunks, and group 0 folds the (m, den, acc) triples through LDS in ascending chunk order (M = max m; den = sum den_g * expf(m_g - M)).
 // A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds them the same way, ascending.  No atomics;
 // the same bits on every call.
+//
+// Score bias (gnnagg_gatv2_run_bias; the BIAS arm of gatv2_walk / k_gatv2, chosen in launch_gatv2_inst from a.bias != nullptr): one fp32 per
+// edge position, or per (edge position, head), added to the finished score -- after the head's reduction, before the batch maximum.  A -inf
+// bias is a masked edge by the rules above.  BIAS = false is the kernel without the operand, instruction for instruction.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
 
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
 __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
                                            const float (&av)[NF][VEC], const int (&hf)[NF], float (&m)[NF], float (&den)[NF],
                                            float (&acc)[NF][VEC])
@@ -35,16 +39,28 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
     const int F = a.feat;
     const TX *__restrict__ xs = static_cast<const TX *>(a.xs) + lane * VEC;
     const int *__restrict__ idx = a.idx;
+    // BIAS.  bias_heads == heads: the value of (edge, hf[f]) is loaded per (edge, fragment) with the batch's rows.
+    // bias_heads == 1: one value per edge, so the group reads a window of GROUP values beside its ids and shuffles them out (my_b, nx_b).
+    [[maybe_unused]] const bool per_edge = BIAS && a.bias_heads == 1;   // (group-uniform)
+    [[maybe_unused]] float my_b = 0.0f;
+    if constexpr (BIAS) {
+        if (per_edge && beg + lane < end) my_b = a.bias[beg + lane];
+    }
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
     for (int cb = beg; cb < end; cb += GROUP) {
         int nx_s = 0;
         if (cb + GROUP + lane < end) nx_s = idx[cb + GROUP + lane];
+        [[maybe_unused]] float nx_b = 0.0f;
+        if constexpr (BIAS) {
+            if (per_edge && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
+        }
         const int n = end - cb < GROUP ? end - cb : GROUP;
         for (int j = 0; j < n; j += U) {
             int s[U];
             Pack<VEC, TX> xv[U][NF];
             float e[U][NF];
+            [[maybe_unused]] float bv[U][NF];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
 #pragma unroll
@@ -54,6 +70,14 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     for (int f = 0; f < NF; ++f)
                         if ((f * GROUP + lane) * VEC < F) xv[u][f] = gatv2_load<VEC, TX>(xs + (size_t)s[u] * F + f * GROUP * VEC, a.x_aligned);
                 }
+            // the batch's biases, one per (edge, head): in flight with the rows (one per edge: already in the window)
+            if constexpr (BIAS) {
+                if (!per_edge) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) gatv2_load_bias<NF>(a, cb + j + u, hf, bv[u]);
+                }
+            }
             // this lane's part of every score
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -100,6 +124,27 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     }
                 }
             }
+            // the bias: one fp32 add to the finished score (-inf: a masked edge)
+            if constexpr (BIAS) {
+                if (per_edge) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) {
+                            const float b = __shfl(my_b, j + u, GROUP);
+#pragma unroll
+                            for (int f = 0; f < NF; ++f)
+                                if (hf[f] >= 0) e[u][f] += b;
+                        }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        if (j + u < n) {
+#pragma unroll
+                            for (int f = 0; f < NF; ++f)
+                                if (hf[f] >= 0) e[u][f] += bv[u][f];
+                        }
+                }
+            }
             // online softmax: at most one rescale per batch, then the batch's edges in CSR order
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -129,11 +174,12 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
             }
         }
         my_s = nx_s;
+        if constexpr (BIAS) my_b = nx_b;
     }
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
@@ -177,7 +223,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
             av[f][k] = ok ? a.a[col + k] : 0.0f;   // a is [heads, D]: element (h, c) sits at column h D + c
         }
     }
-    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED>(a, beg, end, lane, xdv, av, hf, m, den, acc);
+    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED, BIAS>(a, beg, end, lane, xdv, av, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -239,7 +285,9 @@ static int launch_gatv2_inst(const Gatv2Args &a, hipStream_t stream)
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     const int grid = a.n_seg + a.nblocks_short;
     if (grid > 0) {
-        hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
+        if (a.bias) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     if (a.n_mrows > 0) {
@@ -292,6 +340,7 @@ int launch_gatv2(const Gatv2Launch &L, void *stream_v)
     a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0) ? 1 : 0;   // (segmented: F * esize is a multiple of 16)
     a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = L.slope;
+    a.bias = L.bias; a.bias_heads = L.bias_heads;
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_gatv2_typed<8, __bf16>(a, g, stream);
     return launch_gatv2_typed<4, float>(a, g, stream);
 }

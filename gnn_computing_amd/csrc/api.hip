@@ -2058,25 +2058,29 @@ static int gatv2_build_plan(Ctx *c)
     return GNNAGG_OK;
 }
 
-int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
-                     int heads, float slope)
+// gnnagg_gatv2_run and gnnagg_gatv2_run_bias: one body, the refusals under the caller's name (fn)
+static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y,
+                          int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads)
 {
     GET_CTX(h);
+    const std::string fn(fn_name);
     auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
-    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: handle is not a GAT aggregator");
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
     if (!d_xs || !d_xd || !d_a || !d_y)
-        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_gatv2_run: null pointer (") + (!d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : "d_y") + ")");
+        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : "d_y") + ")");
     if (!known(x_dtype) || !known(y_dtype))
-        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
+        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
     if (feat < 1 || heads < 1 || feat % heads != 0)
-        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
                                         ": needs feat >= 1, heads >= 1 and feat % heads == 0");
     if (!(slope >= 0.0f && slope <= 1.0f))
-        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: slope = " + std::to_string(slope) + " is outside [0, 1] (the leaky form max(z, z * slope))");
+        return fail(GNNAGG_ERR_ARG, fn + ": slope = " + std::to_string(slope) + " is outside [0, 1] (the leaky form max(z, z * slope))");
     if (feat > kGatv2MaxFeat)
-        return fail(GNNAGG_ERR_ARG, "gnnagg_gatv2_run: feat = " + std::to_string(feat) + " is above the kernel's limit of " +
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + " is above the kernel's limit of " +
                                         std::to_string(kGatv2MaxFeat) + " columns");
+    if (d_bias && bias_heads != 1 && bias_heads != heads)
+        return fail(GNNAGG_ERR_ARG, fn + ": bias_heads = " + std::to_string(bias_heads) + " is neither 1 nor heads = " + std::to_string(heads));
     if (c->V == 0) return GNNAGG_OK;
     Ctx::Gatv2Plan &p = c->gatv2;
     if (!p.valid)
@@ -2087,31 +2091,49 @@ int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_
     L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
     L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.y = d_y; L.scratch = p.scratch.p; L.x_dtype = x_dtype; L.y_dtype = y_dtype;
     L.V = c->V; L.feat = feat; L.heads = heads; L.slope = slope;
+    L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
     return launch_gatv2(L, c->stream);
 }
 
-int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
-                        int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale)
+int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
+                     int heads, float slope)
+{
+    return gatv2_run_impl("gnnagg_gatv2_run", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, nullptr, 1);
+}
+
+int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype,
+                          int feat, int heads, float slope, const float *d_bias, int bias_heads)
+{
+    return gatv2_run_impl("gnnagg_gatv2_run_bias", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads);
+}
+
+// gnnagg_dot_attn_run and gnnagg_dot_attn_run_bias: one body, the refusals under the caller's name (fn)
+static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v,
+                             long long kv_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias,
+                             int bias_heads)
 {
     GET_CTX(h);
+    const std::string fn(fn_name);
     auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
-    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: handle is not a GAT aggregator");
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
     if (!d_q || !d_k || !d_v || !d_y)
-        return fail(GNNAGG_ERR_ARG, std::string("gnnagg_dot_attn_run: null pointer (") + (!d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : "d_y") + ")");
+        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : "d_y") + ")");
     if (!known(x_dtype) || !known(y_dtype))
-        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
+        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
     if (feat < 1 || heads < 1 || feat % heads != 0)
-        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
                                         ": needs feat >= 1, heads >= 1 and feat % heads == 0");
     if (q_pitch < feat || kv_pitch < feat)
-        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: q_pitch = " + std::to_string(q_pitch) + ", kv_pitch = " + std::to_string(kv_pitch) +
+        return fail(GNNAGG_ERR_ARG, fn + ": q_pitch = " + std::to_string(q_pitch) + ", kv_pitch = " + std::to_string(kv_pitch) +
                                         ": a row pitch (in elements) is at least feat = " + std::to_string(feat));
     if (!std::isfinite(scale))
-        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: scale = " + std::to_string(scale) + " is not finite");
+        return fail(GNNAGG_ERR_ARG, fn + ": scale = " + std::to_string(scale) + " is not finite");
     if (feat > kGatv2MaxFeat)
-        return fail(GNNAGG_ERR_ARG, "gnnagg_dot_attn_run: feat = " + std::to_string(feat) + " is above the kernel's limit of " +
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + " is above the kernel's limit of " +
                                         std::to_string(kGatv2MaxFeat) + " columns");
+    if (d_bias && bias_heads != 1 && bias_heads != heads)
+        return fail(GNNAGG_ERR_ARG, fn + ": bias_heads = " + std::to_string(bias_heads) + " is neither 1 nor heads = " + std::to_string(heads));
     if (c->V == 0) return GNNAGG_OK;
     Ctx::Gatv2Plan &p = c->gatv2;   // the segments, slots and scratch are GATv2's: the same rows are long, and a slot is as large
     if (!p.valid)
@@ -2122,7 +2144,21 @@ int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, con
     L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
     L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.y = d_y; L.scratch = p.scratch.p;
     L.x_dtype = x_dtype; L.y_dtype = y_dtype; L.V = c->V; L.feat = feat; L.heads = heads; L.scale = scale;
+    L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
     return launch_dot_attn(L, c->stream);
+}
+
+int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                        int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale)
+{
+    return dot_attn_run_impl("gnnagg_dot_attn_run", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale, nullptr, 1);
+}
+
+int gnnagg_dot_attn_run_bias(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                             int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads)
+{
+    return dot_attn_run_impl("gnnagg_dot_attn_run_bias", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale, d_bias,
+                             bias_heads);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

@@ -279,6 +279,8 @@ struct Gatv2Launch {
     int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
     int V = 0, feat = 0, heads = 1;
     float slope = 0.2f;
+    const float *bias = nullptr;               // [num_e, bias_heads] fp32 added to the scores (gnnagg_gatv2_run_bias), or null: no bias
+    int bias_heads = 1;                        // 1 or heads
 };
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype);   // 0: a shape the kernel does not cover
 int launch_gatv2(const Gatv2Launch &a, void *stream);
@@ -295,6 +297,8 @@ struct DotAttnLaunch {
     int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
     int V = 0, feat = 0, heads = 1;
     float scale = 1.0f;
+    const float *bias = nullptr;                           // as Gatv2Launch's (gnnagg_dot_attn_run_bias)
+    int bias_heads = 1;
 };
 int launch_dot_attn(const DotAttnLaunch &a, void *stream);
 // Backward of the single-head fused GAT aggregation (k_rowdot + k_gat_bwd_edges); wl = chunked edge work items.

@@ -15,7 +15,21 @@ struct Gatv2Args {
     float *scratch;     // [n_slots][m: NF * GROUP | den: NF * GROUP | acc: NF * GROUP * VEC]
     int V, n_seg, n_mrows, nblocks_short, feat, heads, dhead, lph, y_bf16, yvec, x_aligned, slot_stride;
     float slope;
+    const float *bias;  // [num_e, bias_heads] fp32 added to the scores, or null (the BIAS arm of the walks runs exactly when it is not)
+    int bias_heads;     // 1 (one value per edge serves every head) or heads
 };
+
+// The bias of edge p for the head of each of this lane's fragments, bias_heads == heads (hf[f]: the fragment's head, -1 past F: nothing is
+// loaded).  A direct per-lane load: the lanes of a head share the address, the heads of an edge and the edges of a batch are consecutive
+// floats.  (bias_heads == 1 is read by the walks as a window of one value per lane, like the ids.)
+template <int NF>
+__device__ __forceinline__ void gatv2_load_bias(const Gatv2Args &a, int p, const int (&hf)[NF], float (&b)[NF])
+{
+    const float *__restrict__ bp = a.bias + (size_t)p * (size_t)a.bias_heads;
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+        if (hf[f] >= 0) b[f] = bp[hf[f]];
+}
 
 // VEC elements of a row at p: one 16-byte (or narrower) load, or element by element where the row is not aligned for it
 template <int VEC, typename TX>

@@ -508,6 +508,34 @@ int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_
  * (tests/test_gpu_dot_attn.py, tests/test_dot_attn_host.py) */
 int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
                         int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale);
+/* gnnagg_gatv2_run and gnnagg_dot_attn_run with a per-edge score bias (no reference counterpart; the spatial and edge encodings of
+ * Graphormer, relative-position and edge-type bias tables, the attention masks of dropped or padded edges, the biased sparse attention of
+ * SAN / GPS).  Everything said under the two calls above holds; what is added:
+ *   operand      d_bias is fp32 and dense, [num_e, bias_heads] row-major with bias_heads = 1 (one value per edge serves every head) or
+ *                bias_heads = heads.  It is indexed by the POSITION p of the edge in the CSR (ptr, idx) the handle was created with --
+ *                edge p of row r is ptr[r] <= p < ptr[r + 1] -- and by head.  For edge p, head h:
+ *                    e_p = (the score above: the fp32 chain, reduced over the head) + d_bias[p * bias_heads + (bias_heads == 1 ? 0 : h)]
+ *                ONE fp32 addition after the per-head reduction and before the batch maximum; the index is taken in 64 bits.  Batches, the
+ *                single guarded rescale, the segments and their ordered merge are those of the calls above.  d_bias needs 4-byte alignment
+ *                only (any element offset).  d_y aliases no input, the bias included.
+ *   no bias      d_bias == NULL is gnnagg_gatv2_run / gnnagg_dot_attn_run bit for bit (the same kernels are launched; bias_heads is then
+ *                ignored); a bias of all +0.0 gives those bits too.
+ *   error        the bound of the calls above with L[r, h] = max over the row's edges with a finite bias of (the call's L term + |bias|).
+ *   masks        a bias of -Inf is a mask, and "non-finite" above applies to the sum as it stands: a masked edge has a weight of exactly +0
+ *                wherever it stands in the row and the finite elements keep the error bound, taken over the edges that are left; a
+ *                (row, head) whose edges are all masked is NaN (0 / 0); a +Inf or NaN bias makes that (row, head) NaN; every other
+ *                (row, head) is bit-equal to the run without the non-finite value.  Rows without edges are +0 and have no bias to read.
+ *                For GATv2 a bias mask poisons no column: the source row stays finite (compare "the scored row is the summed row").
+ *   refusals     those of the calls above under this function's name, and GNNAGG_ERR_ARG naming bias_heads = N where d_bias != NULL and
+ *                bias_heads is neither 1 nor heads; nothing launched, d_y untouched.
+ *   streams      no handle state is added: the list of long rows and the scratch are those of the calls above and sized alike, so one
+ *                handle serves biased and unbiased calls of both kinds in any order, and a biased call is captured in a HIP graph like an
+ *                unbiased one.  The capture holds d_bias as it holds the other operands: rewrite the bias in place between replays.
+ * (tests/test_gpu_attn_bias.py, tests/test_attn_bias_host.py) */
+int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype,
+                          int feat, int heads, float slope, const float *d_bias, int bias_heads);
+int gnnagg_dot_attn_run_bias(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                             int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
