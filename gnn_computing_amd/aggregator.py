@@ -106,6 +106,34 @@ def _bias_heads(bias, num_e, heads, like, who):
     return 1 if bias.dim() == 1 else int(shape[1])
 
 
+def _weights_out(weights, stats, num_v, num_e, heads, like, who):
+    """the two outputs of the weights form of run_v2 / run_dot: weights, a contiguous float32 tensor of num_e * heads elements on `like`'s
+    device ([num_e, heads], or [num_e] at one head), and stats, contiguous float32 [V, heads, 2] (allocated here when None).  Returns
+    stats; (None, None) is the call without weights and returns None; raises before any device work.  (A graph without edges has a weights
+    tensor without elements, whose pointer is null: the callers hand the library the stats pointer in its place -- nothing is written there.)"""
+    if weights is None:
+        if stats is not None:
+            raise ValueError("%s: stats without weights -- the row statistics come with the attention weights" % who)
+        return None
+    for t, name, shapes in ((weights, "weights", ((num_e, heads),) + (((num_e,),) if heads == 1 else ())),
+                            (stats, "stats", ((num_v, heads, 2),))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor or None" % (who, name))
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s must be torch.float32, got %s" % (who, name, t.dtype))
+        if tuple(t.shape) not in shapes:
+            raise ValueError("%s: %s must be %s, got %s" % (who, name, " or ".join(str(list(x)) for x in shapes), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous, got strides %s" % (who, name, tuple(t.stride())))
+        if t.device != like.device:
+            raise ValueError("%s: %s is on %s, the operands on %s" % (who, name, t.device, like.device))
+    if stats is None:
+        stats = torch.empty((num_v, heads, 2), dtype=torch.float32, device=like.device)
+    return stats
+
+
 class Aggregator:
     """reference include/aggregator.h:25-151.  Holds the device CSR (borrowed tensors are kept
     alive by this object) and the scheduled work lists."""
@@ -415,13 +443,17 @@ class Aggregator_GAT(Aggregator):
     GATV2_THRESHOLDS = (4, 8, 16, 32, 64, 128, 512)
     GATV2_MAX_FEAT = 1024
 
-    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2, bias=None):
+    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2, bias=None, weights=None, stats=None):
         """gnnagg_gatv2_run (extension): GATv2 attention, e_ij = a[h] . leaky(xd[i] + xs[j]) per head, max-shifted edge softmax over each row's
         edges and the weighted sum of the xs rows, in one call.  xs [n_src, F], xd [>= V, F]: both float32 or both bfloat16 (xd may be xs);
         a: float32, heads * D elements ([heads, D]); vout [>= V, F] float32 or bfloat16 (one rounding of the fp32 result).  Rows without edges
         are +0.  bias (gnnagg_gatv2_run_bias): float32 [num_e], [num_e, 1] or [num_e, heads], contiguous, added to the score of the edge at
-        that position of the CSR (and head) before the softmax; -inf masks the edge.  None is the call without a bias.  Everything is
-        checked here before the library is reached."""
+        that position of the CSR (and head) before the softmax; -inf masks the edge.  None is the call without a bias.
+        weights (gnnagg_gatv2_run_weights): a contiguous float32 [num_e, heads] tensor ([num_e] at one head) the call fills with the attention
+        weight of every (edge position, head); stats: contiguous float32 [V, heads, 2], filled with every (row, head)'s (score maximum, softmax
+        denominator) -- allocated here when weights is given and stats is None, and returned; give both to keep a captured call free of
+        allocations.  stats without weights is a ValueError; neither is the call without them.  Everything is checked here before the library
+        is reached."""
         xt, yt = _feat_dtype(xs, "xs"), _feat_dtype(vout, "vout")
         if _feat_dtype(xd, "xd") != xt:
             raise TypeError("xd (%s) must have xs's dtype %s" % (xd.dtype, xs.dtype))
@@ -440,7 +472,15 @@ class Aggregator_GAT(Aggregator):
         if vout.numel() < self.num_v * feat:
             raise ValueError("vout must hold at least V*F elements")
         bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, xs, "run_v2")
+        stats = _weights_out(weights, stats, self.num_v, self.num_e, heads, xs, "run_v2")
         self._use_current_stream()
+        if weights is not None:
+            check(lib().gnnagg_gatv2_run_weights(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt,
+                                                 _dev_ptr(a, torch.float32, "a"), _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
+                                                 ctypes.c_float(slope), _dev_ptr(bias, torch.float32, "bias"), bias_heads or 1,
+                                                 _dev_ptr(weights if self.num_e else stats, torch.float32, "weights"),
+                                                 _dev_ptr(stats, torch.float32, "stats")))
+            return stats
         if bias is None:
             check(lib().gnnagg_gatv2_run(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt, _dev_ptr(a, torch.float32, "a"),
                                          _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads, ctypes.c_float(slope)))
@@ -449,14 +489,16 @@ class Aggregator_GAT(Aggregator):
                                               _dev_ptr(a, torch.float32, "a"), _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
                                               ctypes.c_float(slope), _dev_ptr(bias, torch.float32, "bias"), bias_heads))
 
-    def run_dot(self, q, k, v, vout, heads=1, scale=None, bias=None):
+    def run_dot(self, q, k, v, vout, heads=1, scale=None, bias=None, weights=None, stats=None):
         """gnnagg_dot_attn_run (extension): scaled dot-product attention over the edges, e_ij = scale * q[i] . k[j] per head (D = F / heads
         columns), max-shifted edge softmax over each row's edges and the weighted sum of the v rows, in one call.  q [>= V, F], k and v
         [n_src, F]: all float32 or all bfloat16, row-pitched views allowed (stride(1) == 1; k and v share stride(0)) -- the column views
         of one [n, 3F] projection are taken as they are, never copied; q, k and v may be one tensor.  vout [>= V, F] float32 or bfloat16
         (one rounding of the fp32 result), contiguous.  scale=None is 1 / sqrt(D).  Rows without edges are +0.  bias
         (gnnagg_dot_attn_run_bias): as run_v2's -- float32 [num_e], [num_e, 1] or [num_e, heads], added to the score; -inf masks the edge;
-        None is the call without a bias.  Everything is checked here before the library is reached."""
+        None is the call without a bias.  weights / stats (gnnagg_dot_attn_run_weights): as run_v2's -- float32 [num_e, heads] filled with
+        the attention weights and float32 [V, heads, 2] with every (row, head)'s (maximum, denominator), which is returned.  Everything is
+        checked here before the library is reached."""
         xt, yt = _feat_dtype(q, "q"), _feat_dtype(vout, "vout")
         if _feat_dtype(k, "k") != xt or _feat_dtype(v, "v") != xt:
             raise TypeError("k (%s) and v (%s) must have q's dtype %s" % (k.dtype, v.dtype, q.dtype))
@@ -487,9 +529,16 @@ class Aggregator_GAT(Aggregator):
             if t.shape[0] > 1 and t.stride(0) < feat:
                 raise ValueError("%s: row pitch stride(0) = %d is below F = %d" % (name, t.stride(0), feat))
         bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, q, "run_dot")
+        stats = _weights_out(weights, stats, self.num_v, self.num_e, heads, q, "run_dot")
         self._use_current_stream()
         (pq, q_pitch), (pk, kv_pitch), (pv, _) = _dev_ptr_rows(q, q.dtype, "q"), _dev_ptr_rows(k, k.dtype, "k"), _dev_ptr_rows(v, v.dtype, "v")
         py = _dev_ptr(vout, vout.dtype, "vout")
+        if weights is not None:
+            check(lib().gnnagg_dot_attn_run_weights(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale),
+                                                    _dev_ptr(bias, torch.float32, "bias"), bias_heads or 1,
+                                                    _dev_ptr(weights if self.num_e else stats, torch.float32, "weights"),
+                                                    _dev_ptr(stats, torch.float32, "stats")))
+            return stats
         if bias is None:
             check(lib().gnnagg_dot_attn_run(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale)))
         else:
@@ -717,14 +766,14 @@ def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
     at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]), stable=stable)
 
 
-def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2, bias=None):
+def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2, bias=None, weights=None, stats=None):
     """Aggregator_GAT.run_v2 as a flat function (extension: the reference has no GATv2)."""
-    at.run_v2(xs, xd, a, out, heads=heads, slope=slope, bias=bias)
+    return at.run_v2(xs, xd, a, out, heads=heads, slope=slope, bias=bias, weights=weights, stats=stats)
 
 
-def dot_attn_run(at, q, k, v, out, heads=1, scale=None, bias=None):
+def dot_attn_run(at, q, k, v, out, heads=1, scale=None, bias=None, weights=None, stats=None):
     """Aggregator_GAT.run_dot as a flat function (extension: the reference has the unnormalised score only, aggr_sddmm.h)."""
-    at.run_dot(q, k, v, out, heads=heads, scale=scale, bias=bias)
+    return at.run_dot(q, k, v, out, heads=heads, scale=scale, bias=bias, weights=weights, stats=stats)
 
 
 def gat_schedule(at, neighbor_num):

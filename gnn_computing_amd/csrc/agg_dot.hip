@@ -16,6 +16,7 @@
 // pointer or a pitch is not 16-byte aligned the geometry stays and a lane loads its elements one by one: same arithmetic, same bits.
 //
 // Score bias (gnnagg_dot_attn_run_bias): the BIAS arm of dot_walk / k_dot_attn, as in agg_gatv2.hip -- one fp32 add to the finished score.
+// Weights out (gnnagg_dot_attn_run_weights): the WEIGHTS arm, as in agg_gatv2.hip -- raw scores to alpha, (maximum, denominator) to stat.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
@@ -37,7 +38,7 @@ constexpr int dot_batch() { return NF >= GNNAGG_DOT_WIDE_NF ? GNNAGG_DOT_WIDE_BA
 static_assert(kGatv2Batch % dot_batch<GNNAGG_DOT_WIDE_NF>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
 
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
 __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int lane, const float (&qv)[NF][VEC], const int (&hf)[NF],
                                          float (&m)[NF], float (&den)[NF], float (&acc)[NF][VEC])
 {
@@ -48,10 +49,13 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
     const TX *__restrict__ vp = static_cast<const TX *>(a.v) + lane * VEC;
     const int *__restrict__ idx = a.idx;
     // BIAS, as in gatv2_walk: per (edge, head) loaded with the batch's rows, per edge (bias_heads == 1) read as a window beside the ids
-    [[maybe_unused]] const bool per_edge = BIAS && a.bias_heads == 1;   // (group-uniform)
+    // WEIGHTS (BIAS arm only, one instantiation for both): a null bias runs as a per-edge bias of +0.0 that is never loaded -- the unbiased
+    // bits (gnnagg.h "no bias").  has_b is a constant without WEIGHTS: the BIAS arm alone is the kernel it was.
+    [[maybe_unused]] const bool has_b = !WEIGHTS || a.bias != nullptr;             // (group-uniform)
+    [[maybe_unused]] const bool per_edge = BIAS && (a.bias_heads == 1 || !has_b);   // (group-uniform)
     [[maybe_unused]] float my_b = 0.0f;
     if constexpr (BIAS) {
-        if (per_edge && beg + lane < end) my_b = a.bias[beg + lane];
+        if (per_edge && has_b && beg + lane < end) my_b = a.bias[beg + lane];
     }
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
@@ -60,7 +64,7 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
         if (cb + GROUP + lane < end) nx_s = idx[cb + GROUP + lane];
         [[maybe_unused]] float nx_b = 0.0f;
         if constexpr (BIAS) {
-            if (per_edge && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
+            if (per_edge && has_b && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
         }
         const int n = end - cb < GROUP ? end - cb : GROUP;
         for (int j = 0; j < n; j += U) {
@@ -156,6 +160,18 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                         }
                 }
             }
+            // WEIGHTS: the finished score of every (edge, head), raw, from the one lane and fragment that starts the head (idle fragments
+            // have hf = -1); launch_attn_finish turns it into the weight once the row's (maximum, denominator) are final
+            if constexpr (WEIGHTS) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < n) {
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            if (gatv2_head_owner(a, (f * GROUP + lane) * VEC, hf[f]))
+                                a.alpha[(size_t)(cb + j + u) * (size_t)a.heads + (size_t)hf[f]] = e[u][f];
+                    }
+            }
             // online softmax: at most one rescale per batch, then the batch's edges in CSR order
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -190,7 +206,7 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
@@ -233,12 +249,15 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
             qv[f][k] = ok && beg < end ? qr.at(k) * a.scale : 0.0f;   // the scale goes on q, once per row
         }
     }
-    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED, BIAS>(a, beg, end, lane, qv, hf, m, den, acc);
+    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>(a, beg, end, lane, qv, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             const int col = (f * GROUP + lane) * VEC;
             if (col < F) gatv2_store<VEC>(a, (size_t)row * F + col, acc[f], den[f], beg < end);
+            if constexpr (WEIGHTS) {
+                if (gatv2_head_owner(a, col, hf[f])) gatv2_store_stat(a, row, hf[f], m[f], den[f]);   // (no edges: (-inf, +0) as initialised)
+            }
         }
         return;
     }
@@ -270,6 +289,9 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
         }
         if (slot < 0) {
             gatv2_store<VEC>(a, (size_t)row * F + col, o, d, true);
+            if constexpr (WEIGHTS) {
+                if (gatv2_head_owner(a, col, hf[f])) gatv2_store_stat(a, row, hf[f], M, d);
+            }
         } else {
             float *sl = a.scratch + (size_t)slot * a.slot_stride;
             const int i = f * GROUP + lane;
@@ -289,13 +311,16 @@ static int launch_dot_inst(const DotArgs &a, hipStream_t stream)
     const int grid = a.n_seg + a.nblocks_short;
     if (grid > 0) {
         // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
-        if (a.bias) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        // ... and the WEIGHTS arm only where the scores are asked for: ONE more instantiation, with or without a bias (dot_walk: has_b)
+        if (a.alpha) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else if (a.bias) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     if (a.n_mrows > 0) {
         const Gatv2Args &base = a;
-        hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
+        if (a.alpha) hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF, true>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
+        else hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
         HIP_TRY(hipGetLastError());
     }
     return GNNAGG_OK;
@@ -347,6 +372,7 @@ int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
     a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = 0.0f;
     a.bias = L.bias; a.bias_heads = L.bias_heads;
+    a.alpha = L.alpha; a.stat = L.stat;
     a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_dot_typed<8, __bf16>(a, g, stream);
     return launch_dot_typed<4, float>(a, g, stream);

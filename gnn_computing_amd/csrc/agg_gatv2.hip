@@ -25,12 +25,17 @@
 // Score bias (gnnagg_gatv2_run_bias; the BIAS arm of gatv2_walk / k_gatv2, chosen in launch_gatv2_inst from a.bias != nullptr): one fp32 per
 // edge position, or per (edge position, head), added to the finished score -- after the head's reduction, before the batch maximum.  A -inf
 // bias is a masked edge by the rules above.  BIAS = false is the kernel without the operand, instruction for instruction.
+//
+// Weights out (gnnagg_gatv2_run_weights; the WEIGHTS arm, on top of BIAS, chosen in launch_gatv2_inst from a.alpha != nullptr): the finished
+// score of every (edge, head) is stored raw to alpha[p, h] by the lane and fragment that start the head, and the row's final (maximum,
+// denominator) to stat[row, h] from wherever the row is finished -- the short-row store, group 0 after the LDS fold, k_gatv2_merge.
+// launch_attn_finish (aux_kernels.hip), behind this launch on the same stream, makes weights of the scores.  y is computed as without.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
 
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
 __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
                                            const float (&av)[NF][VEC], const int (&hf)[NF], float (&m)[NF], float (&den)[NF],
                                            float (&acc)[NF][VEC])
@@ -41,10 +46,13 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
     const int *__restrict__ idx = a.idx;
     // BIAS.  bias_heads == heads: the value of (edge, hf[f]) is loaded per (edge, fragment) with the batch's rows.
     // bias_heads == 1: one value per edge, so the group reads a window of GROUP values beside its ids and shuffles them out (my_b, nx_b).
-    [[maybe_unused]] const bool per_edge = BIAS && a.bias_heads == 1;   // (group-uniform)
+    // WEIGHTS (BIAS arm only, one instantiation for both): a null bias runs as a per-edge bias of +0.0 that is never loaded -- the unbiased
+    // bits (gnnagg.h "no bias").  has_b is a constant without WEIGHTS: the BIAS arm alone is the kernel it was.
+    [[maybe_unused]] const bool has_b = !WEIGHTS || a.bias != nullptr;             // (group-uniform)
+    [[maybe_unused]] const bool per_edge = BIAS && (a.bias_heads == 1 || !has_b);   // (group-uniform)
     [[maybe_unused]] float my_b = 0.0f;
     if constexpr (BIAS) {
-        if (per_edge && beg + lane < end) my_b = a.bias[beg + lane];
+        if (per_edge && has_b && beg + lane < end) my_b = a.bias[beg + lane];
     }
     int my_s = 0;
     if (beg + lane < end) my_s = idx[beg + lane];
@@ -53,7 +61,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
         if (cb + GROUP + lane < end) nx_s = idx[cb + GROUP + lane];
         [[maybe_unused]] float nx_b = 0.0f;
         if constexpr (BIAS) {
-            if (per_edge && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
+            if (per_edge && has_b && cb + GROUP + lane < end) nx_b = a.bias[cb + GROUP + lane];
         }
         const int n = end - cb < GROUP ? end - cb : GROUP;
         for (int j = 0; j < n; j += U) {
@@ -145,6 +153,18 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                         }
                 }
             }
+            // WEIGHTS: the finished score of every (edge, head), raw, from the one lane and fragment that starts the head (idle fragments
+            // have hf = -1); launch_attn_finish turns it into the weight once the row's (maximum, denominator) are final
+            if constexpr (WEIGHTS) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < n) {
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            if (gatv2_head_owner(a, (f * GROUP + lane) * VEC, hf[f]))
+                                a.alpha[(size_t)(cb + j + u) * (size_t)a.heads + (size_t)hf[f]] = e[u][f];
+                    }
+            }
             // online softmax: at most one rescale per batch, then the batch's edges in CSR order
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
@@ -179,7 +199,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS>
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
@@ -223,12 +243,15 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
             av[f][k] = ok ? a.a[col + k] : 0.0f;   // a is [heads, D]: element (h, c) sits at column h D + c
         }
     }
-    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED, BIAS>(a, beg, end, lane, xdv, av, hf, m, den, acc);
+    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>(a, beg, end, lane, xdv, av, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
             const int col = (f * GROUP + lane) * VEC;
             if (col < F) gatv2_store<VEC>(a, (size_t)row * F + col, acc[f], den[f], beg < end);
+            if constexpr (WEIGHTS) {
+                if (gatv2_head_owner(a, col, hf[f])) gatv2_store_stat(a, row, hf[f], m[f], den[f]);   // (no edges: (-inf, +0) as initialised)
+            }
         }
         return;
     }
@@ -260,6 +283,9 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
         }
         if (slot < 0) {
             gatv2_store<VEC>(a, (size_t)row * F + col, o, d, true);
+            if constexpr (WEIGHTS) {
+                if (gatv2_head_owner(a, col, hf[f])) gatv2_store_stat(a, row, hf[f], M, d);
+            }
         } else {
             float *sl = a.scratch + (size_t)slot * a.slot_stride;
             const int i = f * GROUP + lane;
@@ -286,12 +312,15 @@ static int launch_gatv2_inst(const Gatv2Args &a, hipStream_t stream)
     const int grid = a.n_seg + a.nblocks_short;
     if (grid > 0) {
         // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
-        if (a.bias) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        // ... and the WEIGHTS arm only where the scores are asked for: ONE more instantiation, with or without a bias (gatv2_walk: has_b)
+        if (a.alpha) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else if (a.bias) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
         else hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     if (a.n_mrows > 0) {
-        hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
+        if (a.alpha) hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF, true>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     return GNNAGG_OK;
@@ -341,6 +370,7 @@ int launch_gatv2(const Gatv2Launch &L, void *stream_v)
     a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = L.slope;
     a.bias = L.bias; a.bias_heads = L.bias_heads;
+    a.alpha = L.alpha; a.stat = L.stat;
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_gatv2_typed<8, __bf16>(a, g, stream);
     return launch_gatv2_typed<4, float>(a, g, stream);
 }

@@ -2058,9 +2058,11 @@ static int gatv2_build_plan(Ctx *c)
     return GNNAGG_OK;
 }
 
-// gnnagg_gatv2_run and gnnagg_gatv2_run_bias: one body, the refusals under the caller's name (fn)
+// gnnagg_gatv2_run, gnnagg_gatv2_run_bias and gnnagg_gatv2_run_weights: one body, the refusals under the caller's name (fn).  want_w: the
+// weights-out call, which needs d_alpha and d_stat and runs the finishing pass behind the walk.
 static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y,
-                          int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads)
+                          int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads, bool want_w = false,
+                          float *d_alpha = nullptr, float *d_stat = nullptr)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
@@ -2068,6 +2070,8 @@ static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs
     if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
     if (!d_xs || !d_xd || !d_a || !d_y)
         return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : "d_y") + ")");
+    if (want_w && (!d_alpha || !d_stat))
+        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_alpha ? "d_alpha" : "d_stat") + "): the weights-out call needs both outputs");
     if (!known(x_dtype) || !known(y_dtype))
         return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
@@ -2092,7 +2096,10 @@ static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs
     L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.y = d_y; L.scratch = p.scratch.p; L.x_dtype = x_dtype; L.y_dtype = y_dtype;
     L.V = c->V; L.feat = feat; L.heads = heads; L.slope = slope;
     L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
-    return launch_gatv2(L, c->stream);
+    if (!want_w) return launch_gatv2(L, c->stream);
+    L.alpha = d_alpha; L.stat = d_stat;
+    if (int rc = launch_gatv2(L, c->stream)) return rc;
+    return launch_attn_finish(c->d_ptr, c->V, c->E, heads, d_alpha, d_stat, c->stream);
 }
 
 int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
@@ -2107,10 +2114,11 @@ int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, i
     return gatv2_run_impl("gnnagg_gatv2_run_bias", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads);
 }
 
-// gnnagg_dot_attn_run and gnnagg_dot_attn_run_bias: one body, the refusals under the caller's name (fn)
+// gnnagg_dot_attn_run, gnnagg_dot_attn_run_bias and gnnagg_dot_attn_run_weights: one body, the refusals under the caller's name (fn);
+// want_w as in gatv2_run_impl
 static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v,
                              long long kv_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias,
-                             int bias_heads)
+                             int bias_heads, bool want_w = false, float *d_alpha = nullptr, float *d_stat = nullptr)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
@@ -2118,6 +2126,8 @@ static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d
     if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
     if (!d_q || !d_k || !d_v || !d_y)
         return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : "d_y") + ")");
+    if (want_w && (!d_alpha || !d_stat))
+        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_alpha ? "d_alpha" : "d_stat") + "): the weights-out call needs both outputs");
     if (!known(x_dtype) || !known(y_dtype))
         return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
                                         "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
@@ -2145,7 +2155,10 @@ static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d
     L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.y = d_y; L.scratch = p.scratch.p;
     L.x_dtype = x_dtype; L.y_dtype = y_dtype; L.V = c->V; L.feat = feat; L.heads = heads; L.scale = scale;
     L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
-    return launch_dot_attn(L, c->stream);
+    if (!want_w) return launch_dot_attn(L, c->stream);
+    L.alpha = d_alpha; L.stat = d_stat;
+    if (int rc = launch_dot_attn(L, c->stream)) return rc;
+    return launch_attn_finish(c->d_ptr, c->V, c->E, heads, d_alpha, d_stat, c->stream);
 }
 
 int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
@@ -2159,6 +2172,21 @@ int gnnagg_dot_attn_run_bias(gnnagg_handle h, const void *d_q, long long q_pitch
 {
     return dot_attn_run_impl("gnnagg_dot_attn_run_bias", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale, d_bias,
                              bias_heads);
+}
+
+int gnnagg_gatv2_run_weights(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype,
+                             int feat, int heads, float slope, const float *d_bias, int bias_heads, float *d_alpha, float *d_stat)
+{
+    return gatv2_run_impl("gnnagg_gatv2_run_weights", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads, true,
+                          d_alpha, d_stat);
+}
+
+int gnnagg_dot_attn_run_weights(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                                int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads,
+                                float *d_alpha, float *d_stat)
+{
+    return dot_attn_run_impl("gnnagg_dot_attn_run_weights", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale,
+                             d_bias, bias_heads, true, d_alpha, d_stat);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

@@ -486,6 +486,52 @@ int launch_zero_words(void *p, size_t n, void *stream_v)
     return GNNAGG_OK;
 }
 
+// The finishing pass of gnnagg_gatv2_run_weights / gnnagg_dot_attn_run_weights: the walks left the raw fp32 score of every (edge, head) in
+// alpha and every (row, head)'s final (maximum M, denominator) in stat; here alpha[p, h] = expf(e - ms) / den with ms = M, or 0 where M is
+// -inf (the walks' own shift rule: a masked edge is +0, an all-masked (row, head) 0 / 0).  Edge-parallel, so a row of any length costs what
+// its edges cost and no lane group sweeps a hub: a wavefront takes 64 consecutive edges.  Each lane finds the row of ONE of them -- the last
+// r with ptr[r] <= p (rows without edges share their successor's ptr and are stepped over), a bisection over ptr whose upper levels the
+// whole workgroup shares in cache -- and the wavefront then sweeps the 64 * heads floats of its edges in `heads` steps of 64 consecutive
+// floats, every lane taking the row of its element's edge from the lane that found it: the [E, heads] array is read once and written once
+// in whole coalesced lines, and the bisection runs once per edge, not once per element (one per element measured 108-127 us of a 330-450
+// us call at 8 heads on the arxiv-shaped graph).  A launch of its own behind the walk and the merge on the same
+// stream: the scores and the pairs it reads are ordered before it by the stream.
+__global__ __launch_bounds__(256) void k_attn_finish(const int *__restrict__ ptr, int V, int E, int heads, float *alpha,
+                                                     const float *__restrict__ stat)
+{
+    const int lane = threadIdx.x & 63;
+    const long e0 = (long)blockIdx.x * 256 + (threadIdx.x & ~63);   // the wavefront's first edge
+    int row = 0;
+    if (e0 + lane < E) {
+        const int p = (int)(e0 + lane);
+        int lo = 0, hi = V;   // ptr[lo] <= p < ptr[hi] throughout (ptr[0] = 0, ptr[V] = E > p)
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (ptr[mid] <= p) lo = mid; else hi = mid;
+        }
+        row = lo;
+    }
+    for (int t = 0; t < heads; ++t) {       // (uniform over the wavefront: every lane takes part in the shuffle)
+        const int k = t * 64 + lane;        // this lane's element among the wavefront's 64 * heads
+        const int src = k / heads, h = k - src * heads;
+        const int r = __shfl(row, src, 64);
+        if (e0 + src >= E) continue;
+        const float *st = stat + ((size_t)r * (size_t)heads + (size_t)h) * 2;
+        const float M = st[0], den = st[1];
+        const float ms = M == -INFINITY ? 0.0f : M;
+        float *ap = alpha + (size_t)(e0 + src) * (size_t)heads + (size_t)h;
+        *ap = expf(*ap - ms) / den;
+    }
+}
+
+int launch_attn_finish(const int *ptr, int V, int E, int heads, float *alpha, const float *stat, void *stream_v)
+{
+    if (E <= 0 || V <= 0 || heads <= 0) return GNNAGG_OK;
+    hipLaunchKernelGGL(k_attn_finish, dim3((unsigned)(((long)E + 255) / 256)), dim3(256), 0, (hipStream_t)stream_v, ptr, V, E, heads, alpha, stat);
+    HIP_TRY(hipGetLastError());
+    return GNNAGG_OK;
+}
+
 // The inverse for the canonical rows mode on the blocked order: Yt[tile][row][tile_w] -> y[row][feat], finishing the row on the way
 // (mean: / degree as finish_gcn_row does; ReLU).  One thread per (row, 4-column quad); the caller's rows may be 4-byte aligned only.
 __global__ __launch_bounds__(256) void k_untile_y(const float *__restrict__ yt, float *__restrict__ y, const int *__restrict__ row_ptr,

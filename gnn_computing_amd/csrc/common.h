@@ -281,6 +281,8 @@ struct Gatv2Launch {
     float slope = 0.2f;
     const float *bias = nullptr;               // [num_e, bias_heads] fp32 added to the scores (gnnagg_gatv2_run_bias), or null: no bias
     int bias_heads = 1;                        // 1 or heads
+    float *alpha = nullptr;                    // [num_e, heads] the raw scores out (gnnagg_gatv2_run_weights; launch_attn_finish follows), or null
+    float *stat = nullptr;                     // [V, heads, 2] (maximum, denominator) per (row, head); with alpha
 };
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype);   // 0: a shape the kernel does not cover
 int launch_gatv2(const Gatv2Launch &a, void *stream);
@@ -299,8 +301,12 @@ struct DotAttnLaunch {
     float scale = 1.0f;
     const float *bias = nullptr;                           // as Gatv2Launch's (gnnagg_dot_attn_run_bias)
     int bias_heads = 1;
+    float *alpha = nullptr, *stat = nullptr;               // as Gatv2Launch's (gnnagg_dot_attn_run_weights)
 };
 int launch_dot_attn(const DotAttnLaunch &a, void *stream);
+// The finishing pass of the two weights-out calls (aux_kernels.hip): alpha[p, h] = expf(alpha[p, h] - ms) / den in place, with (M, den) =
+// stat[r, h] of the edge's row r (ptr[r] <= p < ptr[r + 1]) and ms = M, or 0 where M is -inf.  Edge-parallel (a wavefront per 64 consecutive edges, one bisection over ptr per edge), any row length.
+int launch_attn_finish(const int *ptr, int V, int E, int heads, float *alpha, const float *stat, void *stream);
 // Backward of the single-head fused GAT aggregation (k_rowdot + k_gat_bwd_edges); wl = chunked edge work items.
 struct GatBwdLaunch {
     WorkList wl;

@@ -17,7 +17,20 @@ struct Gatv2Args {
     float slope;
     const float *bias;  // [num_e, bias_heads] fp32 added to the scores, or null (the BIAS arm of the walks runs exactly when it is not)
     int bias_heads;     // 1 (one value per edge serves every head) or heads
+    float *alpha;       // [num_e, heads] the finished scores go here raw (the WEIGHTS arm of the walks runs exactly when it is not null) ...
+    float *stat;        // ... with [V, heads, 2] = every (row, head)'s final (maximum, denominator); launch_attn_finish makes weights of them
 };
+
+// Whether fragment f of this lane starts its head (column hf * dhead): the one lane that stores the head's score and (m, den)
+__device__ __forceinline__ bool gatv2_head_owner(const Gatv2Args &a, int col, int hf) { return hf >= 0 && col == hf * a.dhead; }
+
+// (row, head)'s final pair, as it stands (not a log-sum-exp: gnnagg.h "weights")
+__device__ __forceinline__ void gatv2_store_stat(const Gatv2Args &a, int row, int h, float m, float den)
+{
+    float *st = a.stat + ((size_t)row * (size_t)a.heads + (size_t)h) * 2;
+    st[0] = m;
+    st[1] = den;
+}
 
 // The bias of edge p for the head of each of this lane's fragments, bias_heads == heads (hf[f]: the fragment's head, -1 past F: nothing is
 // loaded).  A direct per-lane load: the lanes of a head share the address, the heads of an edge and the edges of a batch are consecutive
@@ -63,7 +76,7 @@ __device__ __forceinline__ void gatv2_store(const Gatv2Args &a, size_t off, cons
 }
 
 // Rows of several segments: one lane group folds the row's triples in ascending slot order.
-template <int VEC, int GROUP, int NF>
+template <int VEC, int GROUP, int NF, bool WEIGHTS = false>
 __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2_merge(const Gatv2Args a)
 {
     constexpr int GPB = block_of<GROUP>() / GROUP;
@@ -82,12 +95,17 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2_merge(const Gatv2Ar
         float dn = 0.0f, o[VEC] = {};
         for (int s = d.y; s < d.z; ++s) {
             const float *sl = a.scratch + (size_t)s * a.slot_stride;
-            const float sc = expf(sl[i] - M);   // (every segment has edges: its m is a score, or -inf with den = acc = 0)
+            // (every segment has edges: its m is a score, or -inf with den = acc = 0.  A row masked whole has M = -inf too and NaN factors:
+            // y is NaN either way, but the WEIGHTS form owes (-inf, +0) to stat and takes the factor 0 of the LDS fold)
+            const float sc = WEIGHTS && sl[i] == -INFINITY ? 0.0f : expf(sl[i] - M);
             dn = __builtin_fmaf(sl[NF * GROUP + i], sc, dn);
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = __builtin_fmaf(sl[2 * NF * GROUP + i * VEC + k], sc, o[k]);
         }
         gatv2_store<VEC>(a, (size_t)d.x * F + col, o, dn, true);
+        if constexpr (WEIGHTS) {
+            if (gatv2_head_owner(a, col, col / a.dhead)) gatv2_store_stat(a, d.x, col / a.dhead, M, dn);
+        }
     }
 }
 

@@ -536,6 +536,42 @@ int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, i
                           int feat, int heads, float slope, const float *d_bias, int bias_heads);
 int gnnagg_dot_attn_run_bias(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
                              int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads);
+/* The two calls above with the attention weights and the softmax's row statistics handed back (what gnnagg_gat_run's d_newval and
+ * gnnagg_gat_row_shift / div are to the 2018 form; PyG's return_attention_weights, DGL's get_attention; the tensors a backward pass
+ * would save).  Everything said under gnnagg_gatv2_run, gnnagg_dot_attn_run and the two _bias calls holds, d_bias == NULL included;
+ * what is added:
+ *   d_alpha      fp32, dense [num_e, heads] row-major, indexed like d_bias with bias_heads == heads: by the POSITION p of the edge in the
+ *                handle's CSR (ptr[r] <= p < ptr[r + 1]) and by head, the index taken in 64 bits.
+ *                    alpha[p, h] = expf(e_p - ms) / den
+ *                e_p is the fp32 score the walk formed for that edge and head -- the same FMA chain, head reduction and single bias add
+ *                that y was summed with, stored once and read back, not a second formula; ms is the (row, head)'s FINAL shift, its
+ *                maximum M, or 0 where M is -Inf (the walk's own rule); den is the denominator y was divided by.
+ *   d_stat       fp32, dense [num_v, heads, 2]: stat[r, h, 0] = M, stat[r, h, 1] = den, the pair as it stands (not M + log den, which
+ *                loses the weights' precision at large scores).  All num_v * heads * 2 values are written by every call: a row without
+ *                edges and an all-masked (row, head) are (-Inf, +0); a (row, head) that a +Inf or NaN score reaches has a NaN den and
+ *                an unspecified M.
+ *   operands     both are required; a caller who wants neither has the calls above.  4-byte alignment only (any element offset).  They
+ *                alias nothing the call reads or writes (with num_e == 0 d_alpha is never written: any non-null pointer serves).
+ *   y            bit-equal to the call without the two outputs, on every shape and every bias form.
+ *   error        |alpha - ref| <= 1e-5 * (1 + L[r, h]) * ref against the float64 two-pass formulas: the calls' y bound with v the
+ *                indicator of one edge's source.  M is within 1e-5 * (1 + L) of the float64 maximum, den within that relative bound.
+ *   non-finite   alpha has the class map of the float64 formulas: a -Inf score or bias gives +0 exactly (the bit pattern) and the row's
+ *                other weights keep the bound; an all-masked (row, head), and one with a +Inf or NaN score, is NaN on every one of its
+ *                edges; every (row, head) the non-finite value does not reach is bit-equal to the run without it.
+ *   refusals     those of the _bias calls under these names, and GNNAGG_ERR_ARG naming d_alpha / d_stat when null; nothing launched,
+ *                d_y, d_alpha and d_stat untouched.
+ *   streams      two or three launches on the handle's stream: the walk (which leaves the raw scores in d_alpha and the pairs in d_stat),
+ *                the merge of multi-segment rows, and an edge-parallel finishing pass that turns the scores into weights in place.  The
+ *                finishing pass finds an edge's row by bisection over the handle's ptr and keeps no plan: no handle state is added.  One
+ *                handle serves weights and no-weights calls of both kinds in any order; a call of a shape that has run allocates and
+ *                synchronises nothing and is captured in a HIP graph like the calls above.  A call without weights launches the kernels
+ *                it launched before these calls existed.
+ * (tests/test_gpu_attn_weights.py, tests/test_attn_weights_host.py) */
+int gnnagg_gatv2_run_weights(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype,
+                             int feat, int heads, float slope, const float *d_bias, int bias_heads, float *d_alpha, float *d_stat);
+int gnnagg_dot_attn_run_weights(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                                int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads,
+                                float *d_alpha, float *d_stat);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
