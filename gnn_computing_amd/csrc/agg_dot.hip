@@ -303,79 +303,30 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
     }
 }
 
+struct DotKernel {   // names the kernel for the launch switches (gatv2_shared.cuh)
+    template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+    static constexpr auto get() { return &k_dot_attn<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
+};
+
 // ------------------------------------------------------------------------------------------------ launch
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
-static int launch_dot_inst(const DotArgs &a, hipStream_t stream)
-{
-    constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
-    const int grid = a.n_seg + a.nblocks_short;
-    if (grid > 0) {
-        // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
-        // ... and the WEIGHTS arm only where the scores are asked for: ONE more instantiation, with or without a bias (dot_walk: has_b)
-        if (a.alpha) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else if (a.bias) hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((k_dot_attn<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (a.n_mrows > 0) {
-        const Gatv2Args &base = a;
-        if (a.alpha) hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF, true>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
-        else hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
-        HIP_TRY(hipGetLastError());
-    }
-    return GNNAGG_OK;
-}
-
-template <int VEC, typename TX>
-static int launch_dot_typed(DotArgs &a, const Gatv2Geom &g, hipStream_t stream)
-{
-    a.nblocks_short = ceil_div(a.V, block_for(g.group) / g.group);
-    if (g.segred) {
-        switch (g.group * 10 + g.nf) {
-            case 81:  return launch_dot_inst<VEC, 8, 1, TX, true>(a, stream);
-            case 161: return launch_dot_inst<VEC, 16, 1, TX, true>(a, stream);
-            case 321: return launch_dot_inst<VEC, 32, 1, TX, true>(a, stream);
-            case 641: return launch_dot_inst<VEC, 64, 1, TX, true>(a, stream);
-            case 642: return launch_dot_inst<VEC, 64, 2, TX, true>(a, stream);
-            case 644:
-                if constexpr (VEC == 4) return launch_dot_inst<VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
-                break;
-        }
-    } else {
-        switch (g.nf) {
-            case 1:  return launch_dot_inst<1, 64, 1, TX, false>(a, stream);
-            case 2:  return launch_dot_inst<1, 64, 2, TX, false>(a, stream);
-            case 4:  return launch_dot_inst<1, 64, 4, TX, false>(a, stream);
-            case 10: return launch_dot_inst<1, 64, 10, TX, false>(a, stream);
-            case 16: return launch_dot_inst<1, 64, 16, TX, false>(a, stream);
-        }
-    }
-    return fail(GNNAGG_ERR_STATE, "internal: dot-product attention lane geometry without an instantiation");
-}
-
 int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
-    const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
+    const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     Gatv2Geom g;
     if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: dot-product attention launch outside the kernel's shapes");
     if (L.V <= 0) return GNNAGG_OK;
     DotArgs a;
-    a.ptr = L.ptr; a.idx = L.idx; a.seg = reinterpret_cast<const int4 *>(L.seg); a.mrow = reinterpret_cast<const int4 *>(L.mrow);
-    a.xs = L.k; a.xd = L.q; a.a = nullptr; a.y = L.y; a.scratch = L.scratch;
-    a.V = L.V; a.n_seg = L.n_seg; a.n_mrows = L.n_mrows; a.nblocks_short = 0; a.feat = L.feat; a.heads = L.heads; a.dhead = L.feat / L.heads;
-    a.lph = g.lph; a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
-    a.yvec = align_class(L.feat, L.y, ysize, g.vec);
+    attn_fill_args(a, L, g);
+    a.xs = L.k; a.xd = L.q; a.a = nullptr;
     // (segmented: F * esize is a multiple of 16, so a lane's 16 bytes are aligned exactly when the base and the row pitch are)
     a.x_aligned = ((uintptr_t)L.q % 16 == 0 && (uintptr_t)L.k % 16 == 0 && (uintptr_t)L.v % 16 == 0 && (L.q_pitch * esize) % 16 == 0 &&
                    (L.kv_pitch * esize) % 16 == 0) ? 1 : 0;
-    a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = 0.0f;
-    a.bias = L.bias; a.bias_heads = L.bias_heads;
-    a.alpha = L.alpha; a.stat = L.stat;
     a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
-    if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_dot_typed<8, __bf16>(a, g, stream);
-    return launch_dot_typed<4, float>(a, g, stream);
+    constexpr const char *no_inst = "internal: dot-product attention lane geometry without an instantiation";
+    if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<DotKernel, 8, __bf16>(a, g, stream, no_inst);
+    return attn_launch_typed<DotKernel, 4, float>(a, g, stream, no_inst);
 }
 
 }  // namespace gnnagg

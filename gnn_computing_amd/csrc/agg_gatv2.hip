@@ -22,11 +22,12 @@
 // A row of several segments leaves one triple per segment in scratch and k_gatv2_merge folds them the same way, ascending.  No atomics;
 // the same bits on every call.
 //
-// Score bias (gnnagg_gatv2_run_bias; the BIAS arm of gatv2_walk / k_gatv2, chosen in launch_gatv2_inst from a.bias != nullptr): one fp32 per
-// edge position, or per (edge position, head), added to the finished score -- after the head's reduction, before the batch maximum.  A -inf
-// bias is a masked edge by the rules above.  BIAS = false is the kernel without the operand, instruction for instruction.
+// Score bias (gnnagg_gatv2_run_bias; the BIAS arm of gatv2_walk / k_gatv2, chosen in attn_launch_inst (gatv2_shared.cuh) from
+// a.bias != nullptr): one fp32 per edge position, or per (edge position, head), added to the finished score -- after the head's reduction,
+// before the batch maximum.  A -inf bias is a masked edge by the rules above.  BIAS = false is the kernel without the operand, instruction
+// for instruction.
 //
-// Weights out (gnnagg_gatv2_run_weights; the WEIGHTS arm, on top of BIAS, chosen in launch_gatv2_inst from a.alpha != nullptr): the finished
+// Weights out (gnnagg_gatv2_run_weights; the WEIGHTS arm, on top of BIAS, chosen in attn_launch_inst from a.alpha != nullptr): the finished
 // score of every (edge, head) is stored raw to alpha[p, h] by the lane and fragment that start the head, and the row's final (maximum,
 // denominator) to stat[row, h] from wherever the row is finished -- the short-row store, group 0 after the LDS fold, k_gatv2_merge.
 // launch_attn_finish (aux_kernels.hip), behind this launch on the same stream, makes weights of the scores.  y is computed as without.
@@ -297,6 +298,11 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
     }
 }
 
+struct Gatv2Kernel {   // names the kernel for the launch switches (gatv2_shared.cuh)
+    template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+    static constexpr auto get() { return &k_gatv2<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
+};
+
 // ------------------------------------------------------------------------------------------------ geometry and launch
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype)
 {
@@ -305,74 +311,21 @@ size_t gatv2_slot_floats(int feat, int heads, int x_dtype)
     return (size_t)g.nf * g.group * (g.vec + 2);
 }
 
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED>
-static int launch_gatv2_inst(const Gatv2Args &a, hipStream_t stream)
-{
-    constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
-    const int grid = a.n_seg + a.nblocks_short;
-    if (grid > 0) {
-        // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
-        // ... and the WEIGHTS arm only where the scores are asked for: ONE more instantiation, with or without a bias (gatv2_walk: has_b)
-        if (a.alpha) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else if (a.bias) hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, true>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((k_gatv2<VEC, GROUP, NF, TX, SEGRED, false>), dim3(grid), dim3(BLOCK), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (a.n_mrows > 0) {
-        if (a.alpha) hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF, true>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return GNNAGG_OK;
-}
-
-template <int VEC, typename TX>
-static int launch_gatv2_typed(Gatv2Args &a, const Gatv2Geom &g, hipStream_t stream)
-{
-    a.nblocks_short = ceil_div(a.V, block_for(g.group) / g.group);
-    if (g.segred) {
-        switch (g.group * 10 + g.nf) {
-            case 81:  return launch_gatv2_inst<VEC, 8, 1, TX, true>(a, stream);
-            case 161: return launch_gatv2_inst<VEC, 16, 1, TX, true>(a, stream);
-            case 321: return launch_gatv2_inst<VEC, 32, 1, TX, true>(a, stream);
-            case 641: return launch_gatv2_inst<VEC, 64, 1, TX, true>(a, stream);
-            case 642: return launch_gatv2_inst<VEC, 64, 2, TX, true>(a, stream);
-            case 644:
-                if constexpr (VEC == 4) return launch_gatv2_inst<VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
-                break;
-        }
-    } else {
-        switch (g.nf) {
-            case 1:  return launch_gatv2_inst<1, 64, 1, TX, false>(a, stream);
-            case 2:  return launch_gatv2_inst<1, 64, 2, TX, false>(a, stream);
-            case 4:  return launch_gatv2_inst<1, 64, 4, TX, false>(a, stream);
-            case 10: return launch_gatv2_inst<1, 64, 10, TX, false>(a, stream);
-            case 16: return launch_gatv2_inst<1, 64, 16, TX, false>(a, stream);
-        }
-    }
-    return fail(GNNAGG_ERR_STATE, "internal: GATv2 lane geometry without an instantiation");
-}
-
 int launch_gatv2(const Gatv2Launch &L, void *stream_v)
 {
     hipStream_t stream = (hipStream_t)stream_v;
-    const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, ysize = L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
     Gatv2Geom g;
-    if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: GATv2 launch outside the kernel's shapes");
+    if (!gatv2_geometry(L.feat, L.heads, L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, g))
+        return fail(GNNAGG_ERR_ARG, "internal: GATv2 launch outside the kernel's shapes");
     if (L.V <= 0) return GNNAGG_OK;
     Gatv2Args a;
-    a.ptr = L.ptr; a.idx = L.idx; a.seg = reinterpret_cast<const int4 *>(L.seg); a.mrow = reinterpret_cast<const int4 *>(L.mrow);
-    a.xs = L.xs; a.xd = L.xd; a.a = L.a; a.y = L.y; a.scratch = L.scratch;
-    a.V = L.V; a.n_seg = L.n_seg; a.n_mrows = L.n_mrows; a.nblocks_short = 0; a.feat = L.feat; a.heads = L.heads; a.dhead = L.feat / L.heads;
-    a.lph = g.lph; a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
-    a.yvec = align_class(L.feat, L.y, ysize, g.vec);
+    attn_fill_args(a, L, g);
+    a.xs = L.xs; a.xd = L.xd; a.a = L.a;
     a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0) ? 1 : 0;   // (segmented: F * esize is a multiple of 16)
-    a.slot_stride = g.nf * g.group * (g.vec + 2);
     a.slope = L.slope;
-    a.bias = L.bias; a.bias_heads = L.bias_heads;
-    a.alpha = L.alpha; a.stat = L.stat;
-    if (L.x_dtype == GNNAGG_DTYPE_BF16) return launch_gatv2_typed<8, __bf16>(a, g, stream);
-    return launch_gatv2_typed<4, float>(a, g, stream);
+    constexpr const char *no_inst = "internal: GATv2 lane geometry without an instantiation";
+    if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<Gatv2Kernel, 8, __bf16>(a, g, stream, no_inst);
+    return attn_launch_typed<Gatv2Kernel, 4, float>(a, g, stream, no_inst);
 }
 
 }  // namespace gnnagg

@@ -2058,48 +2058,75 @@ static int gatv2_build_plan(Ctx *c)
     return GNNAGG_OK;
 }
 
-// gnnagg_gatv2_run, gnnagg_gatv2_run_bias and gnnagg_gatv2_run_weights: one body, the refusals under the caller's name (fn).  want_w: the
-// weights-out call, which needs d_alpha and d_stat and runs the finishing pass behind the walk.
+// What the GATv2 and the dot-product calls share of a run, in three pieces around their own operand checks -- every refusal under the
+// caller's name (fn), and in the order the calls always refused in.  The caller puts what it was given into its launch struct first
+// (common.h: AttnLaunch -- the dtypes, feat, heads, y, the bias, and alpha and stat where it is the weights-out call).
+// 1. the handle's kind; the caller's null operand (null_operand: its name, or null where there is none); want_w (the weights-out call, which
+//    needs alpha and stat and runs the finishing pass behind the walk); the dtype codes; feat and heads
+static int attn_check_call(const Ctx *c, const std::string &fn, const char *null_operand, bool want_w, const AttnLaunch &L)
+{
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
+    if (null_operand) return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + null_operand + ")");
+    if (want_w && (!L.alpha || !L.stat))
+        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!L.alpha ? "d_alpha" : "d_stat") + "): the weights-out call needs both outputs");
+    if (!known(L.x_dtype) || !known(L.y_dtype))
+        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(L.x_dtype) + ", y_dtype " + std::to_string(L.y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (L.feat < 1 || L.heads < 1 || L.feat % L.heads != 0)
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(L.feat) + ", heads = " + std::to_string(L.heads) +
+                                        ": needs feat >= 1, heads >= 1 and feat % heads == 0");
+    return GNNAGG_OK;
+}
+
+// 2. behind the caller's own value checks: the kernel's width and the bias layout; then the plan, the scratch and the handle's part of the
+//    launch.  L.V == 0 afterwards: a graph without rows -- nothing was prepared, the call returns GNNAGG_OK.
+static int attn_prepare(Ctx *c, const std::string &fn, AttnLaunch &L)
+{
+    if (L.feat > kGatv2MaxFeat)
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(L.feat) + " is above the kernel's limit of " +
+                                        std::to_string(kGatv2MaxFeat) + " columns");
+    if (L.bias && L.bias_heads != 1 && L.bias_heads != L.heads)
+        return fail(GNNAGG_ERR_ARG, fn + ": bias_heads = " + std::to_string(L.bias_heads) + " is neither 1 nor heads = " + std::to_string(L.heads));
+    if (!L.bias) L.bias_heads = 1;
+    L.V = c->V;
+    if (L.V == 0) return GNNAGG_OK;
+    Ctx::Gatv2Plan &p = c->gatv2;   // the segments, slots and scratch serve both: the same rows are long, and a slot is as large
+    if (!p.valid)
+        if (int rc = gatv2_build_plan(c)) return rc;
+    if (p.n_slots > 0)
+        if (int rc = p.scratch.reserve((size_t)p.n_slots * gatv2_slot_floats(L.feat, L.heads, L.x_dtype))) return rc;
+    L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
+    L.scratch = p.scratch.p;
+    return GNNAGG_OK;
+}
+
+// 3. behind the caller's launch: the finishing pass of the weights-out call
+static int attn_finish(const Ctx *c, const AttnLaunch &L)
+{
+    if (!L.alpha) return GNNAGG_OK;
+    return launch_attn_finish(c->d_ptr, c->V, c->E, L.heads, L.alpha, L.stat, c->stream);
+}
+
+// gnnagg_gatv2_run, gnnagg_gatv2_run_bias and gnnagg_gatv2_run_weights: one body
 static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y,
                           int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads, bool want_w = false,
                           float *d_alpha = nullptr, float *d_stat = nullptr)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
-    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
-    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
-    if (!d_xs || !d_xd || !d_a || !d_y)
-        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : "d_y") + ")");
-    if (want_w && (!d_alpha || !d_stat))
-        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_alpha ? "d_alpha" : "d_stat") + "): the weights-out call needs both outputs");
-    if (!known(x_dtype) || !known(y_dtype))
-        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
-                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
-    if (feat < 1 || heads < 1 || feat % heads != 0)
-        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
-                                        ": needs feat >= 1, heads >= 1 and feat % heads == 0");
+    Gatv2Launch L;
+    L.x_dtype = x_dtype; L.y = d_y; L.y_dtype = y_dtype; L.feat = feat; L.heads = heads; L.bias = d_bias; L.bias_heads = bias_heads;
+    if (want_w) { L.alpha = d_alpha; L.stat = d_stat; }
+    const char *null_operand = !d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : !d_y ? "d_y" : nullptr;
+    if (int rc = attn_check_call(c, fn, null_operand, want_w, L)) return rc;
     if (!(slope >= 0.0f && slope <= 1.0f))
         return fail(GNNAGG_ERR_ARG, fn + ": slope = " + std::to_string(slope) + " is outside [0, 1] (the leaky form max(z, z * slope))");
-    if (feat > kGatv2MaxFeat)
-        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + " is above the kernel's limit of " +
-                                        std::to_string(kGatv2MaxFeat) + " columns");
-    if (d_bias && bias_heads != 1 && bias_heads != heads)
-        return fail(GNNAGG_ERR_ARG, fn + ": bias_heads = " + std::to_string(bias_heads) + " is neither 1 nor heads = " + std::to_string(heads));
-    if (c->V == 0) return GNNAGG_OK;
-    Ctx::Gatv2Plan &p = c->gatv2;
-    if (!p.valid)
-        if (int rc = gatv2_build_plan(c)) return rc;
-    if (p.n_slots > 0)
-        if (int rc = p.scratch.reserve((size_t)p.n_slots * gatv2_slot_floats(feat, heads, x_dtype))) return rc;
-    Gatv2Launch L;
-    L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
-    L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.y = d_y; L.scratch = p.scratch.p; L.x_dtype = x_dtype; L.y_dtype = y_dtype;
-    L.V = c->V; L.feat = feat; L.heads = heads; L.slope = slope;
-    L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
-    if (!want_w) return launch_gatv2(L, c->stream);
-    L.alpha = d_alpha; L.stat = d_stat;
+    if (int rc = attn_prepare(c, fn, L)) return rc;
+    if (L.V == 0) return GNNAGG_OK;
+    L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.slope = slope;
     if (int rc = launch_gatv2(L, c->stream)) return rc;
-    return launch_attn_finish(c->d_ptr, c->V, c->E, heads, d_alpha, d_stat, c->stream);
+    return attn_finish(c, L);
 }
 
 int gnnagg_gatv2_run(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y, int y_dtype, int feat,
@@ -2114,51 +2141,28 @@ int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, i
     return gatv2_run_impl("gnnagg_gatv2_run_bias", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads);
 }
 
-// gnnagg_dot_attn_run, gnnagg_dot_attn_run_bias and gnnagg_dot_attn_run_weights: one body, the refusals under the caller's name (fn);
-// want_w as in gatv2_run_impl
+// gnnagg_dot_attn_run, gnnagg_dot_attn_run_bias and gnnagg_dot_attn_run_weights: one body
 static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v,
                              long long kv_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias,
                              int bias_heads, bool want_w = false, float *d_alpha = nullptr, float *d_stat = nullptr)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
-    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
-    if (c->kind != Ctx::GAT) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GAT aggregator");
-    if (!d_q || !d_k || !d_v || !d_y)
-        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : "d_y") + ")");
-    if (want_w && (!d_alpha || !d_stat))
-        return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_alpha ? "d_alpha" : "d_stat") + "): the weights-out call needs both outputs");
-    if (!known(x_dtype) || !known(y_dtype))
-        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
-                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
-    if (feat < 1 || heads < 1 || feat % heads != 0)
-        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + ", heads = " + std::to_string(heads) +
-                                        ": needs feat >= 1, heads >= 1 and feat % heads == 0");
+    DotAttnLaunch L;
+    L.x_dtype = x_dtype; L.y = d_y; L.y_dtype = y_dtype; L.feat = feat; L.heads = heads; L.bias = d_bias; L.bias_heads = bias_heads;
+    if (want_w) { L.alpha = d_alpha; L.stat = d_stat; }
+    const char *null_operand = !d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : !d_y ? "d_y" : nullptr;
+    if (int rc = attn_check_call(c, fn, null_operand, want_w, L)) return rc;
     if (q_pitch < feat || kv_pitch < feat)
         return fail(GNNAGG_ERR_ARG, fn + ": q_pitch = " + std::to_string(q_pitch) + ", kv_pitch = " + std::to_string(kv_pitch) +
                                         ": a row pitch (in elements) is at least feat = " + std::to_string(feat));
     if (!std::isfinite(scale))
         return fail(GNNAGG_ERR_ARG, fn + ": scale = " + std::to_string(scale) + " is not finite");
-    if (feat > kGatv2MaxFeat)
-        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + " is above the kernel's limit of " +
-                                        std::to_string(kGatv2MaxFeat) + " columns");
-    if (d_bias && bias_heads != 1 && bias_heads != heads)
-        return fail(GNNAGG_ERR_ARG, fn + ": bias_heads = " + std::to_string(bias_heads) + " is neither 1 nor heads = " + std::to_string(heads));
-    if (c->V == 0) return GNNAGG_OK;
-    Ctx::Gatv2Plan &p = c->gatv2;   // the segments, slots and scratch are GATv2's: the same rows are long, and a slot is as large
-    if (!p.valid)
-        if (int rc = gatv2_build_plan(c)) return rc;
-    if (p.n_slots > 0)
-        if (int rc = p.scratch.reserve((size_t)p.n_slots * gatv2_slot_floats(feat, heads, x_dtype))) return rc;
-    DotAttnLaunch L;
-    L.ptr = c->d_ptr; L.idx = c->d_idx; L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows;
-    L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.y = d_y; L.scratch = p.scratch.p;
-    L.x_dtype = x_dtype; L.y_dtype = y_dtype; L.V = c->V; L.feat = feat; L.heads = heads; L.scale = scale;
-    L.bias = d_bias; L.bias_heads = d_bias ? bias_heads : 1;
-    if (!want_w) return launch_dot_attn(L, c->stream);
-    L.alpha = d_alpha; L.stat = d_stat;
+    if (int rc = attn_prepare(c, fn, L)) return rc;
+    if (L.V == 0) return GNNAGG_OK;
+    L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.scale = scale;
     if (int rc = launch_dot_attn(L, c->stream)) return rc;
-    return launch_attn_finish(c->d_ptr, c->V, c->E, heads, d_alpha, d_stat, c->stream);
+    return attn_finish(c, L);
 }
 
 int gnnagg_dot_attn_run(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,

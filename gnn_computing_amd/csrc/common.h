@@ -268,40 +268,32 @@ int launch_gat_row_shift(const int *ptr, const int *idx, const float *att, float
 // slot < 0 = the row's only segment); rows of several segments leave one (m, den, acc) triple per segment in scratch, folded in ascending
 // order (mrow: int4 {row, first slot, end slot, -}).  feat <= kGatv2MaxFeat.
 constexpr int kGatv2Batch = 4, kGatv2LongEdges = 128, kGatv2SegEdges = 512, kGatv2MaxFeat = 1024;
-struct Gatv2Launch {
+struct AttnLaunch {   // what GATv2 and dot-product attention launch alike (gatv2_shared.cuh: attn_fill_args)
     const int *ptr = nullptr, *idx = nullptr;
     const void *seg = nullptr, *mrow = nullptr;
     int n_seg = 0, n_mrows = 0;
-    const void *xs = nullptr, *xd = nullptr;   // elements of x_dtype
-    const float *a = nullptr;                  // [heads, feat / heads]
-    void *y = nullptr;                         // elements of y_dtype
+    void *y = nullptr;                         // dense [V, feat], elements of y_dtype
     float *scratch = nullptr;                  // n_slots * gatv2_slot_floats(feat, heads, x_dtype) floats
     int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
     int V = 0, feat = 0, heads = 1;
-    float slope = 0.2f;
-    const float *bias = nullptr;               // [num_e, bias_heads] fp32 added to the scores (gnnagg_gatv2_run_bias), or null: no bias
+    const float *bias = nullptr;               // [num_e, bias_heads] fp32 added to the scores (the _run_bias calls), or null: no bias
     int bias_heads = 1;                        // 1 or heads
-    float *alpha = nullptr;                    // [num_e, heads] the raw scores out (gnnagg_gatv2_run_weights; launch_attn_finish follows), or null
+    float *alpha = nullptr;                    // [num_e, heads] the raw scores out (the _run_weights calls; launch_attn_finish follows), or null
     float *stat = nullptr;                     // [V, heads, 2] (maximum, denominator) per (row, head); with alpha
+};
+struct Gatv2Launch : AttnLaunch {
+    const void *xs = nullptr, *xd = nullptr;   // elements of x_dtype
+    const float *a = nullptr;                  // [heads, feat / heads]
+    float slope = 0.2f;
 };
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype);   // 0: a shape the kernel does not cover
 int launch_gatv2(const Gatv2Launch &a, void *stream);
 // Scaled dot-product attention over the edges (agg_dot.hip, gnnagg_dot_attn_run): GATv2's frame -- the same geometry, segments, scratch
 // slots (gatv2_slot_floats) and merge -- with the score scale * q[r] . k[j] and the sum over a second gathered row v[j].  Pitches in elements.
-struct DotAttnLaunch {
-    const int *ptr = nullptr, *idx = nullptr;
-    const void *seg = nullptr, *mrow = nullptr;
-    int n_seg = 0, n_mrows = 0;
+struct DotAttnLaunch : AttnLaunch {
     const void *q = nullptr, *k = nullptr, *v = nullptr;   // elements of x_dtype; row i of q at i * q_pitch, row j of k / v at j * kv_pitch
     long long q_pitch = 0, kv_pitch = 0;
-    void *y = nullptr;                                     // dense [V, feat], elements of y_dtype
-    float *scratch = nullptr;
-    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
-    int V = 0, feat = 0, heads = 1;
     float scale = 1.0f;
-    const float *bias = nullptr;                           // as Gatv2Launch's (gnnagg_dot_attn_run_bias)
-    int bias_heads = 1;
-    float *alpha = nullptr, *stat = nullptr;               // as Gatv2Launch's (gnnagg_dot_attn_run_weights)
 };
 int launch_dot_attn(const DotAttnLaunch &a, void *stream);
 // The finishing pass of the two weights-out calls (aux_kernels.hip): alpha[p, h] = expf(alpha[p, h] - ms) / den in place, with (M, den) =

@@ -1,5 +1,7 @@
 // gatv2_shared.cuh -- what the two online-softmax attention kernels share (agg_gatv2.hip: GATv2; agg_dot.hip: scaled dot-product): the kernel
-// arguments, the row-fragment load and the typed store, the lane geometry and the ordered merge of a long row's segments.
+// arguments, the row-fragment load and the typed store, the lane geometry, the ordered merge of a long row's segments, and the launch: the
+// common members of the arguments (attn_fill_args) and the one pair of dispatch switches both kernels are launched through
+// (attn_launch_inst: none / BIAS / BIAS + WEIGHTS and the merge; attn_launch_typed: the lane geometries).
 #pragma once
 #include "kernel_util.cuh"
 
@@ -132,6 +134,73 @@ static bool gatv2_geometry(int F, int heads, int esize, Gatv2Geom &g)
     const int nf = (F + 63) / 64;
     g = {1, 64, nf <= 1 ? 1 : nf <= 2 ? 2 : nf <= 4 ? 4 : nf <= 10 ? 10 : 16, 0, false};
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ launch
+// The members of Gatv2Args that both attentions fill alike from the common part of their launch structs (common.h: AttnLaunch); the
+// operands (xs, xd, a, slope, x_aligned, and what a derived argument struct adds) are the entry point's own.
+static void attn_fill_args(Gatv2Args &a, const AttnLaunch &L, const Gatv2Geom &g)
+{
+    a.ptr = L.ptr; a.idx = L.idx; a.seg = reinterpret_cast<const int4 *>(L.seg); a.mrow = reinterpret_cast<const int4 *>(L.mrow);
+    a.y = L.y; a.scratch = L.scratch;
+    a.V = L.V; a.n_seg = L.n_seg; a.n_mrows = L.n_mrows; a.nblocks_short = 0; a.feat = L.feat; a.heads = L.heads; a.dhead = L.feat / L.heads;
+    a.lph = g.lph; a.y_bf16 = L.y_dtype == GNNAGG_DTYPE_BF16 ? 1 : 0;
+    a.yvec = align_class(L.feat, L.y, L.y_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, g.vec);
+    a.slot_stride = g.nf * g.group * (g.vec + 2);
+    a.bias = L.bias; a.bias_heads = L.bias_heads;
+    a.alpha = L.alpha; a.stat = L.stat;
+}
+
+// One lane geometry of kernel K (a struct whose get<...>() names the __global__ function: Gatv2Kernel, DotKernel) and the merge behind it.
+template <typename K, int VEC, int GROUP, int NF, typename TX, bool SEGRED, typename ARGS>
+static int attn_launch_inst(const ARGS &a, hipStream_t stream)
+{
+    constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
+    const int grid = a.n_seg + a.nblocks_short;
+    if (grid > 0) {
+        // the BIAS arm only where there is a bias: a call without one launches the kernel it always launched
+        // ... and the WEIGHTS arm only where the scores are asked for: ONE more instantiation, with or without a bias (the walks: has_b)
+        if (a.alpha) hipLaunchKernelGGL((K::template get<VEC, GROUP, NF, TX, SEGRED, true, true>()), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else if (a.bias) hipLaunchKernelGGL((K::template get<VEC, GROUP, NF, TX, SEGRED, true, false>()), dim3(grid), dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((K::template get<VEC, GROUP, NF, TX, SEGRED, false, false>()), dim3(grid), dim3(BLOCK), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (a.n_mrows > 0) {
+        const Gatv2Args &base = a;   // (what the merge and the store read is the base)
+        if (a.alpha) hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF, true>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
+        else hipLaunchKernelGGL((k_gatv2_merge<VEC, GROUP, NF>), dim3(ceil_div(a.n_mrows, GPB)), dim3(BLOCK), 0, stream, base);
+        HIP_TRY(hipGetLastError());
+    }
+    return GNNAGG_OK;
+}
+
+// The instantiations: 6 segmented (GROUP, NF) cases and 5 general fragment counts per element type (no_inst: the caller's message for a
+// geometry outside them, which gatv2_geometry never returns).
+template <typename K, int VEC, typename TX, typename ARGS>
+static int attn_launch_typed(ARGS &a, const Gatv2Geom &g, hipStream_t stream, const char *no_inst)
+{
+    a.nblocks_short = ceil_div(a.V, block_for(g.group) / g.group);
+    if (g.segred) {
+        switch (g.group * 10 + g.nf) {
+            case 81:  return attn_launch_inst<K, VEC, 8, 1, TX, true>(a, stream);
+            case 161: return attn_launch_inst<K, VEC, 16, 1, TX, true>(a, stream);
+            case 321: return attn_launch_inst<K, VEC, 32, 1, TX, true>(a, stream);
+            case 641: return attn_launch_inst<K, VEC, 64, 1, TX, true>(a, stream);
+            case 642: return attn_launch_inst<K, VEC, 64, 2, TX, true>(a, stream);
+            case 644:
+                if constexpr (VEC == 4) return attn_launch_inst<K, VEC, 64, 4, TX, true>(a, stream);   // (bf16: at most 128 lanes)
+                break;
+        }
+    } else {
+        switch (g.nf) {
+            case 1:  return attn_launch_inst<K, 1, 64, 1, TX, false>(a, stream);
+            case 2:  return attn_launch_inst<K, 1, 64, 2, TX, false>(a, stream);
+            case 4:  return attn_launch_inst<K, 1, 64, 4, TX, false>(a, stream);
+            case 10: return attn_launch_inst<K, 1, 64, 10, TX, false>(a, stream);
+            case 16: return attn_launch_inst<K, 1, 64, 16, TX, false>(a, stream);
+        }
+    }
+    return fail(GNNAGG_ERR_STATE, no_inst);
 }
 
 }  // namespace gnnagg

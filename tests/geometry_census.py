@@ -51,7 +51,7 @@ def typed_geometry(F, esize, dhead=None, align=16):
 
 def gatv2_geometry(F, heads, esize):
     """gatv2_shared.cuh gatv2_geometry: (segred, vec, group, nf_raw, nf, lph), or None where the picker refuses the shape.  nf_raw is the
-    fragment count the row needs, nf the instantiated one it is rounded up to (the launchers switch on group * 10 + nf, or on nf)."""
+    fragment count the row needs, nf the instantiated one it is rounded up to (attn_launch_typed switches on group * 10 + nf, or on nf)."""
     if F < 1 or heads < 1 or F % heads != 0 or F > GATV2_MAX_FEAT:
         return None
     D, vec = F // heads, 16 // esize
@@ -110,7 +110,7 @@ GAT_BF16 = {
     (4, 32): (8, 16, 1),    # D % 32 == 0 (see GAT_F32)
 }
 
-# run_v2 / run_dot: (heads, D) -> {element size: (segred, vec, group, nf_raw, nf, lph)}.  Every switch label of both launchers for both
+# run_v2 / run_dot: (heads, D) -> {element size: (segred, vec, group, nf_raw, nf, lph)}.  Every switch label of the shared launcher for both
 # element sizes; every rounded fragment count (nf_raw < nf: whole fragments past F); head counts 3, 5, 6, 7 in the segmented geometry
 # (idle lanes inside a group, a partly filled last fragment); lph = 64; one shape segmented in bf16 and general in fp32.
 GATV2 = {

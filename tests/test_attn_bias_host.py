@@ -325,13 +325,16 @@ def test_header_declares_and_the_library_exports_the_bias_calls():
         assert getattr(gnc.lib(), name).argtypes == args
     for phrase in ("p * bias_heads + (bias_heads == 1 ? 0 : h)", "a bias of -Inf is a mask", "captured in a HIP graph"):
         assert phrase in text
-    # the kernels: the operand pair of the shared arguments, and the arm chosen from the pointer in the two launchers
+    # the kernels: the operand pair of the shared arguments, and the arm chosen from the pointer in the one launcher both kernels go through
     csrc = os.path.join(ROOT, "gnn_computing_amd", "csrc")
-    assert re.search(r"const float \*bias;.*\n\s*int bias_heads;", open(os.path.join(csrc, "gatv2_shared.cuh")).read())
-    for name, kernel in (("agg_gatv2.hip", "k_gatv2"), ("agg_dot.hip", "k_dot_attn")):
+    shared = open(os.path.join(csrc, "gatv2_shared.cuh")).read()
+    assert re.search(r"const float \*bias;.*\n\s*int bias_heads;", shared)
+    assert re.search(r"if \(a\.bias\) hipLaunchKernelGGL\(\(K::template get<VEC, GROUP, NF, TX, SEGRED, true, false>\(\)\)", shared)
+    assert re.search(r"else hipLaunchKernelGGL\(\(K::template get<VEC, GROUP, NF, TX, SEGRED, false, false>\(\)\)", shared)
+    for name, functor, kernel in (("agg_gatv2.hip", "Gatv2Kernel", "k_gatv2"), ("agg_dot.hip", "DotKernel", "k_dot_attn")):
         src = open(os.path.join(csrc, name)).read()
-        assert re.search(r"if \(a\.bias\) hipLaunchKernelGGL\(\(%s<VEC, GROUP, NF, TX, SEGRED, true>\)" % kernel, src)
-        assert re.search(r"else hipLaunchKernelGGL\(\(%s<VEC, GROUP, NF, TX, SEGRED, false>\)" % kernel, src)
+        assert re.search(r"struct %s \{[^}]*return &%s<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>;" % (functor, kernel), src)
+        assert "attn_launch_typed<%s, " % functor in src and "hipLaunchKernelGGL" not in src
 
 
 # --------------------------------------------------------------------------------------------------------------- Python-side refusals

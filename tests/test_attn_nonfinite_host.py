@@ -11,7 +11,7 @@ tests/test_nonfinite_host.py).  This file adds
   * an fp32 emulation of the kernels' online recurrence for one (row, head, column): batches of 2 and 4 edges, the chunks of a segment
     folded in ascending order, the segments merged in ascending order -- in the fixed form and, behind a flag, in the form before the fix,
     which is the regression's witness on the CPU: NaN where the first full batch, or a whole chunk, is masked;
-  * gatv2_geometry in Python and the proof that SHAPES reaches every instantiation of launch_gatv2_typed / launch_dot_typed;
+  * gatv2_geometry in Python and the proof that SHAPES reaches every instantiation of attn_launch_typed (both kernels);
   * the condition that keeps the class map independent of the kernel's order: the finite float64 scores of a (row, head) spread by less than
     60, so no fp32 weight or rescale factor underflows to 0 where float64's does not (exp(-60) = 8.8e-27)."""
 import functools
@@ -37,7 +37,7 @@ NINF = -np.inf
 SPREAD = 60.0
 SLOPE = 0.2
 
-# (heads, D): every instantiation of both launchers, fp32 and bf16 (test_the_shapes_reach_every_instantiation)
+# (heads, D): every instantiation of the shared launcher (both kernels), fp32 and bf16 (test_the_shapes_reach_every_instantiation)
 SHAPES = [(1, 8), (4, 16), (8, 16), (8, 32), (4, 128), (8, 128), (4, 3), (1, 100), (1, 200), (2, 301), (1, 1000)]
 
 # which edges of every row with edges are masked
@@ -87,24 +87,27 @@ def leading_half(n):
 
 
 def test_the_shapes_reach_every_instantiation():
-    want = {}
-    for name, launcher in (("agg_gatv2.hip", "gatv2"), ("agg_dot.hip", "dot")):
+    # the one switch pair (gatv2_shared.cuh: attn_launch_typed) ...
+    text = open(os.path.join(CSRC, "gatv2_shared.cuh")).read()
+    body = text[text.index("static int attn_launch_typed"):]
+    body = body[:body.index("\n}\n")]
+    inst = re.findall(r"(if constexpr \(VEC == 4\) )?return attn_launch_inst<K, (VEC|1), (\d+), (\d+), TX, (true|false)>", body)
+    assert len(inst) == 11
+    insts = {(int(g), int(nf), seg == "true", bool(only4)) for only4, _, g, nf, seg in inst}
+    # ... through which both kernels are launched, in both element types: neither file has instantiations of its own
+    for name, functor in (("agg_gatv2.hip", "Gatv2Kernel"), ("agg_dot.hip", "DotKernel")):
         text = open(os.path.join(CSRC, name)).read()
-        body = text[text.index("static int launch_%s_typed" % launcher):]
-        body = body[:body.index("\n}\n")]
-        inst = re.findall(r"(if constexpr \(VEC == 4\) )?return launch_%s_inst<(VEC|1), (\d+), (\d+), TX, (true|false)>" % launcher, body)
-        assert len(inst) == 11
-        want[launcher] = {(int(g), int(nf), seg == "true", bool(only4)) for only4, _, g, nf, seg in inst}
-    assert want["gatv2"] == want["dot"]
+        assert len(re.findall(r"return attn_launch_typed<%s, (?:8, __bf16|4, float)>\(a, g, stream, no_inst\);" % functor, text)) == 2
+        assert "attn_launch_inst<" not in text and not re.search(r"\bswitch\s*\(", text)
     seg = {(8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 4)}
-    assert {(g, nf) for g, nf, s, _ in want["dot"] if s} == seg and {nf for g, nf, s, _ in want["dot"] if not s} == {1, 2, 4, 10, 16}
-    assert {(g, nf) for g, nf, s, only4 in want["dot"] if only4} == {(64, 4)}     # fp32 only: bf16 has at most 128 16-byte lanes
+    assert {(g, nf) for g, nf, s, _ in insts if s} == seg and {nf for g, nf, s, _ in insts if not s} == {1, 2, 4, 10, 16}
+    assert {(g, nf) for g, nf, s, only4 in insts if only4} == {(64, 4)}     # fp32 only: bf16 has at most 128 16-byte lanes
     for esize in (4, 2):
         got = set()
         for H, D in SHAPES:
             g = geometry(H * D, H, esize)
             got.add((g["group"], g["nf"], g["segred"]))
-        expect = {(g, nf, s) for g, nf, s, only4 in want["dot"] if not (only4 and esize == 2)}
+        expect = {(g, nf, s) for g, nf, s, only4 in insts if not (only4 and esize == 2)}
         assert got == expect, (esize, sorted(expect - got))
     # both batches of the dot kernel, and both numbers of lane groups, occur
     assert {dot_batch(geometry(H * D, H, e)["nf"]) for H, D in SHAPES for e in (4, 2)} == {2, 4}

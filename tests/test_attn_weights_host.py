@@ -292,13 +292,18 @@ def test_header_declares_and_the_library_exports_the_weights_calls():
         assert got[:-2] == _lib.SIGNATURES[name.replace("_weights", "_bias")][1]
     for phrase in ("alpha[p, h] = expf(e_p - ms) / den", "stat[r, h, 0] = M, stat[r, h, 1] = den", "(-Inf, +0)", "no handle state is added"):
         assert phrase in text, phrase
-    # the kernels: the arm is chosen from the pointer in the two launchers, ahead of the two existing arms, and adds no case label
+    # the kernels: the arm is chosen from the pointer in the one launcher both kernels go through, ahead of the two existing arms, and adds no
+    # case label
     csrc = os.path.join(ROOT, "gnn_computing_amd", "csrc")
-    assert re.search(r"float \*alpha;.*\n\s*float \*stat;", open(os.path.join(csrc, "gatv2_shared.cuh")).read())
-    for name, kernel in (("agg_gatv2.hip", "k_gatv2"), ("agg_dot.hip", "k_dot_attn")):
+    shared = open(os.path.join(csrc, "gatv2_shared.cuh")).read()
+    assert re.search(r"float \*alpha;.*\n\s*float \*stat;", shared)
+    assert re.search(r"if \(a\.alpha\) hipLaunchKernelGGL\(\(K::template get<VEC, GROUP, NF, TX, SEGRED, true, true>\(\)\)", shared)
+    arms = re.findall(r"(if \(a\.alpha\)|else if \(a\.bias\)|else) hipLaunchKernelGGL\(\(K::template get<", shared)
+    assert arms == ["if (a.alpha)", "else if (a.bias)", "else"]                       # none, BIAS, BIAS + WEIGHTS: no full product
+    for name, functor, kernel in (("agg_gatv2.hip", "Gatv2Kernel", "k_gatv2"), ("agg_dot.hip", "DotKernel", "k_dot_attn")):
         src = open(os.path.join(csrc, name)).read()
-        assert re.search(r"if \(a\.alpha\) hipLaunchKernelGGL\(\(%s<VEC, GROUP, NF, TX, SEGRED, true, true>\)" % kernel, src)
-        assert len(re.findall(r"hipLaunchKernelGGL\(\(%s<" % kernel, src)) == 3      # none, BIAS, BIAS + WEIGHTS: no full product
+        assert re.search(r"struct %s \{[^}]*return &%s<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>;" % (functor, kernel), src)
+        assert "attn_launch_typed<%s, " % functor in src and "hipLaunchKernelGGL" not in src
     assert "k_attn_finish" in open(os.path.join(csrc, "aux_kernels.hip")).read()
 
 

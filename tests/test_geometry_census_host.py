@@ -1,9 +1,10 @@
 """CPU: the lane-geometry census (tests/geometry_census.py) against itself and against the sources.
 
 1. every table entry: the Python restatement of its picker gives the tuple the entry was written for;
-2. the `case` labels of DISPATCH_GEOM_CASES / DISPATCH_GEOM_16BIT (csrc/kernel_util.cuh) and of the two switches each in
-   launch_gatv2_typed (csrc/agg_gatv2.hip) and launch_dot_typed (csrc/agg_dot.hip), read out of the sources, are exactly the labels
-   the tables reach: a case added to (or taken out of) a switch fails here until the census has (or drops) a shape for it;
+2. the `case` labels of DISPATCH_GEOM_CASES / DISPATCH_GEOM_16BIT (csrc/kernel_util.cuh) and of the two switches of attn_launch_typed
+   (csrc/gatv2_shared.cuh), through which both attention kernels (csrc/agg_gatv2.hip, csrc/agg_dot.hip) are launched, read out of the
+   sources, are exactly the labels the tables reach: a case added to (or taken out of) a switch fails here until the census has (or
+   drops) a shape for it;
 3. the restatements at the edges of their domain."""
 import os
 import re
@@ -116,9 +117,9 @@ def test_dispatch_geom_labels_are_the_ones_the_tables_reach():
         assert int(lab) == int(vec) * 100 + int(group)
 
 
-@pytest.mark.parametrize("file,function", [("agg_gatv2.hip", "launch_gatv2_typed"), ("agg_dot.hip", "launch_dot_typed")])
-def test_attention_switch_labels_are_the_ones_the_table_reaches(file, function):
-    switches = function_switches(source(file), function)
+@pytest.mark.parametrize("file,functor,kernel", [("agg_gatv2.hip", "Gatv2Kernel", "k_gatv2"), ("agg_dot.hip", "DotKernel", "k_dot_attn")])
+def test_attention_switch_labels_are_the_ones_the_table_reaches(file, functor, kernel):
+    switches = function_switches(source("gatv2_shared.cuh"), "attn_launch_typed")
     assert len(switches) == 2
     seg, gen = (case_labels(s) for s in switches)
     assert switches[0].startswith("g.group * 10 + g.nf") and switches[1].startswith("g.nf")
@@ -130,10 +131,16 @@ def test_attention_switch_labels_are_the_ones_the_table_reaches(file, function):
     assert re.search(r"case 644:\s*if constexpr \(VEC == 4\)", switches[0])
     assert seg16 == set(seg) - {644}
     # group * 10 + nf, as instantiated
-    for lab, group, nf in re.findall(r"case (\d+):\s*(?:if constexpr \(VEC == 4\) )?return launch_\w+_inst<VEC, (\d+), (\d+), TX, true>", switches[0]):
+    for lab, group, nf in re.findall(r"case (\d+):\s*(?:if constexpr \(VEC == 4\) )?return attn_launch_inst<K, VEC, (\d+), (\d+), TX, true>", switches[0]):
         assert int(lab) == int(group) * 10 + int(nf)
-    for lab, nf in re.findall(r"case (\d+):\s*return launch_\w+_inst<1, 64, (\d+), TX, false>", switches[1]):
+    for lab, nf in re.findall(r"case (\d+):\s*return attn_launch_inst<K, 1, 64, (\d+), TX, false>", switches[1]):
         assert int(lab) == int(nf)
+    # that switch is the only one: the kernel's file has no switch and no label of its own, names its kernel for the shared launcher and
+    # goes through attn_launch_typed once per element type
+    text = source(file)
+    assert not re.search(r"\bswitch\s*\(", text) and case_labels(text) == []
+    assert re.search(r"struct %s \{[^}]*return &%s<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>;" % (functor, kernel), text)
+    assert re.findall(r"return attn_launch_typed<%s, (\d), (\w+)>\(a, g, stream, no_inst\);" % functor, text) == [("8", "__bf16"), ("4", "float")]
 
 
 def test_the_label_readers_see_an_added_and_a_removed_case():
