@@ -10,7 +10,9 @@
 //   starts every NG positions -> prefix sum = group ids -> scatter ptr_s / target -> row -> groups lists by a stable sort of the
 //   group ids by row -> flagged ids.  The sort and the scans are prims.cuh (hand-written, wave64).
 // Only per-GROUP arrays (a few MB) come to the host: the span cut is a greedy walk and the schedule queries read them.
-// Results are identical to the host builders' (tests/test_gpu_blocked.py compares both with the oracle's restatement).
+// Results are identical to the host builders' (tests/test_gpu_blocked.py compares both with the oracle's restatement on hub graphs;
+// tests/test_gpu_plan_census.py does it at every size where a scan, the reduction, a sort or a guard here changes passes or sides:
+// DESIGN.md "Plan-builder switch points").
 #include <algorithm>
 
 #include "devbuf.h"
