@@ -28,7 +28,8 @@ class Model:
     """The aggregators, weights and layer functions of Figure7/our.py for one graph (ptrs, idxs: int32 device CSR)."""
 
     def __init__(self, ptrs, idxs, neighbor_num=32, sched=1, fused_relu=False, dense=torch.mm, seed=123, dtype=torch.float32,
-                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False, transformer=False, edge_bias=False):
+                 stable_softmax=False, fused_nn=False, fused_project=False, heads=1, gatv2=False, transformer=False, edge_bias=False,
+                 edge_dim=0):
         dev = ptrs.device
         torch.manual_seed(seed)                               # our.py:76
         self.num_v, self.num_e = ptrs.numel() - 1, idxs.numel()
@@ -91,6 +92,16 @@ class Model:
             deg = (ptrs[1:] - ptrs[:-1]).to(torch.float64)
             bucket = (torch.frexp(1.0 + deg[idxs.long()])[1] - 1).clamp(max=7).long()   # floor(log2(x)), exact: x = m * 2^e, m in [0.5, 1)
             self.edge_bias = self.bias_table.t()[bucket].contiguous()
+        # edge_dim (--edge-dim K, the two attention models): a feature vector per edge.  ONE seeded [num_e, K] attribute tensor and a weight
+        # [K, DIMS[k + 1]] per layer (a generator of their own again); layer k's edge rows ef = attr . We[k] enter the score (and, for the
+        # transformer, the summed value) through edge= of run_v2 / run_dot -- PyG's GATv2Conv / TransformerConv(edge_dim=K)
+        self.edge_dim, self.edge_attr, self.w_edge = int(edge_dim), None, None
+        if self.edge_dim:
+            if not (gatv2 or transformer):
+                raise ValueError("edge_dim belongs to the attention models our_GATv2 and our_Transformer")
+            gen = torch.Generator().manual_seed(seed + 2)
+            self.edge_attr = torch.randn(self.num_e, self.edge_dim, generator=gen).to(dev).to(dtype)
+            self.w_edge = [(torch.randn(self.edge_dim, DIMS[k + 1], generator=gen) / self.edge_dim ** 0.5).to(dev).to(dtype) for k in range(3)]
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -145,19 +156,26 @@ class Model:
                                    att=att.clone(), out=out.clone(), path=gnc.last_project_path()))
         return out
 
+    def edge_rows(self, k):
+        """layer k's per-edge feature rows [num_e, DIMS[k + 1]] (None without --edge-dim)"""
+        return gnc.matmul_NN(self.edge_attr, self.w_edge[k]) if self.edge_dim else None
+
     def gatv2_layer(self, feat, out, k):
         feat2 = self.dense(feat, self.weights[k])
-        self.at_gat.run_v2(feat2, feat2, self.a_v2[k], out, heads=self.heads, bias=self.edge_bias)
+        ef = self.edge_rows(k)
+        self.at_gat.run_v2(feat2, feat2, self.a_v2[k], out, heads=self.heads, bias=self.edge_bias, edge=ef)
         if self.trace is not None:
-            self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, bias=self.edge_bias, out=out.clone()))
+            self.trace.append(dict(feat=feat, w=self.weights[k], a=self.a_v2[k], heads=self.heads, feat2=feat2, bias=self.edge_bias, ef=ef,
+                                   out=out.clone()))
         return out
 
     def transformer_layer(self, feat, out, k):
         n = DIMS[k + 1]
         qkv = self.dense(feat, self.w_qkv[k])
-        self.at_gat.run_dot(qkv[:, :n], qkv[:, n:2 * n], qkv[:, 2 * n:], out, heads=self.heads, bias=self.edge_bias)
+        ef = self.edge_rows(k)
+        self.at_gat.run_dot(qkv[:, :n], qkv[:, n:2 * n], qkv[:, 2 * n:], out, heads=self.heads, bias=self.edge_bias, edge=ef)
         if self.trace is not None:
-            self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, bias=self.edge_bias, out=out.clone()))
+            self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, bias=self.edge_bias, ef=ef, out=out.clone()))
         return out
 
     def forward(self, model="our_GCN"):
@@ -215,12 +233,17 @@ def main():
     ap.add_argument("--edge-bias", action="store_true",
                     help="our_GATv2 / our_Transformer: add a per-edge, per-head score bias (run_v2 / run_dot bias=): a seeded [heads, 8] table "
                          "looked up once by min(7, floor(log2(1 + degree of the edge's source)))")
+    ap.add_argument("--edge-dim", type=int, default=0,
+                    help="our_GATv2 / our_Transformer: a K-element attribute vector per edge (seeded), projected per layer to the layer's width "
+                         "and passed as edge= of run_v2 / run_dot (GATv2Conv / TransformerConv(edge_dim=K)); 0: off")
     ap.add_argument("--hip-graph", action="store_true",
                     help="capture one forward in a HIP graph and replay it (the 9-12 launches of a forward are short "
                          "enough on the arxiv-sized graph for launch gaps to show)")
     args = ap.parse_args()
     if args.edge_bias and args.model not in ("our_GATv2", "our_Transformer"):
         ap.error("--edge-bias needs --model our_GATv2 or our_Transformer")
+    if args.edge_dim < 0 or (args.edge_dim and args.model not in ("our_GATv2", "our_Transformer")):
+        ap.error("--edge-dim needs K >= 0 and --model our_GATv2 or our_Transformer")
     dev = torch.device("cuda", args.gpu)
 
     if args.datadir:
@@ -230,7 +253,8 @@ def main():
     m = Model(ptrs, idxs, args.neighbor_num, "balanced" if args.balanced else 1, args.fused_relu,
               gnc.matmul_NN if args.dense == "library" else torch.mm, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
               stable_softmax=args.stable_softmax, fused_nn=args.fused_nn, fused_project=args.fused_project or (args.heads != 1 and args.model not in ("our_GATv2", "our_Transformer")), heads=args.heads,
-              gatv2=args.model == "our_GATv2", transformer=args.model == "our_Transformer", edge_bias=args.edge_bias)
+              gatv2=args.model == "our_GATv2", transformer=args.model == "our_Transformer", edge_bias=args.edge_bias,
+              edge_dim=args.edge_dim)
     num_v, num_e = m.num_v, m.num_e
 
     def forward():
@@ -261,6 +285,8 @@ def main():
     if result is not None:
         assert torch.equal(result, y), "graph replay differs from the eager forward"
     extra = {"edge_bias": True} if args.edge_bias else {}
+    if args.edge_dim:
+        extra["edge_dim"] = args.edge_dim
     print(json.dumps({**extra, "model": args.model, "dataset": args.dataset, "num_v": num_v, "num_e": num_e,
                       "seconds_per_forward": dt, "hip_graph": bool(args.hip_graph), "fused_relu": bool(args.fused_relu), "fused_nn": bool(args.fused_nn), "fused_project": bool(m.fused_project), "heads": args.heads, "balanced": bool(args.balanced), "dense": args.dense, "dtype": args.dtype, "stable_softmax": bool(args.stable_softmax), "finite": bool(torch.isfinite(y).all().item())}))
 

@@ -88,6 +88,10 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "gnnagg_dot_attn_run_weights": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_float,
                                             c_void_p, c_int, c_void_p, c_void_p]),
+    "gnnagg_gatv2_run_edge": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_float,
+                                      c_void_p, c_int, c_void_p, c_void_p]),
+    "gnnagg_dot_attn_run_edge": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_int,
+                                         c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "gnnagg_gat_run_part": (c_int,[c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "gnnagg_gat_run_att": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_float]),
     "gnnagg_gat_run_u_add_v": (c_int, [c_int64, c_void_p, c_void_p]),

@@ -106,6 +106,27 @@ def _bias_heads(bias, num_e, heads, like, who):
     return 1 if bias.dim() == 1 else int(shape[1])
 
 
+def _edge_rows(edge, num_e, feat, like, who):
+    """(pointer, pitch in elements) of the per-edge feature rows of run_v2 / run_dot: a [num_e, F] tensor of `like`'s dtype on its device,
+    unit column stride, rows stride(0) >= F elements apart (a column view of a wider tensor is taken as it is); raises before any device
+    work"""
+    if not isinstance(edge, torch.Tensor):
+        raise TypeError("%s: edge must be a torch.Tensor or None" % who)
+    if edge.dtype != like.dtype:
+        raise TypeError("%s: edge must have the operands' dtype %s, got %s" % (who, like.dtype, edge.dtype))
+    if edge.dim() != 2:
+        raise ValueError("%s: edge must be [num_e = %d, F = %d], got %s" % (who, num_e, feat, tuple(edge.shape)))
+    if tuple(edge.shape) != (num_e, feat):
+        raise ValueError("%s: edge must be [num_e = %d, F = %d], got %s" % (who, num_e, feat, tuple(edge.shape)))
+    if feat != 1 and edge.stride(1) != 1:
+        raise ValueError("%s: edge must have stride(1) == 1 (a column view of a row-major tensor), got strides %s" % (who, tuple(edge.stride())))
+    if num_e > 1 and edge.stride(0) < feat:
+        raise ValueError("%s: edge: row pitch stride(0) = %d is below F = %d" % (who, edge.stride(0), feat))
+    if edge.device != like.device:
+        raise ValueError("%s: edge is on %s, the operands on %s" % (who, edge.device, like.device))
+    return ctypes.c_void_p(edge.data_ptr()), (int(edge.stride(0)) if num_e > 1 else feat)
+
+
 def _weights_out(weights, stats, num_v, num_e, heads, like, who):
     """the two outputs of the weights form of run_v2 / run_dot: weights, a contiguous float32 tensor of num_e * heads elements on `like`'s
     device ([num_e, heads], or [num_e] at one head), and stats, contiguous float32 [V, heads, 2] (allocated here when None).  Returns
@@ -443,7 +464,7 @@ class Aggregator_GAT(Aggregator):
     GATV2_THRESHOLDS = (4, 8, 16, 32, 64, 128, 512)
     GATV2_MAX_FEAT = 1024
 
-    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2, bias=None, weights=None, stats=None):
+    def run_v2(self, xs, xd, a, vout, heads=1, slope=0.2, bias=None, weights=None, stats=None, edge=None):
         """gnnagg_gatv2_run (extension): GATv2 attention, e_ij = a[h] . leaky(xd[i] + xs[j]) per head, max-shifted edge softmax over each row's
         edges and the weighted sum of the xs rows, in one call.  xs [n_src, F], xd [>= V, F]: both float32 or both bfloat16 (xd may be xs);
         a: float32, heads * D elements ([heads, D]); vout [>= V, F] float32 or bfloat16 (one rounding of the fp32 result).  Rows without edges
@@ -452,7 +473,10 @@ class Aggregator_GAT(Aggregator):
         weights (gnnagg_gatv2_run_weights): a contiguous float32 [num_e, heads] tensor ([num_e] at one head) the call fills with the attention
         weight of every (edge position, head); stats: contiguous float32 [V, heads, 2], filled with every (row, head)'s (score maximum, softmax
         denominator) -- allocated here when weights is given and stats is None, and returned; give both to keep a captured call free of
-        allocations.  stats without weights is a ValueError; neither is the call without them.  Everything is checked here before the library
+        allocations.  stats without weights is a ValueError; neither is the call without them.
+        edge (gnnagg_gatv2_run_edge): a feature row per edge, [num_e, F] of xs's dtype on its device, stride(1) == 1 and stride(0) >= F (a
+        column view serves), indexed by the edge's position in the CSR: the score becomes a[h] . leaky(xd[i] + (xs[j] + edge[p])); the summed
+        row stays xs[j].  None is the call without it, through the entry points above.  Everything is checked here before the library
         is reached."""
         xt, yt = _feat_dtype(xs, "xs"), _feat_dtype(vout, "vout")
         if _feat_dtype(xd, "xd") != xt:
@@ -473,7 +497,15 @@ class Aggregator_GAT(Aggregator):
             raise ValueError("vout must hold at least V*F elements")
         bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, xs, "run_v2")
         stats = _weights_out(weights, stats, self.num_v, self.num_e, heads, xs, "run_v2")
+        ef = None if edge is None else _edge_rows(edge, self.num_e, feat, xs, "run_v2")
         self._use_current_stream()
+        if ef is not None:
+            check(lib().gnnagg_gatv2_run_edge(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt,
+                                              _dev_ptr(a, torch.float32, "a"), ef[0], ef[1], _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
+                                              ctypes.c_float(slope), _dev_ptr(bias, torch.float32, "bias"), bias_heads or 1,
+                                              None if weights is None else _dev_ptr(weights if self.num_e else stats, torch.float32, "weights"),
+                                              _dev_ptr(stats, torch.float32, "stats")))
+            return stats
         if weights is not None:
             check(lib().gnnagg_gatv2_run_weights(self._h, _dev_ptr(xs, xs.dtype, "xs"), _dev_ptr(xd, xd.dtype, "xd"), xt,
                                                  _dev_ptr(a, torch.float32, "a"), _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
@@ -489,7 +521,7 @@ class Aggregator_GAT(Aggregator):
                                               _dev_ptr(a, torch.float32, "a"), _dev_ptr(vout, vout.dtype, "vout"), yt, feat, heads,
                                               ctypes.c_float(slope), _dev_ptr(bias, torch.float32, "bias"), bias_heads))
 
-    def run_dot(self, q, k, v, vout, heads=1, scale=None, bias=None, weights=None, stats=None):
+    def run_dot(self, q, k, v, vout, heads=1, scale=None, bias=None, weights=None, stats=None, edge=None):
         """gnnagg_dot_attn_run (extension): scaled dot-product attention over the edges, e_ij = scale * q[i] . k[j] per head (D = F / heads
         columns), max-shifted edge softmax over each row's edges and the weighted sum of the v rows, in one call.  q [>= V, F], k and v
         [n_src, F]: all float32 or all bfloat16, row-pitched views allowed (stride(1) == 1; k and v share stride(0)) -- the column views
@@ -497,7 +529,9 @@ class Aggregator_GAT(Aggregator):
         (one rounding of the fp32 result), contiguous.  scale=None is 1 / sqrt(D).  Rows without edges are +0.  bias
         (gnnagg_dot_attn_run_bias): as run_v2's -- float32 [num_e], [num_e, 1] or [num_e, heads], added to the score; -inf masks the edge;
         None is the call without a bias.  weights / stats (gnnagg_dot_attn_run_weights): as run_v2's -- float32 [num_e, heads] filled with
-        the attention weights and float32 [V, heads, 2] with every (row, head)'s (maximum, denominator), which is returned.  Everything is
+        the attention weights and float32 [V, heads, 2] with every (row, head)'s (maximum, denominator), which is returned.
+        edge (gnnagg_dot_attn_run_edge): as run_v2's -- [num_e, F] of q's dtype, row-pitched views allowed, indexed by the edge's position
+        in the CSR: the edge scores k[j] + edge[p] and sums v[j] + edge[p].  None is the call without it.  Everything is
         checked here before the library is reached."""
         xt, yt = _feat_dtype(q, "q"), _feat_dtype(vout, "vout")
         if _feat_dtype(k, "k") != xt or _feat_dtype(v, "v") != xt:
@@ -530,9 +564,16 @@ class Aggregator_GAT(Aggregator):
                 raise ValueError("%s: row pitch stride(0) = %d is below F = %d" % (name, t.stride(0), feat))
         bias_heads = None if bias is None else _bias_heads(bias, self.num_e, heads, q, "run_dot")
         stats = _weights_out(weights, stats, self.num_v, self.num_e, heads, q, "run_dot")
+        ef = None if edge is None else _edge_rows(edge, self.num_e, feat, q, "run_dot")
         self._use_current_stream()
         (pq, q_pitch), (pk, kv_pitch), (pv, _) = _dev_ptr_rows(q, q.dtype, "q"), _dev_ptr_rows(k, k.dtype, "k"), _dev_ptr_rows(v, v.dtype, "v")
         py = _dev_ptr(vout, vout.dtype, "vout")
+        if ef is not None:
+            check(lib().gnnagg_dot_attn_run_edge(self._h, pq, q_pitch, pk, pv, kv_pitch, ef[0], ef[1], xt, py, yt, feat, heads,
+                                                 ctypes.c_float(scale), _dev_ptr(bias, torch.float32, "bias"), bias_heads or 1,
+                                                 None if weights is None else _dev_ptr(weights if self.num_e else stats, torch.float32, "weights"),
+                                                 _dev_ptr(stats, torch.float32, "stats")))
+            return stats
         if weights is not None:
             check(lib().gnnagg_dot_attn_run_weights(self._h, pq, q_pitch, pk, pv, kv_pitch, xt, py, yt, feat, heads, ctypes.c_float(scale),
                                                     _dev_ptr(bias, torch.float32, "bias"), bias_heads or 1,
@@ -766,14 +807,14 @@ def gat_run(at, feat, att, outfeat, blocksize, scheduled, stable=False):
     at.run_with_feat(feat, att, outfeat, blocksize, scheduled, int(feat.shape[1]), stable=stable)
 
 
-def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2, bias=None, weights=None, stats=None):
+def gatv2_run(at, xs, xd, a, out, heads=1, slope=0.2, bias=None, weights=None, stats=None, edge=None):
     """Aggregator_GAT.run_v2 as a flat function (extension: the reference has no GATv2)."""
-    return at.run_v2(xs, xd, a, out, heads=heads, slope=slope, bias=bias, weights=weights, stats=stats)
+    return at.run_v2(xs, xd, a, out, heads=heads, slope=slope, bias=bias, weights=weights, stats=stats, edge=edge)
 
 
-def dot_attn_run(at, q, k, v, out, heads=1, scale=None, bias=None, weights=None, stats=None):
+def dot_attn_run(at, q, k, v, out, heads=1, scale=None, bias=None, weights=None, stats=None, edge=None):
     """Aggregator_GAT.run_dot as a flat function (extension: the reference has the unnormalised score only, aggr_sddmm.h)."""
-    return at.run_dot(q, k, v, out, heads=heads, scale=scale, bias=bias, weights=weights, stats=stats)
+    return at.run_dot(q, k, v, out, heads=heads, scale=scale, bias=bias, weights=weights, stats=stats, edge=edge)
 
 
 def gat_schedule(at, neighbor_num):

@@ -17,6 +17,10 @@
 //
 // Score bias (gnnagg_dot_attn_run_bias): the BIAS arm of dot_walk / k_dot_attn, as in agg_gatv2.hip -- one fp32 add to the finished score.
 // Weights out (gnnagg_dot_attn_run_weights): the WEIGHTS arm, as in agg_gatv2.hip -- raw scores to alpha, (maximum, denominator) to stat.
+// Edge features (gnnagg_dot_attn_run_edge; k_dot_attn_edge, the EDGE arm of dot_walk / k_dot_attn): a row ef[p] per edge POSITION, added to
+// the gathered k row where it is scored and to the gathered v row where it is summed -- one fp32 add each, at the point of use; the rows
+// of a batch are consecutive and read once, packed, behind the gathers.  The batch stays dot_batch (the edge call owes the bits of
+// k_dot_attn on the expanded graph, and the batches are part of the arithmetic).
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
@@ -37,9 +41,15 @@ template <int NF>
 constexpr int dot_batch() { return NF >= GNNAGG_DOT_WIDE_NF ? GNNAGG_DOT_WIDE_BATCH : kGatv2Batch; }
 static_assert(kGatv2Batch % dot_batch<GNNAGG_DOT_WIDE_NF>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
 
+struct DotEdgeArgs : DotArgs {
+    const void *ef;   // [num_e, feat] elements of the operands' type, row p at p * ef_pitch
+    long long ef_pitch;
+};
+
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
-__device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int lane, const float (&qv)[NF][VEC], const int (&hf)[NF],
+// (EDGE keeps dot_batch: the batches are part of the arithmetic, and the edge call owes the bits of k_dot_attn on the expanded graph)
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS, bool EDGE = false, typename ARGS = DotArgs>
+__device__ __forceinline__ void dot_walk(const ARGS &a, int beg, int end, int lane, const float (&qv)[NF][VEC], const int (&hf)[NF],
                                          float (&m)[NF], float (&den)[NF], float (&acc)[NF][VEC])
 {
     constexpr int U = dot_batch<NF>();
@@ -48,6 +58,12 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
     const TX *__restrict__ kp = static_cast<const TX *>(a.xs) + lane * VEC;
     const TX *__restrict__ vp = static_cast<const TX *>(a.v) + lane * VEC;
     const int *__restrict__ idx = a.idx;
+    [[maybe_unused]] const TX *__restrict__ ef = nullptr;
+    [[maybe_unused]] size_t ef_pitch = 0;
+    if constexpr (EDGE) {
+        ef = static_cast<const TX *>(a.ef) + lane * VEC;
+        ef_pitch = (size_t)a.ef_pitch;
+    }
     // BIAS, as in gatv2_walk: per (edge, head) loaded with the batch's rows, per edge (bias_heads == 1) read as a window beside the ids
     // WEIGHTS (BIAS arm only, one instantiation for both): a null bias runs as a per-edge bias of +0.0 that is never loaded -- the unbiased
     // bits (gnnagg.h "no bias").  has_b is a constant without WEIGHTS: the BIAS arm alone is the kernel it was.
@@ -72,6 +88,7 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
             Pack<VEC, TX> kx[U][NF], vx[U][NF];
             float e[U][NF];
             [[maybe_unused]] float bv[U][NF];
+            [[maybe_unused]] Pack<VEC, TX> ev[EDGE ? U : 1][EDGE ? NF : 1];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
 #pragma unroll
@@ -89,6 +106,17 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                     for (int f = 0; f < NF; ++f)
                         if ((f * GROUP + lane) * VEC < F) vx[u][f] = gatv2_load<VEC, TX>(vp + (size_t)s[u] * pitch + f * GROUP * VEC, a.x_aligned);
                 }
+            // the batch's edge rows, consecutive in memory and read once: behind the gathers, kept packed until the adds
+            if constexpr (EDGE) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < n) {
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            if ((f * GROUP + lane) * VEC < F)
+                                ev[u][f] = gatv2_load_once<VEC, TX>(ef + (size_t)(cb + j + u) * ef_pitch + f * GROUP * VEC, a.x_aligned);
+                    }
+            }
             // the batch's biases, one per (edge, head): in flight with the rows (one per edge: already in the window)
             if constexpr (BIAS) {
                 if (!per_edge) {
@@ -105,7 +133,10 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                     float p = 0.0f;
                     if (j + u < n && (f * GROUP + lane) * VEC < F) {
 #pragma unroll
-                        for (int k = 0; k < VEC; ++k) p = __builtin_fmaf(qv[f][k], kx[u][f].at(k), p);
+                        for (int k = 0; k < VEC; ++k) {
+                            if constexpr (EDGE) p = __builtin_fmaf(qv[f][k], kx[u][f].at(k) + ev[u][f].at(k), p);   // k' = k + ef: one fp32 add
+                            else p = __builtin_fmaf(qv[f][k], kx[u][f].at(k), p);
+                        }
                     }
                     e[u][f] = p;
                 }
@@ -196,7 +227,10 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
                         const float w = expf(e[u][f] - ms);
                         den[f] += w;
 #pragma unroll
-                        for (int k = 0; k < VEC; ++k) acc[f][k] = __builtin_fmaf(vx[u][f].at(k), w, acc[f][k]);
+                        for (int k = 0; k < VEC; ++k) {
+                            if constexpr (EDGE) acc[f][k] = __builtin_fmaf(vx[u][f].at(k) + ev[u][f].at(k), w, acc[f][k]);   // v' = v + ef
+                            else acc[f][k] = __builtin_fmaf(vx[u][f].at(k), w, acc[f][k]);
+                        }
                     }
             }
         }
@@ -206,8 +240,9 @@ __device__ __forceinline__ void dot_walk(const DotArgs &a, int beg, int end, int
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false>
-__global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
+// (k_dot_attn: EDGE = false; k_dot_attn_edge: EDGE = true)
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false, bool EDGE = false, typename ARGS = DotArgs>
+__global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const ARGS a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     __shared__ float s_m[BLOCK * NF], s_den[BLOCK * NF], s_acc[BLOCK * NF * VEC];
@@ -249,7 +284,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_dot_attn(const DotArgs a)
             qv[f][k] = ok && beg < end ? qr.at(k) * a.scale : 0.0f;   // the scale goes on q, once per row
         }
     }
-    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>(a, beg, end, lane, qv, hf, m, den, acc);
+    if (beg < end) dot_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS, EDGE, ARGS>(a, beg, end, lane, qv, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -308,6 +343,16 @@ struct DotKernel {   // names the kernel for the launch switches (gatv2_shared.c
     static constexpr auto get() { return &k_dot_attn<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
 };
 
+// k_dot_attn_edge<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>: the kernel with the EDGE arm, a sibling instantiation of the same template (a
+// wrapper around a shared body would reorder the instructions of k_dot_attn; as a defaulted parameter it leaves them as they were)
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+constexpr auto k_dot_attn_edge = &k_dot_attn<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS, true, DotEdgeArgs>;
+
+struct DotEdgeKernel {
+    template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+    static constexpr auto get() { return k_dot_attn_edge<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
+};
+
 // ------------------------------------------------------------------------------------------------ launch
 int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
 {
@@ -316,6 +361,19 @@ int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
     Gatv2Geom g;
     if (!gatv2_geometry(L.feat, L.heads, esize, g)) return fail(GNNAGG_ERR_ARG, "internal: dot-product attention launch outside the kernel's shapes");
     if (L.V <= 0) return GNNAGG_OK;
+    constexpr const char *no_inst = "internal: dot-product attention lane geometry without an instantiation";
+    if (L.ef) {   // the edge call: the alignment flag also covers the ef base and its row pitch
+        DotEdgeArgs a;
+        attn_fill_args(a, L, g);
+        a.xs = L.k; a.xd = L.q; a.a = nullptr;
+        a.x_aligned = ((uintptr_t)L.q % 16 == 0 && (uintptr_t)L.k % 16 == 0 && (uintptr_t)L.v % 16 == 0 && (uintptr_t)L.ef % 16 == 0 &&
+                       (L.q_pitch * esize) % 16 == 0 && (L.kv_pitch * esize) % 16 == 0 && (L.ef_pitch * esize) % 16 == 0) ? 1 : 0;
+        a.slope = 0.0f;
+        a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
+        a.ef = L.ef; a.ef_pitch = L.ef_pitch;
+        if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<DotEdgeKernel, 8, __bf16>(a, g, stream, no_inst);
+        return attn_launch_typed<DotEdgeKernel, 4, float>(a, g, stream, no_inst);
+    }
     DotArgs a;
     attn_fill_args(a, L, g);
     a.xs = L.k; a.xd = L.q; a.a = nullptr;
@@ -324,7 +382,6 @@ int launch_dot_attn(const DotAttnLaunch &L, void *stream_v)
                    (L.kv_pitch * esize) % 16 == 0) ? 1 : 0;
     a.slope = 0.0f;
     a.v = L.v; a.q_pitch = L.q_pitch; a.kv_pitch = L.kv_pitch; a.scale = L.scale;
-    constexpr const char *no_inst = "internal: dot-product attention lane geometry without an instantiation";
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<DotKernel, 8, __bf16>(a, g, stream, no_inst);
     return attn_launch_typed<DotKernel, 4, float>(a, g, stream, no_inst);
 }

@@ -31,13 +31,23 @@
 // score of every (edge, head) is stored raw to alpha[p, h] by the lane and fragment that start the head, and the row's final (maximum,
 // denominator) to stat[row, h] from wherever the row is finished -- the short-row store, group 0 after the LDS fold, k_gatv2_merge.
 // launch_attn_finish (aux_kernels.hip), behind this launch on the same stream, makes weights of the scores.  y is computed as without.
+//
+// Edge features (gnnagg_gatv2_run_edge; k_gatv2_edge, the EDGE arm of gatv2_walk / k_gatv2): a row ef[p] of F elements per edge POSITION,
+// added to the gathered row inside the score only -- z = xd + (xs[j] + ef[p]), the inner add first -- while the summed row stays xs[j].
+// The rows of a batch are consecutive (p = cb + j + u): a lane reads its fragments of them with the loads of the gather, behind the gathers,
+// and keeps them packed (TX) until the add.  EDGE = false is k_gatv2, instruction for instruction.
 #include "gatv2_shared.cuh"
 
 namespace gnnagg {
 
+struct Gatv2EdgeArgs : Gatv2Args {   // what the merge and the store read is the base
+    const void *ef;                  // [num_e, feat] elements of the operands' type, row p at p * ef_pitch
+    long long ef_pitch;
+};
+
 // The online-softmax walk of one lane group over edges [beg, end) of its row, into (m, den, acc).  Control flow is uniform over the group.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
-__device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS, bool EDGE = false, typename ARGS = Gatv2Args>
+__device__ __forceinline__ void gatv2_walk(const ARGS &a, int beg, int end, int lane, const float (&xdv)[NF][VEC],
                                            const float (&av)[NF][VEC], const int (&hf)[NF], float (&m)[NF], float (&den)[NF],
                                            float (&acc)[NF][VEC])
 {
@@ -45,6 +55,12 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
     const int F = a.feat;
     const TX *__restrict__ xs = static_cast<const TX *>(a.xs) + lane * VEC;
     const int *__restrict__ idx = a.idx;
+    [[maybe_unused]] const TX *__restrict__ ef = nullptr;
+    [[maybe_unused]] size_t ef_pitch = 0;
+    if constexpr (EDGE) {
+        ef = static_cast<const TX *>(a.ef) + lane * VEC;
+        ef_pitch = (size_t)a.ef_pitch;
+    }
     // BIAS.  bias_heads == heads: the value of (edge, hf[f]) is loaded per (edge, fragment) with the batch's rows.
     // bias_heads == 1: one value per edge, so the group reads a window of GROUP values beside its ids and shuffles them out (my_b, nx_b).
     // WEIGHTS (BIAS arm only, one instantiation for both): a null bias runs as a per-edge bias of +0.0 that is never loaded -- the unbiased
@@ -70,6 +86,7 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
             Pack<VEC, TX> xv[U][NF];
             float e[U][NF];
             [[maybe_unused]] float bv[U][NF];
+            [[maybe_unused]] Pack<VEC, TX> ev[EDGE ? U : 1][EDGE ? NF : 1];
 #pragma unroll
             for (int u = 0; u < U; ++u) s[u] = __shfl(my_s, j + u, GROUP);
 #pragma unroll
@@ -79,6 +96,17 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     for (int f = 0; f < NF; ++f)
                         if ((f * GROUP + lane) * VEC < F) xv[u][f] = gatv2_load<VEC, TX>(xs + (size_t)s[u] * F + f * GROUP * VEC, a.x_aligned);
                 }
+            // the batch's edge rows, consecutive in memory and read once: behind the gathers, kept packed until the add
+            if constexpr (EDGE) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < n) {
+#pragma unroll
+                        for (int f = 0; f < NF; ++f)
+                            if ((f * GROUP + lane) * VEC < F)
+                                ev[u][f] = gatv2_load_once<VEC, TX>(ef + (size_t)(cb + j + u) * ef_pitch + f * GROUP * VEC, a.x_aligned);
+                    }
+            }
             // the batch's biases, one per (edge, head): in flight with the rows (one per edge: already in the window)
             if constexpr (BIAS) {
                 if (!per_edge) {
@@ -96,7 +124,9 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
                     if (j + u < n && (f * GROUP + lane) * VEC < F) {
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) {
-                            const float z = xdv[f][k] + xv[u][f].at(k);
+                            float xe = xv[u][f].at(k);
+                            if constexpr (EDGE) xe += ev[u][f].at(k);   // (the inner add first; the summed row below is xv alone)
+                            const float z = xdv[f][k] + xe;
                             const float zs = z * a.slope;
                             p = __builtin_fmaf(av[f][k], z > zs ? z : zs, p);
                         }
@@ -200,8 +230,9 @@ __device__ __forceinline__ void gatv2_walk(const Gatv2Args &a, int beg, int end,
 }
 
 // Workgroups [0, n_seg): one segment of a long row each.  The others: block_of<GROUP>() / GROUP short rows each, one lane group per row.
-template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false>
-__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
+// (k_gatv2: EDGE = false; k_gatv2_edge: EDGE = true)
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS = false, bool EDGE = false, typename ARGS = Gatv2Args>
+__global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const ARGS a)
 {
     constexpr int BLOCK = block_of<GROUP>(), GPB = BLOCK / GROUP;
     __shared__ float s_m[BLOCK * NF], s_den[BLOCK * NF], s_acc[BLOCK * NF * VEC];
@@ -244,7 +275,7 @@ __global__ __launch_bounds__(block_of<GROUP>()) void k_gatv2(const Gatv2Args a)
             av[f][k] = ok ? a.a[col + k] : 0.0f;   // a is [heads, D]: element (h, c) sits at column h D + c
         }
     }
-    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>(a, beg, end, lane, xdv, av, hf, m, den, acc);
+    if (beg < end) gatv2_walk<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS, EDGE, ARGS>(a, beg, end, lane, xdv, av, hf, m, den, acc);
     if (!seg_block) {
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -303,6 +334,16 @@ struct Gatv2Kernel {   // names the kernel for the launch switches (gatv2_shared
     static constexpr auto get() { return &k_gatv2<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
 };
 
+// k_gatv2_edge<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>: the kernel with the EDGE arm, a sibling instantiation of the same template (a
+// wrapper around a shared body would reorder the instructions of k_gatv2; as a defaulted parameter it leaves them as they were)
+template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+constexpr auto k_gatv2_edge = &k_gatv2<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS, true, Gatv2EdgeArgs>;
+
+struct Gatv2EdgeKernel {
+    template <int VEC, int GROUP, int NF, typename TX, bool SEGRED, bool BIAS, bool WEIGHTS>
+    static constexpr auto get() { return k_gatv2_edge<VEC, GROUP, NF, TX, SEGRED, BIAS, WEIGHTS>; }
+};
+
 // ------------------------------------------------------------------------------------------------ geometry and launch
 size_t gatv2_slot_floats(int feat, int heads, int x_dtype)
 {
@@ -318,12 +359,23 @@ int launch_gatv2(const Gatv2Launch &L, void *stream_v)
     if (!gatv2_geometry(L.feat, L.heads, L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4, g))
         return fail(GNNAGG_ERR_ARG, "internal: GATv2 launch outside the kernel's shapes");
     if (L.V <= 0) return GNNAGG_OK;
+    constexpr const char *no_inst = "internal: GATv2 lane geometry without an instantiation";
+    if (L.ef) {   // the edge call: the alignment flag also covers the ef base and its row pitch
+        const int esize = L.x_dtype == GNNAGG_DTYPE_BF16 ? 2 : 4;
+        Gatv2EdgeArgs a;
+        attn_fill_args(a, L, g);
+        a.xs = L.xs; a.xd = L.xd; a.a = L.a;
+        a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0 && (uintptr_t)L.ef % 16 == 0 && (L.ef_pitch * esize) % 16 == 0) ? 1 : 0;
+        a.slope = L.slope;
+        a.ef = L.ef; a.ef_pitch = L.ef_pitch;
+        if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<Gatv2EdgeKernel, 8, __bf16>(a, g, stream, no_inst);
+        return attn_launch_typed<Gatv2EdgeKernel, 4, float>(a, g, stream, no_inst);
+    }
     Gatv2Args a;
     attn_fill_args(a, L, g);
     a.xs = L.xs; a.xd = L.xd; a.a = L.a;
     a.x_aligned = ((uintptr_t)L.xs % 16 == 0 && (uintptr_t)L.xd % 16 == 0) ? 1 : 0;   // (segmented: F * esize is a multiple of 16)
     a.slope = L.slope;
-    constexpr const char *no_inst = "internal: GATv2 lane geometry without an instantiation";
     if (L.x_dtype == GNNAGG_DTYPE_BF16) return attn_launch_typed<Gatv2Kernel, 8, __bf16>(a, g, stream, no_inst);
     return attn_launch_typed<Gatv2Kernel, 4, float>(a, g, stream, no_inst);
 }

@@ -2108,23 +2108,29 @@ static int attn_finish(const Ctx *c, const AttnLaunch &L)
     return launch_attn_finish(c->d_ptr, c->V, c->E, L.heads, L.alpha, L.stat, c->stream);
 }
 
-// gnnagg_gatv2_run, gnnagg_gatv2_run_bias and gnnagg_gatv2_run_weights: one body
+// gnnagg_gatv2_run, gnnagg_gatv2_run_bias, gnnagg_gatv2_run_weights and gnnagg_gatv2_run_edge: one body (edge: the call with d_ef, which
+// is needed where the graph has edges; a graph without edges reads none and runs the kernel without the operand)
 static int gatv2_run_impl(const char *fn_name, gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, void *d_y,
                           int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads, bool want_w = false,
-                          float *d_alpha = nullptr, float *d_stat = nullptr)
+                          float *d_alpha = nullptr, float *d_stat = nullptr, bool edge = false, const void *d_ef = nullptr,
+                          long long ef_pitch = 0)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
     Gatv2Launch L;
     L.x_dtype = x_dtype; L.y = d_y; L.y_dtype = y_dtype; L.feat = feat; L.heads = heads; L.bias = d_bias; L.bias_heads = bias_heads;
     if (want_w) { L.alpha = d_alpha; L.stat = d_stat; }
-    const char *null_operand = !d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : !d_y ? "d_y" : nullptr;
+    const char *null_operand = !d_xs ? "d_xs" : !d_xd ? "d_xd" : !d_a ? "d_a" : !d_y ? "d_y" : edge && !d_ef && c->E > 0 ? "d_ef" : nullptr;
     if (int rc = attn_check_call(c, fn, null_operand, want_w, L)) return rc;
     if (!(slope >= 0.0f && slope <= 1.0f))
         return fail(GNNAGG_ERR_ARG, fn + ": slope = " + std::to_string(slope) + " is outside [0, 1] (the leaky form max(z, z * slope))");
+    if (edge && ef_pitch < feat)
+        return fail(GNNAGG_ERR_ARG, fn + ": ef_pitch = " + std::to_string(ef_pitch) + ": a row pitch (in elements) is at least feat = " +
+                                        std::to_string(feat));
     if (int rc = attn_prepare(c, fn, L)) return rc;
     if (L.V == 0) return GNNAGG_OK;
     L.xs = d_xs; L.xd = d_xd; L.a = d_a; L.slope = slope;
+    if (edge && c->E > 0) { L.ef = d_ef; L.ef_pitch = ef_pitch; }
     if (int rc = launch_gatv2(L, c->stream)) return rc;
     return attn_finish(c, L);
 }
@@ -2141,26 +2147,31 @@ int gnnagg_gatv2_run_bias(gnnagg_handle h, const void *d_xs, const void *d_xd, i
     return gatv2_run_impl("gnnagg_gatv2_run_bias", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads);
 }
 
-// gnnagg_dot_attn_run, gnnagg_dot_attn_run_bias and gnnagg_dot_attn_run_weights: one body
+// gnnagg_dot_attn_run, gnnagg_dot_attn_run_bias, gnnagg_dot_attn_run_weights and gnnagg_dot_attn_run_edge: one body (edge: as above)
 static int dot_attn_run_impl(const char *fn_name, gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v,
                              long long kv_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias,
-                             int bias_heads, bool want_w = false, float *d_alpha = nullptr, float *d_stat = nullptr)
+                             int bias_heads, bool want_w = false, float *d_alpha = nullptr, float *d_stat = nullptr, bool edge = false,
+                             const void *d_ef = nullptr, long long ef_pitch = 0)
 {
     GET_CTX(h);
     const std::string fn(fn_name);
     DotAttnLaunch L;
     L.x_dtype = x_dtype; L.y = d_y; L.y_dtype = y_dtype; L.feat = feat; L.heads = heads; L.bias = d_bias; L.bias_heads = bias_heads;
     if (want_w) { L.alpha = d_alpha; L.stat = d_stat; }
-    const char *null_operand = !d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : !d_y ? "d_y" : nullptr;
+    const char *null_operand = !d_q ? "d_q" : !d_k ? "d_k" : !d_v ? "d_v" : !d_y ? "d_y" : edge && !d_ef && c->E > 0 ? "d_ef" : nullptr;
     if (int rc = attn_check_call(c, fn, null_operand, want_w, L)) return rc;
     if (q_pitch < feat || kv_pitch < feat)
         return fail(GNNAGG_ERR_ARG, fn + ": q_pitch = " + std::to_string(q_pitch) + ", kv_pitch = " + std::to_string(kv_pitch) +
                                         ": a row pitch (in elements) is at least feat = " + std::to_string(feat));
+    if (edge && ef_pitch < feat)
+        return fail(GNNAGG_ERR_ARG, fn + ": ef_pitch = " + std::to_string(ef_pitch) + ": a row pitch (in elements) is at least feat = " +
+                                        std::to_string(feat));
     if (!std::isfinite(scale))
         return fail(GNNAGG_ERR_ARG, fn + ": scale = " + std::to_string(scale) + " is not finite");
     if (int rc = attn_prepare(c, fn, L)) return rc;
     if (L.V == 0) return GNNAGG_OK;
     L.q = d_q; L.k = d_k; L.v = d_v; L.q_pitch = q_pitch; L.kv_pitch = kv_pitch; L.scale = scale;
+    if (edge && c->E > 0) { L.ef = d_ef; L.ef_pitch = ef_pitch; }
     if (int rc = launch_dot_attn(L, c->stream)) return rc;
     return attn_finish(c, L);
 }
@@ -2191,6 +2202,35 @@ int gnnagg_dot_attn_run_weights(gnnagg_handle h, const void *d_q, long long q_pi
 {
     return dot_attn_run_impl("gnnagg_dot_attn_run_weights", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale,
                              d_bias, bias_heads, true, d_alpha, d_stat);
+}
+
+// Without a visible GPU there is no handle to call with: the calls then say so (GNNAGG_ERR_HIP) instead of "invalid handle".
+static int edge_call_without_device(gnnagg_handle h)
+{
+    if (lookup(h)) return GNNAGG_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(GNNAGG_ERR_HIP, "no HIP device available: libgnnagg has no CPU fallback");
+    return GNNAGG_OK;
+}
+
+// (the weights-out form where either output is given: exactly one of them is the refusal of the _weights calls)
+int gnnagg_gatv2_run_edge(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, const void *d_ef,
+                          long long ef_pitch, void *d_y, int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads,
+                          float *d_alpha, float *d_stat)
+{
+    if (int rc = edge_call_without_device(h)) return rc;
+    return gatv2_run_impl("gnnagg_gatv2_run_edge", h, d_xs, d_xd, x_dtype, d_a, d_y, y_dtype, feat, heads, slope, d_bias, bias_heads,
+                          d_alpha || d_stat, d_alpha, d_stat, true, d_ef, ef_pitch);
+}
+
+int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                             const void *d_ef, long long ef_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale,
+                             const float *d_bias, int bias_heads, float *d_alpha, float *d_stat)
+{
+    if (int rc = edge_call_without_device(h)) return rc;
+    return dot_attn_run_impl("gnnagg_dot_attn_run_edge", h, d_q, q_pitch, d_k, d_v, kv_pitch, x_dtype, d_y, y_dtype, feat, heads, scale,
+                             d_bias, bias_heads, d_alpha || d_stat, d_alpha, d_stat, true, d_ef, ef_pitch);
 }
 
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,

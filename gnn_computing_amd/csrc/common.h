@@ -280,6 +280,8 @@ struct AttnLaunch {   // what GATv2 and dot-product attention launch alike (gatv
     int bias_heads = 1;                        // 1 or heads
     float *alpha = nullptr;                    // [num_e, heads] the raw scores out (the _run_weights calls; launch_attn_finish follows), or null
     float *stat = nullptr;                     // [V, heads, 2] (maximum, denominator) per (row, head); with alpha
+    const void *ef = nullptr;                  // [num_e, feat] of x_dtype, row p at p * ef_pitch: the _run_edge calls (the edge kernels), or null
+    long long ef_pitch = 0;
 };
 struct Gatv2Launch : AttnLaunch {
     const void *xs = nullptr, *xd = nullptr;   // elements of x_dtype

@@ -67,6 +67,30 @@ __device__ __forceinline__ Pack<VEC, TX> gatv2_load(const TX *p, int aligned)
     }
 }
 
+// gatv2_load for the per-edge feature rows (the EDGE arm of the walks): a stream read once, in order, beside gathered rows that are
+// re-read and mostly cache hits.  The aligned 16-byte load is marked non-temporal: 13 - 40 us faster at fp32 and for the bf16 dot-product,
+// even for bf16 GATv2 (profiles/attn_edge/nontemporal_ab.jsonl).  GNNAGG_EDGE_NT = 0 (an A/B switch, measurement
+// builds only) is the plain load.  Same bytes either way: the bits do not depend on it.
+#ifndef GNNAGG_EDGE_NT
+#define GNNAGG_EDGE_NT 1
+#endif
+template <int VEC, typename TX>
+__device__ __forceinline__ Pack<VEC, TX> gatv2_load_once(const TX *p, int aligned)
+{
+#if GNNAGG_EDGE_NT
+    if constexpr (VEC * sizeof(TX) == 16) {
+        if (aligned) {
+            typedef unsigned u4 __attribute__((ext_vector_type(4)));
+            const u4 t = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(p));
+            Pack<VEC, TX> r;
+            __builtin_memcpy(&r, &t, 16);
+            return r;
+        }
+    }
+#endif
+    return gatv2_load<VEC, TX>(p, aligned);
+}
+
 // acc / den of a finished row piece, stored in Y's type
 template <int VEC>
 __device__ __forceinline__ void gatv2_store(const Gatv2Args &a, size_t off, const float (&acc)[VEC], float den, bool has_edges)

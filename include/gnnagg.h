@@ -572,6 +572,47 @@ int gnnagg_gatv2_run_weights(gnnagg_handle h, const void *d_xs, const void *d_xd
 int gnnagg_dot_attn_run_weights(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
                                 int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale, const float *d_bias, int bias_heads,
                                 float *d_alpha, float *d_stat);
+/* The two attentions with a feature VECTOR per edge (no reference counterpart; the edge_dim / edge_attr argument of PyG's GATv2Conv and
+ * TransformerConv and of DGL's equivalents, after the layer's own projection to feat columns: bond features of molecular graphs, relation
+ * embeddings of knowledge graphs, the edge channel of GPS / SAN-style graph transformers) -- without the [num_e, feat] intermediate
+ * xs[idx] + ef that the calls above would need.  One entry point per attention; each carries the optional bias and the optional weights
+ * and statistics.  Everything said under gnnagg_gatv2_run, gnnagg_dot_attn_run, the _bias and the _weights calls holds -- batches, the
+ * single guarded rescale, segments and their ordered merge, the bias add, the masks, the weights-out form, "no atomics, the same bits on
+ * every call", "depends on the lane geometry of (feat, heads, x_dtype) only, never on alignment or pitch"; what is added:
+ *   operand      d_ef holds [num_e, feat] elements of x_dtype (the type of the other operands), row p at element p * ef_pitch with
+ *                ef_pitch >= feat, the offset taken in 64 bits.  Rows are indexed by the POSITION p of the edge in the handle's CSR
+ *                (ptr[r] <= p < ptr[r + 1]), exactly like d_bias.  Any element offset, any pitch >= feat.  d_y aliases no input.
+ *   arithmetic   fp32 throughout; bf16 is widened exactly and nothing is rounded back to bf16 before use.  For edge p = (row r, source j):
+ *                GATv2 (gnnagg_gatv2_run_edge; GATv2Conv(edge_dim=)):
+ *                    z_jc = xd[r, c] + (xs[j, c] + ef[p, c])     the inner add first, each ONE fp32 add
+ *                    e_p  = sum_c a[h, c] * leaky(z_jc)          y[r] = sum_p alpha_p * xs[j]     (the summed row is xs[j] WITHOUT ef)
+ *                dot-product (gnnagg_dot_attn_run_edge; TransformerConv(edge_dim=)):
+ *                    k'_p = k[j] + ef[p],  v'_p = v[j] + ef[p]   each ONE fp32 add per element
+ *                    e_p  = sum_c (scale * q[r, c]) * k'_p[c]    the FMA chain of gnnagg_dot_attn_run
+ *                    y[r] = sum_p alpha_p * v'_p
+ *                so, for fp32 operands, gnnagg_dot_attn_run_edge on (ptr, idx) gives the bits of gnnagg_dot_attn_run on the graph
+ *                (ptr, 0 .. num_e - 1) with k' and v' materialised by one fp32 add, and gnnagg_gatv2_run_edge gives that graph's alpha and
+ *                stat with xs' = xs[idx] + ef (its y sums xs[j], not xs').
+ *   zero         an ef of all +0.0 gives the values of the call without it (== on every element; only the sign of a zero may differ).
+ *   error        the bounds of the calls above with L taken over the scores WITH ef (and the bias), S[r] = sum_p alpha_p |v'_p| for the
+ *                dot-product and sum_p alpha_p |xs_j| for GATv2.
+ *   non-finite   non-finite ef elements follow plain IEEE on k', v' and z: the call has the class map of the float64 formulas on those
+ *                operands, and every (row, head) the value does not reach is bit-equal to the run without it.
+ *   outputs      d_bias may be NULL (bias_heads is then ignored).  d_alpha and d_stat are both NULL (no weights out) or both given.
+ *   refusals     those of the _weights calls under these names, and GNNAGG_ERR_ARG naming the argument for a null d_ef (where num_e > 0),
+ *                for ef_pitch < feat, and for exactly one of d_alpha / d_stat; nothing launched, d_y, d_alpha and d_stat untouched.
+ *   streams      no handle state is added: the segment list, the slots and the scratch are those of the calls above and sized alike.  One
+ *                handle serves edge and non-edge calls of both kinds in any order; a call of a shape that has run allocates and synchronises
+ *                nothing and is captured in a HIP graph, which holds d_ef as it holds the other operands (rewrite ef in place between
+ *                replays).  Where the d_ef base or ef_pitch * element size is not 16-byte aligned the whole call loads element by element:
+ *                the aligned run's bits.  A call without ef launches the kernels it launched before these calls existed.
+ * (tests/test_gpu_attn_edge.py, tests/test_attn_edge_host.py) */
+int gnnagg_gatv2_run_edge(gnnagg_handle h, const void *d_xs, const void *d_xd, int x_dtype, const float *d_a, const void *d_ef,
+                          long long ef_pitch, void *d_y, int y_dtype, int feat, int heads, float slope, const float *d_bias, int bias_heads,
+                          float *d_alpha, float *d_stat);
+int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
+                             const void *d_ef, long long ef_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale,
+                             const float *d_bias, int bias_heads, float *d_alpha, float *d_stat);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
