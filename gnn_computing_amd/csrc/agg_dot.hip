@@ -31,15 +31,12 @@ struct DotArgs : Gatv2Args {   // q is xd, k is xs (a and slope are unused); wha
     float scale;
 };
 
-#ifndef GNNAGG_DOT_WIDE_BATCH   // A/B switches (measurement builds only): the batch of the geometries with GNNAGG_DOT_WIDE_NF or more fragments per lane
-#define GNNAGG_DOT_WIDE_BATCH (kGatv2Batch / 2)
-#endif
-#ifndef GNNAGG_DOT_WIDE_NF
-#define GNNAGG_DOT_WIDE_NF 2
-#endif
+// the batch of the geometries with kDotWideNf or more fragments per lane
+static constexpr int kDotWideBatch = kGatv2Batch / 2;
+static constexpr int kDotWideNf = 2;
 template <int NF>
-constexpr int dot_batch() { return NF >= GNNAGG_DOT_WIDE_NF ? GNNAGG_DOT_WIDE_BATCH : kGatv2Batch; }
-static_assert(kGatv2Batch % dot_batch<GNNAGG_DOT_WIDE_NF>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
+constexpr int dot_batch() { return NF >= kDotWideNf ? kDotWideBatch : kGatv2Batch; }
+static_assert(kGatv2Batch % dot_batch<kDotWideNf>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
 
 struct DotEdgeArgs : DotArgs {
     const void *ef;   // [num_e, feat] elements of the operands' type, row p at p * ef_pitch

@@ -500,9 +500,7 @@ int launch_gat(const GatLaunch &L, void *stream_v)
 // 64 lanes (the rule of k_gcn_plan), typed launches from 16-lane groups on: the
 // arxiv-shaped 1 head x 128 in bf16 (16 lanes of 8 elements) runs 73.0 / 65.0 us (fp32 / bf16 y) with 4 gathers (63 VGPRs) against 85.6 /
 // 82.1 us with 8 (89 VGPRs, 5 waves per SIMD); 8 heads x 16: 77.7 / 70.1 against 77.8 / 71.7 (profiles/bf16_gat/).  8-lane groups keep 8.
-#ifndef GNNAGG_GAT_TYPED_U4_GROUP   // A/B switch (measurement builds only): the narrowest lane group that takes 4 gathers per batch
-#define GNNAGG_GAT_TYPED_U4_GROUP 16
-#endif
+static constexpr int kGatTypedU4Group = 16;  // the narrowest lane group of a typed launch that takes 4 gathers per batch
 template <int VEC, int GROUP, int UNROLL, typename TX, bool TYPED, bool SHIFT>
 static void launch_gat_plan_unroll(const GatPlanArgs &a, int grid, int blk, hipStream_t stream)
 {
@@ -512,7 +510,7 @@ static void launch_gat_plan_unroll(const GatPlanArgs &a, int grid, int blk, hipS
 template <int VEC, int GROUP, typename TX, bool TYPED, bool SHIFT = false>
 static void launch_gat_plan_geom(const GatPlanArgs &a, bool u4, int grid, int blk, hipStream_t stream)
 {
-    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= (TYPED ? GNNAGG_GAT_TYPED_U4_GROUP : 32)) {
+    if constexpr (VEC * sizeof(TX) == 16 && GROUP >= (TYPED ? kGatTypedU4Group : 32)) {
         if (u4) return launch_gat_plan_unroll<VEC, GROUP, 4, TX, TYPED, SHIFT>(a, grid, blk, stream);
     }
     launch_gat_plan_unroll<VEC, GROUP, kUnroll, TX, TYPED, SHIFT>(a, grid, blk, stream);

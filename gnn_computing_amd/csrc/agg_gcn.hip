@@ -232,11 +232,6 @@ __device__ __forceinline__ bool hub_arrive_and_fold(const PlanArgs &a, const int
     return true;
 }
 
-#ifdef GNNAGG_PLAN_WAVES  // A/B: ask the register allocator for this many waves per SIMD (default: what 76 VGPRs give, 6)
-#define PLAN_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(GNNAGG_PLAN_WAVES, GNNAGG_PLAN_WAVES)))
-#else
-#define PLAN_WAVES_ATTR
-#endif
 // UNROLL: row gathers issued per batch before the first FMA.  8 by default; 4 for the 32- and 64-lane float4 geometries (F > 64)
 // of the balanced / scheduled orders: 59 instead of 76 VGPRs, 8 instead of 6 waves per SIMD -- the arxiv-shaped headline
 // with the locality reorder 77.9 -> 74.0 us (without reorder, and at F = 100: unchanged); the canonical rows mode keeps 8
@@ -245,7 +240,7 @@ __device__ __forceinline__ bool hub_arrive_and_fold(const PlanArgs &a, const int
 // TYPED = true stores Y through store_y_typed (a.y_bf16, a.yvec).  Chains, LDS stage, partial rows and hub fold stay fp32, so a bf16 X
 // gives bit for bit the fp32 run on X widened.  The defaults are the fp32 kernel, instruction for instruction.
 template <int VEC, int GROUP, bool IS_MAX, bool PROBE = false, int UNROLL = kUnroll, typename TX = float, bool TYPED = false>
-__global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(const PlanArgs a)
+__global__ __launch_bounds__(block_of<GROUP>()) void k_gcn_plan(const PlanArgs a)
 {
     static_assert(TYPED || std::is_same<TX, float>::value, "16-bit X needs the typed store");
     constexpr int GPB = block_of<GROUP>() / GROUP;
@@ -368,16 +363,10 @@ __global__ __launch_bounds__(block_of<GROUP>()) PLAN_WAVES_ATTR void k_gcn_plan(
 // Unlike the reference (partial . W added with atomics per neighbor group) W is applied to the FINAL row: rows that
 // are folded from several chunks get their product where the fold ends (segment workgroup, hub fold, k_combine: one fmaf
 // chain per output column, row_times_weight); the rows-mode long rows from k_dense_rows after the join.
-#ifndef NN_ROWS
-#define NN_ROWS 16
-#endif
-static constexpr int kNnRows = NN_ROWS;  // short rows a workgroup of the fused kernel aggregates and multiplies
-#ifndef NN_ROWS_BF16
-#define NN_ROWS_BF16 16
-#endif
+static constexpr int kNnRows = 16;  // short rows a workgroup of the fused kernel aggregates and multiplies
 // ... with the bf16 product, which stages W in LDS once per workgroup.  More rows per staging lose: every pass of GPB rows is one more
 // dependent round of gathers per wavefront (arxiv-shaped, bf16 128 -> 32: 16 / 32 / 64 rows 65.3 / 74.6 / 99.0 us; 64 -> 32: 44.1 / 57.6 / 81.3).
-static constexpr int kNnRowsBf16 = NN_ROWS_BF16;
+static constexpr int kNnRowsBf16 = 16;
 
 struct NnArgs {
     const void *weight;  // [K, N] row-major: fp32; bf16 in the bf16-product instantiations (YB)
@@ -823,12 +812,7 @@ __global__ __launch_bounds__(BLOCK) void k_gcn_rows_long(const RowsLongArgs a)
                     ws[q] = *reinterpret_cast<const float4 *>(&wst[k + 4 * q]);
                 }
                 unsigned long long v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                while ((int)(v >> 32) != gb) {
-#ifdef GNNAGG_EXP_POLL_SLEEP
-                    __builtin_amdgcn_s_sleep(GNNAGG_EXP_POLL_SLEEP);
-#endif
-                    v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
+                while ((int)(v >> 32) != gb) v = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 float acc = __uint_as_float((unsigned)v);
                 auto step = [&](float x1, float w1) {
                     if (IS_MAX) {

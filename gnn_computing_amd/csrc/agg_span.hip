@@ -24,23 +24,10 @@
 
 namespace gnnagg {
 
-#ifndef GNNAGG_PARTIAL_AUX
-#define GNNAGG_PARTIAL_AUX 2
-#endif
-static constexpr int kPartialAux = GNNAGG_PARTIAL_AUX;  // (the flushes cost 0.8 ms of R's 15.05: a build without them runs 14.25 ms)  // partial rows: streaming (nt) stores, see store_pack_wt
-// The id (and value) stream is read once per column tile and never again by this workgroup: streaming loads (A/B: GNNAGG_ID_NT)
-#ifndef GNNAGG_ID_NT
-#define GNNAGG_ID_NT 0
-#endif
-template <class T>
-__device__ __forceinline__ T stream_load(const T *p)
-{
-#if GNNAGG_ID_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+static constexpr int kPartialAux = 2;  // (the flushes cost 0.8 ms of R's 15.05: a build without them runs 14.25 ms)  // partial rows: streaming (nt) stores, see store_pack_wt
+// The id (and value) stream is read once per column tile and never again by this workgroup, yet it is read with plain loads: the
+// non-temporal form stayed off (such loads of once-streamed metadata measured 1-5 % slower, see chain_edges; its text is in
+// scripts/attic/ab_switches_retired.patch).
 static constexpr unsigned kLastFlag = 0x80000000u;    // id word: last edge of its group
 static constexpr unsigned kDirectFlag = 0x40000000u;  // (with kLastFlag) the group is its row's only group: result goes to Y
 static constexpr unsigned kIdMask = 0x3fffffffu;
@@ -65,18 +52,13 @@ struct SpanArgs {
 
 // FAST_ADDR: every byte offset inside one tile image of X fits 32 bits and ids fit 24 (host-checked): the gather address
 // is (uniform tile base) + a 32-bit lane offset -- one 24-bit multiply per gather instead of 64-bit address arithmetic.
-#ifdef GNNAGG_SPAN_WAVES  // A/B: ask the register allocator for this many waves per SIMD (default: what 64-80 VGPRs give, 6-8)
-#define SPAN_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(GNNAGG_SPAN_WAVES, GNNAGG_SPAN_WAVES)))
-#else
-#define SPAN_WAVES_ATTR
-#endif
 // CHAIN (canonical rows mode on the blocked order, gnnagg "rows_blocked"): a launch covers ONE source range; a group is a whole
 // (row, range) sub-row; its chain starts from what the row's earlier ranges left in the tiled image of Y (`partial` = Yt[tile][row],
 // zeroed before the first range) and goes back there -- for rows whose neighbors are sorted, range after range IS the CSR order, so
 // every (row, column) is the reference's one sequential chain (aggr_gcn.h:13-35), bit for bit, with the gathers served by the L2.
 // The carry of the NEXT group is requested while the current one is walked (its row comes from a 16-group window of targets).
 template <int GROUP, bool IS_MAX, bool HAS_VAL, bool PROBE, bool FAST_ADDR, bool CHAIN = false>
-__global__ __launch_bounds__(256) SPAN_WAVES_ATTR void k_gcn_span(const SpanArgs a)
+__global__ __launch_bounds__(256) void k_gcn_span(const SpanArgs a)
 {
     constexpr int VEC = 4, GPB = 256 / GROUP, U = kUnroll;
     const int lane = threadIdx.x & (GROUP - 1);
@@ -130,30 +112,21 @@ __global__ __launch_bounds__(256) SPAN_WAVES_ATTR void k_gcn_span(const SpanArgs
     unsigned my_s = 0;
     float my_w = 1.0f;
     if (e0 + lane < e_end) {
-        my_s = (unsigned)stream_load(&a.idx_f[e0 + lane]);
-        if (HAS_VAL) my_w = stream_load(&a.val_s[e0 + lane]);
+        my_s = (unsigned)a.idx_f[e0 + lane];
+        if (HAS_VAL) my_w = a.val_s[e0 + lane];
     }
-    // one batch of U edges of the window at cb: gathers issued together, then the chain in list order.  JC >= 0: a full window,
-    // batch offset known at compile time (no bound checks; the id / value of edge JC + u comes by group_bcast: a DPP move for
-    // 16-lane groups); JC == -2: a full window, runtime offset; JC == -1: the last, partial window.
-    auto batch = [&](auto jc_tag, int cb, int j, int n) {
-        constexpr int JC = decltype(jc_tag)::value;
-        constexpr bool FULL = JC != -1;  // -2: a full window with a runtime batch offset (wider lane groups: no DPP form)
+    // one batch of U edges of the window at cb: gathers issued together, then the chain in list order.  FULL: a full window (no bound
+    // checks); otherwise the last, partial window.  (The form with compile-time batch offsets and DPP broadcasts for 16-lane groups
+    // measured slower, see group_bcast: its text is in scripts/attic/ab_switches_retired.patch.)
+    auto batch = [&](auto full_tag, int cb, int j, int n) {
+        constexpr bool FULL = decltype(full_tag)::value;
         unsigned sr[U];
         float w[U];
         Pack<VEC> xv[U];
-        if constexpr (JC >= 0) {
-            static_for<U>([&](auto uc) {
-                constexpr int u = decltype(uc)::value;
-                sr[u] = (unsigned)group_bcast<GROUP, JC + u>((int)my_s);
-                if (HAS_VAL) w[u] = group_bcast<GROUP, JC + u>(my_w);
-            });
-        } else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                sr[u] = (unsigned)__shfl((int)my_s, j + u, GROUP);
-                if (HAS_VAL) w[u] = __shfl(my_w, j + u, GROUP);
-            }
+        for (int u = 0; u < U; ++u) {
+            sr[u] = (unsigned)__shfl((int)my_s, j + u, GROUP);
+            if (HAS_VAL) w[u] = __shfl(my_w, j + u, GROUP);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -233,23 +206,16 @@ __global__ __launch_bounds__(256) SPAN_WAVES_ATTR void k_gcn_span(const SpanArgs
         unsigned nx_s = 0;
         float nx_w = 1.0f;
         if (cb + GROUP + lane < e_end) {
-            nx_s = (unsigned)stream_load(&a.idx_f[cb + GROUP + lane]);
-            if (HAS_VAL) nx_w = stream_load(&a.val_s[cb + GROUP + lane]);
+            nx_s = (unsigned)a.idx_f[cb + GROUP + lane];
+            if (HAS_VAL) nx_w = a.val_s[cb + GROUP + lane];
         }
         const int n = e_end - cb < GROUP ? e_end - cb : GROUP;
         if (n == GROUP) {
-            if constexpr (GROUP == 16 && GNNAGG_DPP_SPAN_GCN) {
-                static_for<GROUP / U>([&](auto bc) {
-                    constexpr int J = decltype(bc)::value * U;
-                    batch(std::integral_constant<int, J>{}, cb, J, n);
-                });
-            } else {
 #pragma unroll 1
-                for (int j = 0; j < GROUP; j += U) batch(std::integral_constant<int, -2>{}, cb, j, n);
-            }
+            for (int j = 0; j < GROUP; j += U) batch(std::true_type{}, cb, j, n);
         } else {
 #pragma unroll 1
-            for (int j = 0; j < n; j += U) batch(std::integral_constant<int, -1>{}, cb, j, n);
+            for (int j = 0; j < n; j += U) batch(std::false_type{}, cb, j, n);
         }
         my_s = nx_s;
         my_w = nx_w;
@@ -387,12 +353,8 @@ __device__ __forceinline__ float row_bcast_banks(float old, float v)
 // from a wave-uniform tile base), one broadcast per head of the tile for the weight (bank-masked: no select), the FMAs, the
 // denominator add and the group-end test.  Everything that happens once per window or once per group stays out of it.
 // PROBE: the same id / attention-term loads and tile-row gathers, XOR-consumed; no exp, no chain, no store (gnnagg_gat_probe_gather).
-#ifndef GAT_SPAN_U
-#define GAT_SPAN_U 16
-#endif
-#ifndef GAT_SPAN_WAVES
-#define GAT_SPAN_WAVES 4
-#endif
+static constexpr int kGatSpanU = 16;     // gathers in flight per batch (below)
+static constexpr int kGatSpanWaves = 4;  // waves per SIMD asked for at 1-2 heads per tile (above)
 // CHAIN (gnnagg "rows_blocked", GAT): one launch per source range, a group = a whole (row, range) sub-row; its numerator chain starts
 // from what the row's earlier ranges left in Yt[tile][row] and its denominator chain from den_t[tile][row][head] -- both go back
 // there at the group's end, the next group's carries are requested while the current one is walked.  For rows whose neighbors are
@@ -400,11 +362,11 @@ __device__ __forceinline__ float row_bcast_banks(float old, float v)
 // chain of aggr_gat (aggr_gat.h:125-163); k_untile_y divides.  A head wider than the tile keeps one denominator copy per tile (the
 // tiles of a row run in different workgroups of the same launch: a shared copy would be read after another tile had updated it).
 template <int GROUP, int HT, bool SHIFT, bool PROBE, bool CHAIN = false>
-__global__ __launch_bounds__(256, (HT <= 2 ? GAT_SPAN_WAVES : 2)) void k_gat_span(const GatSpanArgs A)
+__global__ __launch_bounds__(256, (HT <= 2 ? kGatSpanWaves : 2)) void k_gat_span(const GatSpanArgs A)
 {
     const SpanArgs &a = A.s;
     // a whole 16-edge window of gathers in flight (8 per batch: 13.0 ms, 16: 9.7 ms on the reddit-shaped 8 x 32 case)
-    constexpr int VEC = 4, GPB = 256 / GROUP, U = GROUP < GAT_SPAN_U ? GROUP : GAT_SPAN_U;
+    constexpr int VEC = 4, GPB = 256 / GROUP, U = GROUP < kGatSpanU ? GROUP : kGatSpanU;
     constexpr bool BANKED = GROUP == 16 && (HT == 2 || HT == 4);  // a head's lanes = whole DPP banks
     const int lane = threadIdx.x & (GROUP - 1);
     const int grp = (int)threadIdx.x / GROUP;
@@ -464,7 +426,7 @@ __global__ __launch_bounds__(256, (HT <= 2 ? GAT_SPAN_WAVES : 2)) void k_gat_spa
         if (valid) load_terms<HT>(as_hg + (size_t)(sw & kIdMask) * HT, as);
     };
     if (e0 + lane < e_end) {
-        my_s = (unsigned)stream_load(&a.idx_f[e0 + lane]);
+        my_s = (unsigned)a.idx_f[e0 + lane];
         if (A.newval) my_e = A.eperm[e0 + lane];
     }
     load_src_terms(my_s, e0 + lane < e_end, as_c);
@@ -501,7 +463,7 @@ __global__ __launch_bounds__(256, (HT <= 2 ? GAT_SPAN_WAVES : 2)) void k_gat_spa
         int nx_e = 0;
         const bool nx_valid = cb + GROUP + lane < e_end;
         if (nx_valid) {
-            nx_s = (unsigned)stream_load(&a.idx_f[cb + GROUP + lane]);
+            nx_s = (unsigned)a.idx_f[cb + GROUP + lane];
             if (A.newval) nx_e = A.eperm[cb + GROUP + lane];
         }
         const int n = e_end - cb < GROUP ? e_end - cb : GROUP;

@@ -304,10 +304,8 @@ static int build_balanced_plan_keep(Ctx *c) { return build_plan_into(c, c->plan,
 // consecutive windows (and with them the XCD ranges) still follow the row order.  Measured on the arxiv-shaped input:
 // F=32 43.3 -> 36.8 us, F=64 51.6 -> 51.0 us; F=128 (2 rows per wavefront) gets slower, so it keeps the row order.
 // The rule is about rows per wavefront, i.e. ROW BYTES (16-byte lanes): fp32 F <= 64, bf16 F <= 128 (gnnagg_gcn_run_typed).
-#ifndef GNNAGG_SORT_ROW_BYTES   // A/B switch (measurement builds only)
-#define GNNAGG_SORT_ROW_BYTES 256
-#endif
-static bool wants_sorted_rows(const Ctx *c, long row_bytes) { return c->sort_window > 1 && row_bytes <= GNNAGG_SORT_ROW_BYTES; }
+static constexpr int kSortRowBytes = 256;
+static bool wants_sorted_rows(const Ctx *c, long row_bytes) { return c->sort_window > 1 && row_bytes <= kSortRowBytes; }
 
 static int ensure_sorted_rows(Ctx *c, BalancedPlan &p)
 {

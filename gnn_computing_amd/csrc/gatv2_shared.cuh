@@ -69,15 +69,11 @@ __device__ __forceinline__ Pack<VEC, TX> gatv2_load(const TX *p, int aligned)
 
 // gatv2_load for the per-edge feature rows (the EDGE arm of the walks): a stream read once, in order, beside gathered rows that are
 // re-read and mostly cache hits.  The aligned 16-byte load is marked non-temporal: 13 - 40 us faster at fp32 and for the bf16 dot-product,
-// even for bf16 GATv2 (profiles/attn_edge/nontemporal_ab.jsonl).  GNNAGG_EDGE_NT = 0 (an A/B switch, measurement
-// builds only) is the plain load.  Same bytes either way: the bits do not depend on it.
-#ifndef GNNAGG_EDGE_NT
-#define GNNAGG_EDGE_NT 1
-#endif
+// even for bf16 GATv2 (profiles/attn_edge/nontemporal_ab.jsonl).  Same bytes as the plain load it was measured against
+// (scripts/attic/ab_switches_retired.patch has the switch): the bits do not depend on it.
 template <int VEC, typename TX>
 __device__ __forceinline__ Pack<VEC, TX> gatv2_load_once(const TX *p, int aligned)
 {
-#if GNNAGG_EDGE_NT
     if constexpr (VEC * sizeof(TX) == 16) {
         if (aligned) {
             typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -87,7 +83,6 @@ __device__ __forceinline__ Pack<VEC, TX> gatv2_load_once(const TX *p, int aligne
             return r;
         }
     }
-#endif
     return gatv2_load<VEC, TX>(p, aligned);
 }
 

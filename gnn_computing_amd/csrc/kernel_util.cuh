@@ -52,10 +52,7 @@ static inline int block_for(int group) { return group * 8 < kBlock ? group * 8 :
 // gathers (59 VGPRs, 8 waves per SIMD) beat 8 (76 VGPRs, 6 waves): 74.0 vs 77.9 us -- k_gcn_plan / k_gat_plan therefore
 // take the batch size as a template parameter (4 on the 32- and 64-lane float4 geometries of the balanced / scheduled
 // orders, this default elsewhere: long chains and narrow geometries want 8).
-#ifndef KUNROLL
-#define KUNROLL 8
-#endif
-static constexpr int kUnroll = KUNROLL;
+static constexpr int kUnroll = 8;
 static constexpr int kSegChunks = 16;  // chunks of a long row that one segment workgroup folds in LDS (plan kernels)
 
 // ---------------------------------------------------------------------------------- helpers
@@ -194,14 +191,12 @@ __device__ __forceinline__ void store_pack_any(float *p, const float (&a)[VEC], 
 // Output rows are written once and never re-read by this kernel: a write-through (sc1) store leaves the XCD's L2
 // to the gathered feature rows instead of parking 87 MB of results in it.  Buffer store so the cache bits can be
 // given (aux 16 = sc1); `yoff` is the element offset from `ybase` (callers guarantee the byte offset fits 31 bits).
-#ifndef GNNAGG_WT_AUX
-#define GNNAGG_WT_AUX 16
-#endif
+static constexpr int kWtAux = 16;
 // AUX: cache-policy bits of the buffer store (gfx950: 1 = sc0, 2 = nt, 16 = sc1).  sc1 (write-through to device scope) for
 // results and for the hub scratch other XCDs read in the same launch; nt (streaming) for the partial rows of the 2-D
 // blocked order, which only a later launch reads: they then do not displace the X slice the L2 is there to hold
 // (reddit-shaped F = 602: 15.40 -> 14.97 ms, GAT 8 x 32: 7.84 -> 7.56 ms; nt + sc1: 15.15 / 7.69).
-template <int VEC, int AUX = GNNAGG_WT_AUX>
+template <int VEC, int AUX = kWtAux>
 __device__ __forceinline__ void store_pack_wt(float *ybase, unsigned nbytes, size_t yoff, const float (&a)[VEC])
 {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(ybase, 0, (int)nbytes, 0x00020000);
@@ -289,7 +284,7 @@ __device__ __forceinline__ void store_pack_bf16(__bf16 *p, const float (&a)[VEC]
 }
 
 // Write-through form (store_pack_wt) of a whole lane, VEC >= 2: `yoff` in elements from `ybase`
-template <int VEC, int AUX = GNNAGG_WT_AUX>
+template <int VEC, int AUX = kWtAux>
 __device__ __forceinline__ void store_pack_bf16_wt(__bf16 *ybase, unsigned nbytes, size_t yoff, const float (&a)[VEC])
 {
     static_assert(VEC >= 2, "whole words only");
@@ -384,14 +379,6 @@ __device__ __forceinline__ int logical_block_tile_major(int b, int item_blocks, 
     return (L - tile * item_blocks) * ntiles + tile;
 }
 
-// A/B switches for the DPP forms of the id / value broadcast (measured: DESIGN.md section 4).
-#ifndef GNNAGG_DPP_CHAIN
-#define GNNAGG_DPP_CHAIN 0
-#endif
-#ifndef GNNAGG_DPP_SPAN_GCN
-#define GNNAGG_DPP_SPAN_GCN 0
-#endif
-
 // Compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
 template <int N, class Fn>
 __device__ __forceinline__ void static_for(Fn &&f)
@@ -406,7 +393,8 @@ __device__ __forceinline__ void static_for(Fn &&f)
 // DPP rows: row_newbcast is a full-rate VALU move with no LDS round trip -- ds_bpermute, what __shfl compiles to, goes
 // through the LDS pipe and puts ~100 cycles into the id -> address -> gather chain.  Used by the GAT span kernel (10.2 ->
 // 8.7 ms on the reddit-shaped 8 x 32 case); on the GCN kernels the unrolled form costs registers and measured slower
-// (arxiv-shaped headline 77 -> 103 us, reddit-shaped F = 602 15.9 -> 16.1 ms): GNNAGG_DPP_CHAIN / GNNAGG_DPP_SPAN_GCN stay 0.
+// (arxiv-shaped headline 77 -> 103 us, reddit-shaped F = 602 15.9 -> 16.1 ms): chain_edges and k_gcn_span
+// broadcast with __shfl, and the DPP forms of both are kept as text in scripts/attic/ab_switches_retired.patch.
 template <int GROUP, int SRC>
 __device__ __forceinline__ int group_bcast(int v)
 {
@@ -444,60 +432,6 @@ __device__ __forceinline__ void chain_edges(float (&acc)[VEC], int beg, int end,
                                             const int *__restrict__ idx, const float *__restrict__ val,
                                             const TX *__restrict__ xcol, int F)
 {
-    if constexpr (GROUP >= 16 && GNNAGG_DPP_CHAIN) {
-        // Windows of 16 edges, one copy per 16-lane DPP row of the group (lanes l and l + 16 load the same id: one request):
-        // the (id, value) of edge cb + u then reaches every lane of the group by row_newbcast -- a VALU move instead of the
-        // ds_bpermute round trip through the LDS pipe (arxiv-shaped headline: see DESIGN.md section 4).  Same edge order,
-        // same bits.
-        const int l16 = lane & 15;
-        int my_s = 0;
-        float my_w = 1.0f;
-        if (beg + l16 < end) {
-            my_s = idx[beg + l16];
-            if (val) my_w = val[beg + l16];
-        }
-        for (int cb = beg; cb < end; cb += 16) {
-            int nx_s = 0;
-            float nx_w = 1.0f;
-            if (cb + 16 + l16 < end) {
-                nx_s = idx[cb + 16 + l16];
-                if (val) nx_w = val[cb + 16 + l16];
-            }
-            const int n = end - cb < 16 ? end - cb : 16;
-            static_for<16 / UNROLL>([&](auto bc) {
-                constexpr int J = decltype(bc)::value * UNROLL;
-                if (J < n) {
-                    int s[UNROLL];
-                    float w[UNROLL];
-                    Pack<VEC, TX> xv[UNROLL];
-                    static_for<UNROLL>([&](auto uc) {
-                        constexpr int u = decltype(uc)::value;
-                        s[u] = group_bcast<16, J + u>(my_s);
-                        w[u] = group_bcast<16, J + u>(my_w);
-                    });
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u)
-                        if (J + u < n && col_ok) xv[u] = load_pack<VEC>(xcol + (size_t)s[u] * F);
-#pragma unroll
-                    for (int u = 0; u < UNROLL; ++u)
-                        if (J + u < n && col_ok) {
-#pragma unroll
-                            for (int k = 0; k < VEC; ++k) {
-                                if (IS_MAX) {
-                                    const float p = xv[u].at(k) * w[u];
-                                    acc[k] = p > acc[k] ? p : acc[k];
-                                } else {
-                                    acc[k] = __builtin_fmaf(xv[u].at(k), w[u], acc[k]);
-                                }
-                            }
-                        }
-                }
-            });
-            my_s = nx_s;
-            my_w = nx_w;
-        }
-        return;
-    }
     int my_s = 0;
     float my_w = 1.0f;
     if (beg + lane < end) {
@@ -653,16 +587,14 @@ static int align_class(int F, const void *p, int esize, int maxvec)
     while (v > 1 && (F % v != 0 || (uintptr_t)p % ((uintptr_t)v * esize) != 0)) v >>= 1;
     return v;
 }
-#ifndef GNNAGG_TYPED_LANE_BYTES   // A/B switch (measurement builds only): the widest lane of a typed launch
-#define GNNAGG_TYPED_LANE_BYTES 16
-#endif
+static constexpr int kTypedLaneBytes = 16;  // the widest lane of a typed launch
 // Lanes as wide as F and X's alignment allow, up to 16 bytes: 8 bf16 elements (F = 128 -> 16-lane groups reading 256-byte rows), 8-,
 // 4- or 2-byte lanes where F or the alignment forces them.  Y's alignment class is set apart (PlanArgs::yvec): a fp32 Y row is twice
 // as wide as the bf16 row a lane reads.  The fp32 partial rows live in scratch the library allocates, aligned for any lane.
 // dhead (GAT; pick_geometry's rule): a lane's VEC columns lie inside one head, so VEC divides dhead too (dhead divides F; GCN: dhead = F).
 static Geometry typed_geometry(int F, const void *x, int xsize, int dhead)
 {
-    const int vec = align_class(dhead, x, xsize, GNNAGG_TYPED_LANE_BYTES / xsize);
+    const int vec = align_class(dhead, x, xsize, kTypedLaneBytes / xsize);
     const int lanes = (F + vec - 1) / vec;
     int group = 8;
     while (group < 64 && group < lanes) group <<= 1;

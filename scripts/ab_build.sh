@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B builds of the kernel files: scripts/ab_build.sh NAME "-DFOO=1 ..." -> gnn_computing_amd/csrc/build/ab/libgnnagg_NAME.so
-# (select at run time with GNNAGG_LIB=<path>).
+# (select at run time with GNNAGG_LIB=<path>).  The second argument goes to every kernel file's compile line: -mllvm options, or the -D of
+# a patched tree.  The shipped sources have no compile-time switch left: to rebuild a retired form, apply scripts/attic/ab_switches_retired.patch
+# (or gemm_switches_retired.patch, on the commit it names) to a copy of the tree and run that copy's ab_build.sh with the switch's -D.
 set -e
 cd "$(dirname "$0")/../gnn_computing_amd/csrc"
 make -s -j4

@@ -15,8 +15,8 @@ once, y) plus the E * F * esize bytes of ef; the achieved rate against the in-pr
 Arms alternate inside every round on a non-null stream; a round times `--calls` back-to-back calls of one arm between device events; the
 figure of an arm is the median over `--rounds` rounds, printed with the minimum and maximum of a round.  The edge output is checked against
 the float64 judges of tests/test_attn_edge_host.py on a fixed row sample plus the longest rows.  One JSON line per (call, shape, types);
-nothing is asserted about speed.  `--label` names the library in the record (GNNAGG_LIB selects it: the A/B of the non-temporal ef loads,
--DGNNAGG_EDGE_NT=1, is two builds run alternately in one session).
+nothing is asserted about speed.  `--label` names the library in the record (GNNAGG_LIB selects it: the A/B of the non-temporal ef loads
+was two builds run alternately in one session; the switch that built the plain-load arm is in scripts/attic/ab_switches_retired.patch).
 
     python scripts/bench_attn_edge.py [--rounds 9] [--calls 20] [--dataset arxiv] [--label main]"""
 import argparse
