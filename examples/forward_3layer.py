@@ -102,6 +102,7 @@ class Model:
             gen = torch.Generator().manual_seed(seed + 2)
             self.edge_attr = torch.randn(self.num_e, self.edge_dim, generator=gen).to(dev).to(dtype)
             self.w_edge = [(torch.randn(self.edge_dim, DIMS[k + 1], generator=gen) / self.edge_dim ** 0.5).to(dev).to(dtype) for k in range(3)]
+        self.w_pna = None                                     # model "our_PNA": drawn on its first forward (init_pna)
         self.trace = None                                     # set to a list to record every layer's intermediates
 
     def gcn_layer(self, feat, out, w):                        # our.py:171-176
@@ -178,9 +179,27 @@ class Model:
             self.trace.append(dict(feat=feat, w=self.w_qkv[k], heads=self.heads, qkv=qkv, bias=self.edge_bias, ef=ef, out=out.clone()))
         return out
 
+    def init_pna(self, seed=126):
+        """model "our_PNA": a layer is relu(dense(cat[x, multi(x)], W)) with multi = Aggregator_GCN.run_multi -- mean, min, max and std of the
+        neighbourhood from one gather (the aggregation stage of PNAConv, identity scaler).  The weights [5 * in, out] come from a generator
+        of their own, on the model's first PNA forward: every other tensor keeps its values, and the constructor its signature"""
+        dev, gen = self.h.device, torch.Generator().manual_seed(seed)
+        self.w_pna = [(torch.randn(5 * DIMS[k], DIMS[k + 1], generator=gen) / (5 * DIMS[k]) ** 0.5).to(dev).to(self.dtype) for k in range(3)]
+        self.multi = [torch.empty(self.num_v, 4 * DIMS[k], device=dev, dtype=self.dtype) for k in range(3)]
+
+    def pna_layer(self, feat, k):
+        self.at.run_multi(feat, self.multi[k])
+        cat = torch.cat([feat, self.multi[k]], 1)
+        res = F.relu(self.dense(cat, self.w_pna[k]))
+        if self.trace is not None:
+            self.trace.append(dict(feat=feat, w=self.w_pna[k], multi=self.multi[k].clone(), cat=cat, out=res.clone()))
+        return res
+
     def forward(self, model="our_GCN"):
         if self.fused_nn and model == "our_GCN":
             return self.forward_gcn_fused_nn()
+        if model == "our_PNA" and self.w_pna is None:
+            self.init_pna()
         x = self.h
         for k in range(3):
             if model == "our_GCN":
@@ -189,6 +208,8 @@ class Model:
                 x = self.gatv2_layer(x, self.outs[k], k)
             elif model == "our_Transformer":
                 x = self.transformer_layer(x, self.outs[k], k)
+            elif model == "our_PNA":
+                x = self.pna_layer(x, k)
             elif self.fused_project:
                 x = self.gat_layer_project(x, self.outs[k], k)
             else:
@@ -198,8 +219,10 @@ class Model:
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT", "our_GATv2", "our_Transformer"],
-                    help="our_GATv2: GATv2 attention (Aggregator_GAT.run_v2) on the projected features; our_Transformer: one [Wq | Wk | Wv] "
+    ap.add_argument("--model", default="our_GCN", choices=["our_GCN", "our_GAT", "our_GATv2", "our_Transformer", "our_PNA"],
+                    help="our_PNA: relu(dense(cat[x, mean | min | max | std of the neighbourhood], W)) with the four reductions from one gather "
+                         "(Aggregator_GCN.run_multi), honours --dtype and --hip-graph; "
+                         "our_GATv2: GATv2 attention (Aggregator_GAT.run_v2) on the projected features; our_Transformer: one [Wq | Wk | Wv] "
                          "projection and scaled dot-product attention on its column views (Aggregator_GAT.run_dot); both honour --dtype, "
                          "--heads, --hip-graph")
     ap.add_argument("--dataset", default="arxiv")

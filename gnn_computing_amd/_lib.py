@@ -16,6 +16,8 @@ MODE_ROWS, MODE_SCHEDULED, MODE_BALANCED = 0, 1, 2
 FLAG_ACCUMULATE = 1
 FLAG_RELU = 2
 DTYPE_F32, DTYPE_BF16 = 0, 1
+AGGR_SUM, AGGR_MEAN, AGGR_MIN, AGGR_MAX, AGGR_VAR, AGGR_STD = 1, 2, 4, 8, 16, 32   # gnnagg_gcn_run_multi
+SCALER_IDENTITY, SCALER_AMPLIFICATION, SCALER_ATTENUATION = 1, 2, 4
 
 c_int, c_float, c_void_p, c_char_p, c_int64 = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p,
                                                 ctypes.c_int64)
@@ -92,6 +94,7 @@ SIGNATURES = {
                                       c_void_p, c_int, c_void_p, c_void_p]),
     "gnnagg_dot_attn_run_edge": (c_int, [c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_int,
                                          c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "gnnagg_gcn_run_multi": (c_int, [c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float]),
     "gnnagg_gat_run_part": (c_int,[c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "gnnagg_gat_run_att": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_float]),
     "gnnagg_gat_run_u_add_v": (c_int, [c_int64, c_void_p, c_void_p]),

@@ -32,6 +32,9 @@ class Schedule(enum.IntEnum):
 
 REDUCE = {"sum": _lib.REDUCE_SUM, "mean": _lib.REDUCE_MEAN, "max": _lib.REDUCE_MAX}
 MODE = {"rows": _lib.MODE_ROWS, "scheduled": _lib.MODE_SCHEDULED, "balanced": _lib.MODE_BALANCED}
+AGGRS = {"sum": _lib.AGGR_SUM, "mean": _lib.AGGR_MEAN, "min": _lib.AGGR_MIN, "max": _lib.AGGR_MAX, "var": _lib.AGGR_VAR,
+         "std": _lib.AGGR_STD}   # gnnagg_gcn_run_multi
+SCALERS = {"identity": _lib.SCALER_IDENTITY, "amplification": _lib.SCALER_AMPLIFICATION, "attenuation": _lib.SCALER_ATTENUATION}
 FEATURE_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16}   # gnnagg_gcn_run_typed / gnnagg_gat_run_typed
 
 
@@ -364,6 +367,39 @@ class Aggregator_GCN(Aggregator):
                                                  _dev_ptr(weight, weight.dtype, "weight"), wt,
                                                  _dev_ptr(transformed, transformed.dtype, "transformed"), tt, feat, n_out,
                                                  _mode(scheduled), REDUCE[reduce], _lib.FLAG_RELU if relu else 0))
+
+    def run_multi(self, vin, vout, aggrs=("mean", "min", "max", "std"), scalers=("identity",), delta=None):
+        """gnnagg_gcn_run_multi (extension; the aggregation stage of PNA / PyG's MultiAggregation): several reductions of the messages
+        val * vin[idx] from one gather, times degree scalers.  vin [n_src, F] float32 or bfloat16; vout [V, S * A * F] float32 or bfloat16
+        (one rounding of the fp32 value), contiguous, with A = len(aggrs) of "sum", "mean", "min", "max", "var", "std" and S =
+        len(scalers) of "identity", "amplification", "attenuation".  Blocks lie scaler-major in the order of the library's bits (the
+        order of the names above), whatever order the names are given in: column (s_pos * A + a_pos) * F + c.  delta (pna_delta(ptr): the
+        training set's mean of log(d + 1)) is needed by the two non-identity scalers.  Rows without edges are +0.  Everything is checked
+        here before the library is reached."""
+        xt, yt = _feat_dtype(vin, "vin"), _feat_dtype(vout, "vout")
+        aggrs = (aggrs,) if isinstance(aggrs, str) else tuple(aggrs)
+        scalers = (scalers,) if isinstance(scalers, str) else tuple(scalers)
+        for names, table, what in ((aggrs, AGGRS, "aggrs"), (scalers, SCALERS, "scalers")):
+            unknown = [n for n in names if n not in table]
+            if unknown or not names or len(set(names)) != len(names):
+                raise ValueError("run_multi: %s must be distinct names of %s, got %r" % (what, sorted(table, key=table.get), names))
+        amask, smask = sum(AGGRS[n] for n in aggrs), sum(SCALERS[n] for n in scalers)
+        if vin.dim() != 2 or vout.dim() != 2:
+            raise ValueError("run_multi: vin must be [n_src, F] and vout [V, S * A * F], got %s and %s" % (tuple(vin.shape), tuple(vout.shape)))
+        feat = int(vin.shape[1])
+        if feat < 1:
+            raise ValueError("run_multi: vin has no columns")
+        want = (self.num_v, len(scalers) * len(aggrs) * feat)
+        if tuple(vout.shape) != want:
+            raise ValueError("run_multi: vout must be [V = %d, S * A * F = %d * %d * %d], got %s" % (want[0], len(scalers), len(aggrs), feat, tuple(vout.shape)))
+        if smask != _lib.SCALER_IDENTITY:
+            if delta is None:
+                raise ValueError("run_multi: the amplification and attenuation scalers need delta (pna_delta(ptr))")
+            if not (math.isfinite(float(delta)) and float(delta) > 0.0):
+                raise ValueError("run_multi: delta = %r must be finite and > 0" % (delta,))
+        self._use_current_stream()
+        check(lib().gnnagg_gcn_run_multi(self._h, _dev_ptr(vin, vin.dtype, "vin"), xt, _dev_ptr(vout, vout.dtype, "vout"), yt, feat, amask,
+                                         smask, ctypes.c_float(1.0 if delta is None else float(delta))))
 
     def last_nn_path(self):
         """gnnagg_last_nn_path: 0 no run_with_nn / run_with_nn_typed call on this aggregator yet, 1 the product ran as the epilogue of the
@@ -790,6 +826,21 @@ def gcn_update_val(at, val):
 def gcn_run(at, feat, outfeat, blocksize, scheduled, relu=False):
     """Figure7/kernel.cpp:97-106; relu=True fuses the F.relu that follows it in our.py:176 (extension)."""
     at.run_with_feat(feat, outfeat, blocksize, scheduled, int(feat.shape[1]), relu=relu)
+
+
+def gcn_run_multi(at, feat, outfeat, aggrs=("mean", "min", "max", "std"), scalers=("identity",), delta=None):
+    """Aggregator_GCN.run_multi as a flat function (extension: the reference has one reduction per launch)."""
+    return at.run_multi(feat, outfeat, aggrs=aggrs, scalers=scalers, delta=delta)
+
+
+def pna_delta(ptr):
+    """PNA's delta of a graph: the mean over its rows of log(d + 1), d the row's degree (float64 on the host; ptr: the CSR offsets as a
+    tensor, array or sequence).  A graph without rows gives 1.0."""
+    p = ptr.detach().cpu().numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr)
+    if p.ndim != 1 or p.size < 1:
+        raise ValueError("pna_delta: ptr must be the 1-D CSR offsets [V + 1]")
+    d = np.diff(p.astype(np.int64))
+    return float(np.log(d.astype(np.float64) + 1.0).mean()) if d.size else 1.0
 
 
 def gcn_schedule(at, neighbor_num):

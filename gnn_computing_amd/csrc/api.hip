@@ -2231,6 +2231,48 @@ int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch
                              d_bias, bias_heads, d_alpha || d_stat, d_alpha, d_stat, true, d_ef, ef_pitch);
 }
 
+// Multi-aggregation on a GCN handle (agg_multi.hip).  The list of long rows is the attention calls' (gatv2_build_plan reads ptr alone; a
+// GCN handle has no other use for it), and so is the scratch, sized here by this kernel's slots.
+int gnnagg_gcn_run_multi(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int aggr_mask, int scaler_mask,
+                         float delta)
+{
+    if (int rc = edge_call_without_device(h)) return rc;
+    GET_CTX(h);
+    const std::string fn("gnnagg_gcn_run_multi");
+    auto known = [](int t) { return t == GNNAGG_DTYPE_F32 || t == GNNAGG_DTYPE_BF16; };
+    constexpr int all_aggr = GNNAGG_AGGR_SUM | GNNAGG_AGGR_MEAN | GNNAGG_AGGR_MIN | GNNAGG_AGGR_MAX | GNNAGG_AGGR_VAR | GNNAGG_AGGR_STD;
+    constexpr int all_scalers = GNNAGG_SCALER_IDENTITY | GNNAGG_SCALER_AMPLIFICATION | GNNAGG_SCALER_ATTENUATION;
+    if (c->kind != Ctx::GCN) return fail(GNNAGG_ERR_ARG, fn + ": handle is not a GCN aggregator");
+    if (!d_x || !d_y) return fail(GNNAGG_ERR_ARG, fn + ": null pointer (" + (!d_x ? "d_x" : "d_y") + ")");
+    if (!known(x_dtype) || !known(y_dtype))
+        return fail(GNNAGG_ERR_ARG, fn + ": unknown dtype code (x_dtype " + std::to_string(x_dtype) + ", y_dtype " + std::to_string(y_dtype) +
+                                        "): GNNAGG_DTYPE_F32 (0) or GNNAGG_DTYPE_BF16 (1)");
+    if (feat < 1) return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + ": needs feat >= 1");
+    if (feat > kGatv2MaxFeat)
+        return fail(GNNAGG_ERR_ARG, fn + ": feat = " + std::to_string(feat) + " is above the kernel's limit of " + std::to_string(kGatv2MaxFeat) +
+                                        " columns");
+    if (aggr_mask == 0 || (aggr_mask & ~all_aggr))
+        return fail(GNNAGG_ERR_ARG, fn + ": aggr_mask = " + std::to_string(aggr_mask) + ": needs at least one and only GNNAGG_AGGR_* bits (1 .. " +
+                                        std::to_string(all_aggr) + ")");
+    if (scaler_mask == 0 || (scaler_mask & ~all_scalers))
+        return fail(GNNAGG_ERR_ARG, fn + ": scaler_mask = " + std::to_string(scaler_mask) + ": needs at least one and only GNNAGG_SCALER_* bits (1 .. " +
+                                        std::to_string(all_scalers) + ")");
+    if ((scaler_mask & ~GNNAGG_SCALER_IDENTITY) && !(std::isfinite(delta) && delta > 0.0f))
+        return fail(GNNAGG_ERR_ARG, fn + ": delta = " + std::to_string(delta) + ": the amplification and attenuation scalers need a finite delta > 0");
+    if (c->V == 0) return GNNAGG_OK;
+    Ctx::Gatv2Plan &p = c->gatv2;
+    if (!p.valid)
+        if (int rc = gatv2_build_plan(c)) return rc;
+    if (p.n_slots > 0)
+        if (int rc = p.scratch.reserve((size_t)p.n_slots * multi_aggr_slot_floats(feat, x_dtype))) return rc;
+    MultiAggrLaunch L;
+    L.ptr = c->d_ptr; L.idx = c->d_idx; L.val = c->d_val;
+    L.seg = p.seg.p; L.mrow = p.mrow.p; L.n_seg = p.n_seg; L.n_mrows = p.n_mrows; L.scratch = p.scratch.p;
+    L.x = d_x; L.y = d_y; L.x_dtype = x_dtype; L.y_dtype = y_dtype; L.V = c->V; L.feat = feat;
+    L.aggr_mask = aggr_mask; L.scaler_mask = scaler_mask; L.delta = delta;
+    return launch_multi_aggr(L, c->stream);
+}
+
 int gnnagg_gat_run_part(gnnagg_handle h, const float *d_x, const float *d_att, float *d_y, int feat, int heads, float slope, int part,
                         float *d_den_io)
 {

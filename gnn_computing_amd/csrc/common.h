@@ -298,6 +298,24 @@ struct DotAttnLaunch : AttnLaunch {
     float scale = 1.0f;
 };
 int launch_dot_attn(const DotAttnLaunch &a, void *stream);
+// Multi-aggregation (agg_multi.hip, gnnagg_gcn_run_multi): sum / mean / min / max / var / std of a row's messages val * x[idx] from one
+// gather, on the attention frame -- the same segments and multi-segment rows (seg, mrow: gatv2_build_plan), a scratch slot of
+// multi_aggr_slot_floats(feat, x_dtype) floats per segment of a multi-segment row.  y is dense [V, S * A * feat].
+struct MultiAggrLaunch {
+    const int *ptr = nullptr, *idx = nullptr;
+    const float *val = nullptr;                // nullptr => the message is x[idx[p]] itself
+    const void *seg = nullptr, *mrow = nullptr;
+    int n_seg = 0, n_mrows = 0;
+    const void *x = nullptr;                   // dense [n_src, feat], elements of x_dtype
+    void *y = nullptr;                         // elements of y_dtype
+    float *scratch = nullptr;
+    int x_dtype = GNNAGG_DTYPE_F32, y_dtype = GNNAGG_DTYPE_F32;
+    int V = 0, feat = 0;
+    int aggr_mask = 0, scaler_mask = GNNAGG_SCALER_IDENTITY;   // GNNAGG_AGGR_* / GNNAGG_SCALER_* bits (validated by the entry point)
+    float delta = 1.0f;
+};
+size_t multi_aggr_slot_floats(int feat, int x_dtype);   // 0: a shape the kernel does not cover
+int launch_multi_aggr(const MultiAggrLaunch &a, void *stream);
 // The finishing pass of the two weights-out calls (aux_kernels.hip): alpha[p, h] = expf(alpha[p, h] - ms) / den in place, with (M, den) =
 // stat[r, h] of the edge's row r (ptr[r] <= p < ptr[r + 1]) and ms = M, or 0 where M is -inf.  Edge-parallel (a wavefront per 64 consecutive edges, one bisection over ptr per edge), any row length.
 int launch_attn_finish(const int *ptr, int V, int E, int heads, float *alpha, const float *stat, void *stream);

@@ -613,6 +613,50 @@ int gnnagg_gatv2_run_edge(gnnagg_handle h, const void *d_xs, const void *d_xd, i
 int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch,
                              const void *d_ef, long long ef_pitch, int x_dtype, void *d_y, int y_dtype, int feat, int heads, float scale,
                              const float *d_bias, int bias_heads, float *d_alpha, float *d_stat);
+/* Multi-aggregation: several reductions of the same neighbourhood from ONE gather, times degree scalers (no reference counterpart; the
+ * aggregation stage of PNA -- PyG's PNAConv and aggr=["mean", "min", "max", "std"] / MultiAggregation, DGL's PNAConv).  On a GCN handle.
+ *   messages     for edge position p of row r (ptr[r] <= p < ptr[r + 1]) the message is m_p[c] = val[p] * x[idx[p], c], ONE fp32 multiply;
+ *                m_p = x[idx[p]] exactly where the handle has no val.  val is read at call time (gnnagg_update_val is honoured).  d_x is
+ *                dense [n_src, feat] of x_dtype (GNNAGG_DTYPE_F32 / GNNAGG_DTYPE_BF16; bf16 is widened exactly).  Column ids may exceed
+ *                num_v (d_x has that many rows).  d_y aliases no input.
+ *   per row      with d = ptr[r + 1] - ptr[r] (the handle's own degree; row_aux is not consulted), per column:
+ *                    S1 = sum_p m_p (a plain fp32 add per edge)   S2 = sum_p m_p * m_p   mn = min_p m_p   mx = max_p m_p
+ *                    sum = S1        mean = S1 / (float)d (one fp32 division)        min = mn        max = mx
+ *                    var = max(S2 / d - mean * mean, 0)  (the two-moment form PyG and DGL compute, clamped: never negative)
+ *                    std = sqrtf(var)
+ *                A row without edges is +0 in every block.
+ *   layout       d_y is dense [num_v, S * A * feat] of y_dtype, A and S the numbers of set bits of aggr_mask and scaler_mask.  Blocks in
+ *                ascending bit order, scaler-major: column (s_pos * A + a_pos) * feat + c -- PyG's cat([out * scaler ...]) order.  A bf16 y
+ *                is ONE round-to-nearest-even of the fp32 value.
+ *   scalers      identity = 1; amplification = logf(d + 1) / delta; attenuation = delta / logf(d + 1): one fp32 scalar per row, multiplied
+ *                into the finished fp32 aggregate once.  delta is the caller's training-set mean of log(d + 1).  The aggregate is computed
+ *                once whatever S is.
+ *   order        for a row of at most 128 edges S1 is the sequential fp32 chain s = s + m_p in CSR order from +0 (reproducible on the host
+ *                with numpy float32).  Longer rows are cut at the attention calls' segment (512 edges) and chunk boundaries and folded in
+ *                ascending order.  No atomics; the same bits on every call.  A block's bits never depend on which other blocks or scalers
+ *                were selected, nor on a pointer's alignment.  min and max are exact for any order.
+ *   error        |sum - ref| <= 1e-5 * sum_p |m_p| against float64, mean within that / d; |var - ref| <= 4e-5 * S2 / d.
+ *   non-finite   +-Inf in x follows plain IEEE through sum, mean, min and max; every row a non-finite value does not reach keeps its bits.
+ *                var and std over non-finite messages, and min and max over NaN, are unspecified (as GNNAGG_REDUCE_MAX).
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, nothing launched, d_y untouched: a handle that is not a GCN aggregator, a
+ *                null pointer, an unknown dtype code, feat < 1, feat > 1024 (the kernel's limit), a mask that is 0 or has unknown bits, a
+ *                non-identity scaler with delta not finite or <= 0.
+ *   streams      on the handle's stream.  The first call builds the list of long rows (one read of ptr, ordered behind the stream) and a
+ *                call allocates only while the handle's scratch for the partials of multi-segment rows is smaller than its (feat, x_dtype)
+ *                needs; any later call of a covered shape allocates and synchronises nothing and can be captured in a HIP graph (one or
+ *                two launches in a line) -- until a call that needs more scratch reallocates it: the capture must then be made again.
+ * (tests/test_gpu_multi_aggr.py, tests/test_multi_aggr_host.py; DESIGN.md "Multi-aggregation") */
+#define GNNAGG_AGGR_SUM 1
+#define GNNAGG_AGGR_MEAN 2
+#define GNNAGG_AGGR_MIN 4
+#define GNNAGG_AGGR_MAX 8
+#define GNNAGG_AGGR_VAR 16
+#define GNNAGG_AGGR_STD 32
+#define GNNAGG_SCALER_IDENTITY 1
+#define GNNAGG_SCALER_AMPLIFICATION 2
+#define GNNAGG_SCALER_ATTENUATION 4
+int gnnagg_gcn_run_multi(gnnagg_handle h, const void *d_x, int x_dtype, void *d_y, int y_dtype, int feat, int aggr_mask, int scaler_mask,
+                         float delta);
 /* The fused GAT aggregation in TWO passes over disjoint edge sets of the same rows (two handles over the same rows: the
  * row-partitioned step's local-source edges, then its halo-source edges once the exchange has landed).  GNNAGG_MODE_BALANCED on
  * the chunked plan; 16-byte aligned rows of at most 256 columns, head widths that are multiples of 4 (a lane's four columns lie in one head).
