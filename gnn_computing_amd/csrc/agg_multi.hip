@@ -109,6 +109,7 @@ __device__ __forceinline__ void multi_walk(const MultiArgs &a, int beg, int end,
 
 // A finished row piece (VEC columns from col) into every selected block of y: the aggregates in ascending bit order, each computed once
 // and multiplied by the row's scalers (one fp32 scalar each; identity stores the aggregate itself).  deg == 0: +0 everywhere.
+// Non-finite messages (gnnagg.h): var and std keep a NaN, min and max of NaN messages alone are NaN, a NaN is stored as the quiet NaN.
 template <int VEC>
 __device__ __forceinline__ void multi_store_row(const MultiArgs &a, int row, int col, int deg, const float (&s1)[VEC], const float (&s2)[VEC],
                                                 const float (&mn)[VEC], const float (&mx)[VEC])
@@ -133,16 +134,21 @@ __device__ __forceinline__ void multi_store_row(const MultiArgs &a, int row, int
             if (deg > 0) {
                 if (t == 0) r = s1[k];
                 else if (t == 1) r = s1[k] / dg;
-                else if (t == 2) r = mn[k];
-                else if (t == 3) r = mx[k];
-                else {
+                else if (t == 2 || t == 3) {
+                    // mn > mx: the seeds, which with deg > 0 only a (row, column) of NaN messages alone keeps (the walk, the folds and the
+                    // merge skip NaN and carry the seeds through) -- NaN, never a value no message had
+                    r = mn[k] > mx[k] ? __builtin_nanf("") : t == 2 ? mn[k] : mx[k];
+                } else {
                     const float mu = s1[k] / dg;
                     const float q = s2[k] / dg;
-                    r = fmaxf(q - mu * mu, 0.0f);   // the two-moment form, clamped: cancellation may leave it below zero
+                    const float d = q - mu * mu;    // the two-moment form, clamped: cancellation may leave it below zero
+                    r = d < 0.0f ? 0.0f : d;        // (not fmaxf, which drops a NaN: an Inf or NaN message is a NaN var and std)
                     if (t == 5) r = sqrtf(r);
                 }
             }
-            v[k] = r;
+            // a NaN is stored as THE quiet NaN: which of two NaN operands an add hands on (the sign and payload of x's NaN, or of the one an
+            // Inf - Inf made) is the compiler's choice per instantiation, and a block's bits depend on no arm
+            v[k] = r != r ? __builtin_nanf("") : r;
         }
         int sp = 0;
         for (int s = 0; s < kMultiScalerBits; ++s) {

@@ -636,8 +636,17 @@ int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch
  *                ascending order.  No atomics; the same bits on every call.  A block's bits never depend on which other blocks or scalers
  *                were selected, nor on a pointer's alignment.  min and max are exact for any order.
  *   error        |sum - ref| <= 1e-5 * sum_p |m_p| against float64, mean within that / d; |var - ref| <= 4e-5 * S2 / d.
- *   non-finite   +-Inf in x follows plain IEEE through sum, mean, min and max; every row a non-finite value does not reach keeps its bits.
- *                var and std over non-finite messages, and min and max over NaN, are unspecified (as GNNAGG_REDUCE_MAX).
+ *   non-finite   three rules, for messages that are +-Inf or NaN (from x, from val, or 0 * Inf formed by the multiply):
+ *                sum, mean, var, std: the class map (finite / +Inf / -Inf / NaN, element for element) of the float64 two-moment formulas
+ *                over the fp32 messages.  var and std are NaN wherever a message of the (row, column) is +-Inf or NaN (the clamp above
+ *                keeps a NaN).  One case stays unspecified: var / std where the fp32 chain S2 overflows although every message is finite
+ *                -- inherent to the two-moment form.
+ *                min, max: NaN messages are SKIPPED (np.fmin.reduce / np.fmax.reduce), +-Inf messages are exact, and a (row, column) whose
+ *                messages are all NaN is NaN, never a value no message had.  This differs from torch.amin / torch.amax (and PyG's min /
+ *                max aggregation), which propagate a NaN.
+ *                Every (row, column) that no non-finite message reaches keeps the bits of the run without it.  A NaN is stored as the
+ *                quiet NaN 0x7fc00000 (a bf16 y: its one rounding) whatever NaN operands met on the way, so what "order" says of a block's
+ *                bits holds here too.
  *   refusals     GNNAGG_ERR_ARG with a text naming the argument, nothing launched, d_y untouched: a handle that is not a GCN aggregator, a
  *                null pointer, an unknown dtype code, feat < 1, feat > 1024 (the kernel's limit), a mask that is 0 or has unknown bits, a
  *                non-identity scaler with delta not finite or <= 0.
@@ -645,7 +654,8 @@ int gnnagg_dot_attn_run_edge(gnnagg_handle h, const void *d_q, long long q_pitch
  *                call allocates only while the handle's scratch for the partials of multi-segment rows is smaller than its (feat, x_dtype)
  *                needs; any later call of a covered shape allocates and synchronises nothing and can be captured in a HIP graph (one or
  *                two launches in a line) -- until a call that needs more scratch reallocates it: the capture must then be made again.
- * (tests/test_gpu_multi_aggr.py, tests/test_multi_aggr_host.py; DESIGN.md "Multi-aggregation") */
+ * (tests/test_gpu_multi_aggr.py, tests/test_multi_aggr_host.py; non-finite: tests/test_gpu_multi_aggr_nonfinite.py,
+ * tests/test_multi_aggr_nonfinite_host.py; shapes, masks and handle history: tests/test_gpu_multi_aggr_shapes.py; DESIGN.md "Multi-aggregation") */
 #define GNNAGG_AGGR_SUM 1
 #define GNNAGG_AGGR_MEAN 2
 #define GNNAGG_AGGR_MIN 4
