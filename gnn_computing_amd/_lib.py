@@ -137,6 +137,14 @@ SIGNATURES = {
     "gnnagg_dist_step_gcn": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gnnagg_dist_step_gat": (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
                                      c_void_p]),
+    # F: neighbour sampling
+    "gnnagg_sampler_create": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int64)]),
+    "gnnagg_sampler_destroy": (c_int, [c_int64]),
+    "gnnagg_sampler_set_stream": (c_int, [c_int64, c_void_p]),
+    "gnnagg_sampler_sample": (c_int, [c_int64, c_void_p, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
+                                      c_void_p, c_void_p]),
+    "gnnagg_sample_block_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p,
+                                         ctypes.c_longlong, c_void_p, c_void_p]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

@@ -8,6 +8,7 @@
 // Results are bit-identical to the reference routines (tests/test_host_graph.py pins them
 // against the oracle and the golden vectors).
 #include "common.h"
+#include "sample_key.h"
 
 #include <sys/stat.h>
 
@@ -393,6 +394,68 @@ int halo_plan(const int *ptr, const int *idx, int V, const int *bounds, int npar
 {
     const int r0 = bounds[rank];
     return halo_plan_slice(ptr + r0, idx + ptr[r0], V, bounds, nparts, rank, lptr, lidx, halo_ids_o, halo_counts, num_halo);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Neighbour sampling on the host (gnnagg.h "Neighbour sampling"): the specification of csrc/sample.hip, bit for bit.  Rows in parallel
+// (the fanout-th smallest key of a row by nth_element, then the kept edges in CSR order), first-appearance relabel serial.
+int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, int num_seeds, int fanout, unsigned long long seed, int *blk_ptr,
+                      int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts)
+{
+    for (int i = 0; i < num_seeds; ++i)
+        if (seeds[i] < 0 || seeds[i] >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a seed is no row of the graph");
+    const uint32_t s = sample_seed_mix(seed);
+    long long total = 0;
+    blk_ptr[0] = 0;
+    for (int i = 0; i < num_seeds; ++i) {
+        const int d = ptr[seeds[i] + 1] - ptr[seeds[i]];
+        total += fanout < 0 ? d : std::min(d, fanout);
+        blk_ptr[i + 1] = (int)total;
+    }
+    counts[0] = (int)total;
+    counts[1] = src_nodes ? num_seeds : V;
+    if (total > cap_e || total >= (1ll << 31)) return GNNAGG_OK;   // blk_ptr and counts[0] say what was needed; nothing else is written
+#pragma omp parallel
+    {
+        std::vector<uint32_t> keys;
+#pragma omp for schedule(dynamic, 64)
+        for (int i = 0; i < num_seeds; ++i) {
+            const int beg = ptr[seeds[i]], d = ptr[seeds[i] + 1] - beg, k = blk_ptr[i + 1] - blk_ptr[i];
+            int q = blk_ptr[i];
+            uint32_t T = 0xFFFFFFFFu;
+            if (k < d) {
+                keys.resize((size_t)d);
+                for (int t = 0; t < d; ++t) keys[t] = sample_key((uint32_t)(beg + t), s);
+                std::nth_element(keys.begin(), keys.begin() + (k - 1), keys.end());
+                T = keys[k - 1];
+            }
+            for (int t = 0; t < d; ++t)
+                if (k == d || sample_key((uint32_t)(beg + t), s) <= T) {
+                    blk_idx[q] = idx[beg + t];
+                    if (blk_eid) blk_eid[q] = beg + t;
+                    ++q;
+                }
+        }
+    }
+    if (src_nodes) {
+        std::vector<int> local((size_t)V, -1);
+        for (int i = 0; i < num_seeds; ++i) {
+            src_nodes[i] = seeds[i];
+            if (local[seeds[i]] < 0) local[seeds[i]] = i;
+        }
+        int n_src = num_seeds;
+        for (long long q = 0; q < total; ++q) {
+            const int v = blk_idx[q];
+            if (v < 0 || v >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a neighbour id is no row of the graph");
+            if (local[v] < 0) {
+                local[v] = n_src;
+                src_nodes[n_src++] = v;
+            }
+            blk_idx[q] = local[v];
+        }
+        counts[1] = n_src;
+    }
+    return GNNAGG_OK;
 }
 
 }  // namespace gnnagg

@@ -1,0 +1,591 @@
+// sample.hip -- neighbour sampling on the device (include/gnnagg.h, section "Neighbour sampling"): seeds + fanout -> a message-flow block.
+//
+// A seed row r with d edges at positions p in [ptr[r], ptr[r+1]) keeps all of them (fanout = -1 or d <= fanout) or the `fanout` edges with
+// the smallest key(seed, p); kept edges stay in CSR order.  key is a bijection of p for a fixed seed (sample_key.h), so the fanout-th
+// smallest key T of a row is unique and "key <= T" names the kept set: a SELECT of one threshold per row, then one ordered emission.
+//
+//   k_sample_counts   min(d, fanout) per seed                                  -> prims::scan -> blk_ptr
+//   k_sample_select   a wavefront (sixteen per workgroup) takes 64 consecutive seeds; rows that keep everything and have <= 64 edges are copied by 8-lane groups,
+//                     every other row by the whole wavefront: d <= 64 keys in registers, T by a 32-step radix select over ballots (ONE key
+//                     evaluation per edge); d > 64 four passes of 8-bit digit histograms in this wavefront's 1 KB of LDS, then the
+//                     emission in rounds of 64 edges (FIVE key evaluations per edge); rows above kHubEdges edges are queued and walked by
+//                     the whole workgroup, their candidate keys buffered in LDS (TWO evaluations per edge: select_threshold_hub).  Output positions are ballot prefix ranks: no
+//                     atomics touch the output, and nothing is loaded but ptr and the kept idx entries.
+//   relabelling       the sampler's num_v-entry map is kUnseen between calls.  Seeds atomicMin (i - num_seeds) < 0, kept edges atomicMin
+//                     their block position >= 0: the lowest seed index / first appearance wins whatever the order of the atomics.  An
+//                     edge whose entry equals its position is a first appearance; a scan of those flags numbers the new source rows; one
+//                     pass relabels and writes src_nodes; a last pass puts kUnseen back at the entries src_nodes names: O(batch).
+//                     (GNNAGG_SAMPLE_RELABEL=sort at creation: a stable sort of (id, position) pairs in its place, the same bits; the
+//                     measurement that chose between them is in DESIGN.md.)  The scans read one buffer and write another.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdlib>
+#include <mutex>
+#include <set>
+
+// prims.cuh as it is (tests/plan_census.py pins its text).  Its scan is a template; its two sort kernels are plain __global__ functions of a
+// header that plan_gpu.hip includes as well, so this translation unit gives its (unused) copies names of their own for the linker.
+#define k_sort_hist k_sort_hist_in_sample
+#define k_sort_scatter k_sort_scatter_in_sample
+#include "prims.cuh"
+#undef k_sort_hist
+#undef k_sort_scatter
+#include "sample_key.h"
+
+namespace gnnagg {
+namespace {
+
+constexpr int kUnseen = INT_MAX;     // (a block position is < cap_e <= INT_MAX - 1)
+constexpr int kSelBlock = 1024;      // k_sample_select: sixteen wavefronts of 64 seeds each
+constexpr int kHubEdges = 2048;      // rows above it are walked by the whole workgroup, not by one wavefront
+
+// edges [beg, beg + d) of row r; a row id or a ptr pair that does not lie inside the CSR counts as a row without edges
+__device__ __forceinline__ void row_extent(const int *__restrict__ ptr, int num_v, int num_e, int r, int &beg, int &d)
+{
+    beg = 0;
+    d = 0;
+    if ((unsigned)r < (unsigned)num_v) {
+        const int b = ptr[r], e = ptr[r + 1];
+        if (b >= 0 && e >= b && e <= num_e) { beg = b; d = e - b; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sample_counts(const int *__restrict__ ptr, int num_v, int num_e, const int *__restrict__ seeds, int num_seeds,
+                                                       int fanout, int *__restrict__ cnt /* [num_seeds + 1] */)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > num_seeds) return;
+    int c = 0;
+    if (i < num_seeds) {
+        int beg, d;
+        row_extent(ptr, num_v, num_e, seeds[i], beg, d);
+        c = fanout < 0 ? d : (d < fanout ? d : fanout);
+    }
+    cnt[i] = c;
+}
+
+// LDS traffic of ONE wavefront (its own histogram): orders the wavefront's LDS atomics and loads for the compiler; the hardware runs a
+// wavefront's LDS instructions in order
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int wave_bcast(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src, 64)); }
+
+struct SampleOut {
+    int *idx;         // [cap]
+    int *eid;         // nullptr or [cap]
+    long long cap;
+};
+
+__device__ __forceinline__ void emit(const SampleOut &o, const int *__restrict__ idx, long long q, int p)
+{
+    if (q >= 0 && q < o.cap) {   // (q < 0: a total past 2^31 wrapped -- nothing is written)
+        o.idx[q] = idx[p];
+        if (o.eid) o.eid[q] = p;
+    }
+}
+
+// the digit whose bin holds the k-th smallest of the keys counted in hist[256] (1 <= k <= their number); k becomes the rank inside that bin.
+// Every wavefront that calls it reads the same bins and comes to the same answer.
+__device__ __forceinline__ int pick_digit(const int *hist, int lane, int &k)
+{
+    int h[4], sum = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { h[b] = hist[lane * 4 + b]; sum += h[b]; }
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    const int excl = incl - sum;
+    const unsigned long long hit = __ballot(excl < k && k <= incl);   // exactly one lane
+    const int src = __ffsll((long long)hit) - 1;
+    int digit = lane * 4, c = excl, knew = k;
+    bool found = false;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        if (!found && k <= c + h[b]) { digit = lane * 4 + b; knew = k - c; found = true; }
+        c += h[b];
+    }
+    k = wave_bcast(knew, src);
+    return wave_bcast(digit, src);
+}
+
+// the k-th smallest (k >= 1) of the keys of positions [beg, beg + d): four passes of 8-bit digit histograms, most significant digit first.
+// BLOCK = false: one wavefront and its own histogram; BLOCK = true: the whole workgroup on one shared histogram (every wavefront reads the
+// same bins and comes to the same digit).  `tid` is the thread's index in the group of `GROUP` threads that walks the row.
+template <bool BLOCK>
+__device__ unsigned select_threshold_lds(int beg, int d, int k, unsigned s, int *hist /* [256] */, int tid, int lane)
+{
+    constexpr unsigned GROUP = BLOCK ? kSelBlock : 64;
+    unsigned prefix = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (tid < 64) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) hist[tid * 4 + b] = 0;
+        }
+        if (BLOCK) __syncthreads(); else wave_lds_sync();
+        for (unsigned t = (unsigned)tid; t < (unsigned)d; t += GROUP) {
+            const unsigned key = sample_key((unsigned)beg + t, s);
+            if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+        }
+        if (BLOCK) __syncthreads(); else wave_lds_sync();
+        const int digit = pick_digit(hist, lane, k);
+        prefix = (prefix << 8) | (unsigned)digit;
+        if (BLOCK) __syncthreads(); else wave_lds_sync();
+    }
+    return prefix;
+}
+
+// Hub rows (the whole workgroup): a row much longer than k is walked ONCE for the select.  The keys below 2^(32 - c), c chosen so that
+// 1024 .. 2047 of them are expected, are buffered in LDS (their order there does not matter: only the k-th smallest is taken from them), and
+// the radix select runs over the buffer.  Fewer than k candidates, or more than the buffer holds: the four walks of select_threshold_lds.
+constexpr int kCand = (kSelBlock / 64) * 256;   // the wavefronts' own histograms, idle by then, are the buffer
+__device__ unsigned select_threshold_hub(int beg, int d, int k, unsigned s, int *hist /* shared [256] */, int *buf /* shared [kCand] */, int *cand_n,
+                                         int tid, int lane)
+{
+    int c = 1;
+    while (c < 24 && (d >> (c + 1)) >= 1024) ++c;
+    if (tid == 0) *cand_n = 0;
+    __syncthreads();
+    for (unsigned t = (unsigned)tid; t < (unsigned)d; t += kSelBlock) {
+        const unsigned key = sample_key((unsigned)beg + t, s);
+        if ((key >> (32 - c)) == 0u) {
+            const int pos = atomicAdd(cand_n, 1);
+            if (pos < kCand) buf[pos] = (int)key;
+        }
+    }
+    __syncthreads();
+    const int n = *cand_n;
+    __syncthreads();
+    if (n < k || n > kCand) return select_threshold_lds<true>(beg, d, k, s, hist, tid, lane);   // (the same for every thread)
+    unsigned prefix = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (tid < 64) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) hist[tid * 4 + b] = 0;
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += kSelBlock) {
+            const unsigned key = (unsigned)buf[j];
+            if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        const int digit = pick_digit(hist, lane, k);
+        prefix = (prefix << 8) | (unsigned)digit;
+        __syncthreads();
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restrict__ ptr, const int *__restrict__ idx, int num_v, int num_e,
+                                                             const int *__restrict__ seeds, int num_seeds, unsigned s,
+                                                             const int *__restrict__ blk_ptr, SampleOut out)
+{
+    constexpr int kWaves = kSelBlock / 64;
+    __shared__ int hist_all[kWaves][256];
+    __shared__ int hub_hist[256], hub_list[kSelBlock], hub_n, cand_n, wcount[kWaves];
+    __shared__ int s_beg[kSelBlock], s_d[kSelBlock], s_out0[kSelBlock], s_cnt[kSelBlock];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int *hist = hist_all[wave];
+    if (tid == 0) hub_n = 0;
+    const long long i = (long long)blockIdx.x * kSelBlock + tid;
+    int beg = 0, d = 0, out0 = 0, cnt = 0;
+    if (i < num_seeds) {
+        row_extent(ptr, num_v, num_e, seeds[i], beg, d);
+        out0 = blk_ptr[i];
+        cnt = blk_ptr[i + 1] - out0;
+        if (cnt < 0 || cnt > d) { cnt = 0; d = 0; }   // (a wrapped total: the row is skipped)
+    }
+    s_beg[tid] = beg; s_d[tid] = d; s_out0[tid] = out0; s_cnt[tid] = cnt;
+    __syncthreads();   // (hub_n = 0 is seen by everyone before the first append)
+    const bool small_copy = d > 0 && cnt == d && d <= 64;
+    const bool hub = d > kHubEdges;
+    const bool by_wave = d > 0 && !small_copy && !hub;
+    const unsigned long long m_small = __ballot(small_copy);
+    unsigned long long m_wave = __ballot(by_wave);
+    const unsigned long long m_hub = __ballot(hub);
+    if (m_hub) {   // hub rows wait for the whole workgroup (their order in the list does not reach the output)
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&hub_n, __popcll(m_hub));
+        base = wave_bcast(base, 0);
+        if (hub) hub_list[base + __popcll(m_hub & ((1ull << lane) - 1ull))] = tid;
+    }
+
+    // rows that keep every edge and have at most 64: eight rows at a time, eight lanes each
+    const int sub = lane >> 3, sl = lane & 7;
+    for (int round = 0; round < 8; ++round) {
+        if (((m_small >> (round * 8)) & 0xffull) == 0) continue;
+        const int j = round * 8 + sub;
+        const int b = __shfl(beg, j, 64), dd = __shfl(d, j, 64), o = __shfl(out0, j, 64);
+        if ((m_small >> j) & 1ull)
+            for (int t = sl; t < dd; t += 8) emit(out, idx, (long long)o + t, b + t);
+    }
+
+    // every other row of up to kHubEdges edges: the whole wavefront
+    while (m_wave) {
+        const int j = __ffsll((long long)m_wave) - 1;
+        m_wave &= m_wave - 1;
+        const int b = wave_bcast(beg, j), dd = wave_bcast(d, j), o = wave_bcast(out0, j), k = wave_bcast(cnt, j);
+        if (k == dd) {   // a long row kept whole
+            for (int t = lane; t < dd; t += 64) emit(out, idx, (long long)o + t, b + t);
+            continue;
+        }
+        if (dd <= 64) {   // keys in registers; the k-th smallest bit by bit, most significant first
+            const bool valid = lane < dd;
+            const unsigned key = sample_key((unsigned)(b + lane), s);
+            unsigned long long cand = __ballot(valid);
+            int kk = k;
+            for (int bit = 31; bit >= 0; --bit) {
+                const unsigned long long ones = __ballot((key >> bit) & 1u);
+                const unsigned long long zeros = cand & ~ones;
+                const int c0 = __popcll(zeros);
+                if (kk <= c0) cand = zeros;
+                else { kk -= c0; cand &= ones; }
+            }
+            // cand is the single lane that holds the k-th smallest key
+            const unsigned T = (unsigned)wave_bcast((int)key, __ffsll((long long)cand) - 1);
+            const bool keep = valid && key <= T;
+            const unsigned long long bal = __ballot(keep);
+            if (keep) emit(out, idx, (long long)o + __popcll(bal & ((1ull << lane) - 1ull)), b + lane);
+            continue;
+        }
+        const unsigned T = select_threshold_lds<false>(b, dd, k, s, hist, lane, lane);
+        int run = 0;
+        for (int base = 0; base < dd; base += 64) {   // (k > 64: the emission takes several rounds all the same)
+            const int t = base + lane;
+            const bool keep = t < dd && sample_key((unsigned)(b + t), s) <= T;
+            const unsigned long long bal = __ballot(keep);
+            if (keep) emit(out, idx, (long long)o + run + __popcll(bal & ((1ull << lane) - 1ull)), b + t);
+            run += __popcll(bal);
+        }
+    }
+
+    // hub rows (more than kHubEdges edges): the whole workgroup per row, one after the other
+    __syncthreads();
+    const int n_hub = hub_n;   // (the same for every thread: the loop and its barriers are uniform)
+    for (int h = 0; h < n_hub; ++h) {
+        const int j = hub_list[h];
+        const int b = s_beg[j], dd = s_d[j], o = s_out0[j], k = s_cnt[j];
+        if (k == dd) {
+            for (unsigned t = (unsigned)tid; t < (unsigned)dd; t += kSelBlock) emit(out, idx, (long long)o + t, b + (int)t);
+            continue;
+        }
+        const unsigned T = select_threshold_hub(b, dd, k, s, hub_hist, &hist_all[0][0], &cand_n, tid, lane);
+        int run = 0;
+        for (unsigned base = 0; base < (unsigned)dd; base += kSelBlock) {
+            const unsigned t = base + (unsigned)tid;
+            const bool keep = t < (unsigned)dd && sample_key((unsigned)b + t, s) <= T;
+            const unsigned long long bal = __ballot(keep);
+            if (lane == 0) wcount[wave] = __popcll(bal);
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) {
+                const int c = wcount[w];
+                if (w < wave) before += c;
+                total += c;
+            }
+            if (keep) emit(out, idx, (long long)o + run + before + __popcll(bal & ((1ull << lane) - 1ull)), b + (int)t);
+            run += total;
+            __syncthreads();
+        }
+    }
+}
+
+// ---- relabelling
+__device__ __forceinline__ int kept_edges(const int *__restrict__ blk_ptr, int num_seeds, long long cap)
+{
+    const int total = blk_ptr[num_seeds];
+    return total < 0 ? 0 : (int)(total < cap ? total : cap);
+}
+
+__global__ __launch_bounds__(256) void k_sample_mark_seeds(const int *__restrict__ seeds, int num_seeds, int num_v, int *__restrict__ map,
+                                                           int *__restrict__ src_nodes)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= num_seeds) return;
+    const int r = seeds[i];
+    src_nodes[i] = r;
+    if ((unsigned)r < (unsigned)num_v) atomicMin(&map[r], i - num_seeds);
+}
+
+__global__ __launch_bounds__(256) void k_sample_mark_edges(const int *__restrict__ blk_ptr, int num_seeds, long long cap, const int *__restrict__ blk_idx,
+                                                           int num_v, int *__restrict__ map)
+{
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= kept_edges(blk_ptr, num_seeds, cap)) return;
+    const int v = blk_idx[q];
+    if ((unsigned)v < (unsigned)num_v) atomicMin(&map[v], (int)q);
+}
+
+// flag[q] = 1 where edge q is the first appearance of a row that is no seed; flag[n] = 0 closes the scan
+__global__ __launch_bounds__(256) void k_sample_flags(const int *__restrict__ blk_ptr, int num_seeds, long long cap, const int *__restrict__ blk_idx,
+                                                      int num_v, const int *__restrict__ map, long long n, int *__restrict__ flag)
+{
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q > n) return;
+    int f = 0;
+    if (q < kept_edges(blk_ptr, num_seeds, cap)) {
+        const int v = blk_idx[q];
+        f = (unsigned)v < (unsigned)num_v && map[v] == (int)q;
+    }
+    flag[q] = f;
+}
+
+__global__ __launch_bounds__(256) void k_sample_relabel(const int *__restrict__ blk_ptr, int num_seeds, long long cap, int *__restrict__ blk_idx, int num_v,
+                                                        const int *__restrict__ map, const int *__restrict__ first_rank, int *__restrict__ src_nodes)
+{
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= kept_edges(blk_ptr, num_seeds, cap)) return;
+    const int v = blk_idx[q];
+    int local = -1;   // (an id outside the CSR's rows: an invalid graph)
+    if ((unsigned)v < (unsigned)num_v) {
+        const int m = map[v];
+        if (m < 0) local = m + num_seeds;
+        else {
+            local = num_seeds + first_rank[m];
+            if (m == (int)q) src_nodes[local] = v;
+        }
+    }
+    blk_idx[q] = local;
+}
+
+__global__ __launch_bounds__(256) void k_sample_restore(const int *__restrict__ src_nodes, int num_seeds, const int *__restrict__ first_rank, long long n,
+                                                        int num_v, int *__restrict__ map)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (long long)num_seeds + first_rank[n]) return;
+    const int v = src_nodes[j];
+    if ((unsigned)v < (unsigned)num_v) map[v] = kUnseen;
+}
+
+// ---- relabelling by a sort of (id, position) pairs (GNNAGG_SAMPLE_RELABEL=sort: the form the atomic map was measured against).  Items
+// j < num_seeds are the seeds, item num_seeds + q is block position q; after the STABLE sort by id the head of every group of equal ids is
+// its lowest item: the first seed of that id, else the first appearance.  No map, nothing to restore.
+__global__ __launch_bounds__(256) void k_sample_pairs(const int *__restrict__ seeds, int num_seeds, const int *__restrict__ blk_ptr, long long cap,
+                                                      const int *__restrict__ blk_idx, int num_v, long long m, unsigned *__restrict__ keys,
+                                                      int *__restrict__ vals, int *__restrict__ src_nodes)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    int v = num_v;   // (past the kept edges, or no row of the graph: sorts behind every id)
+    if (j < num_seeds) {
+        v = seeds[j];
+        src_nodes[j] = v;
+    } else if (j - num_seeds < kept_edges(blk_ptr, num_seeds, cap)) v = blk_idx[j - num_seeds];
+    keys[j] = (unsigned)v < (unsigned)num_v ? (unsigned)v : (unsigned)num_v;
+    vals[j] = (int)j;
+}
+
+__global__ __launch_bounds__(256) void k_sample_heads(const unsigned *__restrict__ keys, long long m, int *__restrict__ head)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) head[j] = (j > 0 && keys[j] != keys[j - 1]) ? (int)j : 0;
+}
+
+// first[item] = the lowest item of its id (-1: no id); flag[q] = 1 where block position q is a first appearance of a row that is no seed
+__global__ __launch_bounds__(256) void k_sample_firsts(const unsigned *__restrict__ keys, const int *__restrict__ vals, const int *__restrict__ headidx,
+                                                       long long m, int num_seeds, int num_v, long long n, int *__restrict__ first, int *__restrict__ flag)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j == 0) flag[n] = 0;
+    if (j >= m) return;
+    const int item = vals[j];
+    const int lowest = keys[j] == (unsigned)num_v ? -1 : vals[headidx[j]];
+    first[item] = lowest;
+    if (item >= num_seeds) flag[item - num_seeds] = lowest == item;
+}
+
+__global__ __launch_bounds__(256) void k_sample_relabel_sorted(const int *__restrict__ blk_ptr, int num_seeds, long long cap, int *__restrict__ blk_idx,
+                                                               const int *__restrict__ first, const int *__restrict__ first_rank,
+                                                               int *__restrict__ src_nodes)
+{
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= kept_edges(blk_ptr, num_seeds, cap)) return;
+    const int v = blk_idx[q], lowest = first[num_seeds + q];
+    int local = -1;
+    if (lowest >= 0) {
+        local = lowest < num_seeds ? lowest : num_seeds + first_rank[lowest - num_seeds];
+        if (lowest == num_seeds + q) src_nodes[local] = v;
+    }
+    blk_idx[q] = local;
+}
+
+__global__ void k_sample_finish(const int *__restrict__ blk_ptr, int num_seeds, const int *__restrict__ first_rank, long long n, int num_v,
+                                int *__restrict__ counts)
+{
+    counts[0] = blk_ptr[num_seeds];
+    counts[1] = first_rank ? num_seeds + first_rank[n] : num_v;
+}
+
+__global__ __launch_bounds__(256) void k_sample_fill(int *__restrict__ p, long long n, int v)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+struct Sampler {
+    const int *d_ptr = nullptr, *d_idx = nullptr;
+    int V = 0, E = 0;
+    hipStream_t stream = nullptr;
+    bool relabel_by_sort = false;   // GNNAGG_SAMPLE_RELABEL=sort at creation (a measurement aid: DESIGN.md "Neighbour sampling")
+    DevBuf<int> map, cnt, flag, rank, scan_tmp;
+    DevBuf<int> keys_a, keys_b, vals_a, vals_b, first, sort_counts;   // the sort form only
+};
+
+std::mutex g_sampler_mu;
+std::set<Sampler *> g_samplers;
+
+Sampler *lookup_sampler(gnnagg_sampler h)
+{
+    std::lock_guard<std::mutex> lk(g_sampler_mu);
+    Sampler *s = reinterpret_cast<Sampler *>(h);
+    return g_samplers.count(s) ? s : nullptr;
+}
+
+inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
+
+int sampler_sample(Sampler *c, const int *d_seeds, int num_seeds, int fanout, unsigned long long seed, int *d_blk_ptr, int *d_blk_idx, int *d_blk_eid,
+                   long long cap_e, int *d_src_nodes, int *d_counts)
+{
+    if (num_seeds < 0) return fail(GNNAGG_ERR_ARG, "sample: num_seeds < 0");
+    if (fanout == 0 || fanout < -1) return fail(GNNAGG_ERR_ARG, "sample: fanout must be -1 (every edge) or >= 1");
+    if (cap_e < 0) return fail(GNNAGG_ERR_ARG, "sample: cap_e < 0");
+    if ((long long)num_seeds + cap_e >= (1ll << 31)) return fail(GNNAGG_ERR_ARG, "sample: num_seeds + cap_e must stay below 2^31");
+    if (!d_blk_ptr || !d_counts || (num_seeds > 0 && !d_seeds) || (cap_e > 0 && !d_blk_idx))
+        return fail(GNNAGG_ERR_ARG, "sample: null pointer (d_seeds, d_blk_ptr, d_blk_idx, d_counts)");
+    const bool relabel = d_src_nodes != nullptr;
+    // positions the relabelling passes are launched over (they guard with blk_ptr[num_seeds], read on the device)
+    const long long n = fanout > 0 ? std::min<long long>(cap_e, (long long)num_seeds * fanout) : cap_e;
+    int rc;
+    if ((rc = c->cnt.reserve((size_t)num_seeds + 1))) return rc;
+    if (relabel && ((rc = c->flag.reserve((size_t)n + 1)) || (rc = c->rank.reserve((size_t)n + 1)))) return rc;
+    const long long m = (long long)num_seeds + n;   // items of the sort form
+    if (relabel && c->relabel_by_sort && m > 0)
+        for (DevBuf<int> *b : {&c->keys_a, &c->keys_b, &c->vals_a, &c->vals_b, &c->first})
+            if ((rc = b->reserve((size_t)m))) return rc;
+    hipStream_t st = c->stream;
+    const unsigned s = sample_seed_mix(seed);
+
+    hipLaunchKernelGGL(k_sample_counts, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds, fanout,
+                       c->cnt.p);
+    if ((rc = prims::scan<prims::OpSum, true>(c->cnt.p, d_blk_ptr, (long)num_seeds + 1, c->scan_tmp, st))) return rc;
+    if (num_seeds > 0) {
+        const SampleOut out{d_blk_idx, d_blk_eid, cap_e};
+        hipLaunchKernelGGL(k_sample_select, dim3((unsigned)((num_seeds + kSelBlock - 1) / kSelBlock)), dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s,
+                           d_blk_ptr, out);
+    }
+    if (relabel && c->relabel_by_sort) {
+        if (m > 0) {
+            unsigned *ka = reinterpret_cast<unsigned *>(c->keys_a.p), *kb = reinterpret_cast<unsigned *>(c->keys_b.p);
+            int bits = 1;
+            while (bits < 31 && (1ll << bits) <= c->V) ++bits;   // ids 0 .. V (V: no id) fit
+            hipLaunchKernelGGL(k_sample_pairs, dim3(blocks_of(m)), dim3(256), 0, st, d_seeds, num_seeds, d_blk_ptr, cap_e, d_blk_idx, c->V, m, ka,
+                               c->vals_a.p, d_src_nodes);
+            if ((rc = prims::sort_pairs(ka, kb, c->vals_a.p, c->vals_b.p, (long)m, bits, c->sort_counts, c->scan_tmp, st))) return rc;
+            // (the sort clobbered its inputs: keys_a now holds the head marks, vals_a their running maximum = every item's group head)
+            hipLaunchKernelGGL(k_sample_heads, dim3(blocks_of(m)), dim3(256), 0, st, kb, m, c->keys_a.p);
+            if ((rc = prims::scan<prims::OpMax, false>(c->keys_a.p, c->vals_a.p, (long)m, c->scan_tmp, st))) return rc;
+            hipLaunchKernelGGL(k_sample_firsts, dim3(blocks_of(m)), dim3(256), 0, st, kb, c->vals_b.p, c->vals_a.p, m, num_seeds, c->V, n, c->first.p,
+                               c->flag.p);
+        } else {
+            hipLaunchKernelGGL(k_sample_fill, dim3(1), dim3(256), 0, st, c->flag.p, 1ll, 0);
+        }
+        if ((rc = prims::scan<prims::OpSum, true>(c->flag.p, c->rank.p, (long)n + 1, c->scan_tmp, st))) return rc;
+        if (n > 0)
+            hipLaunchKernelGGL(k_sample_relabel_sorted, dim3(blocks_of(n)), dim3(256), 0, st, d_blk_ptr, num_seeds, cap_e, d_blk_idx, c->first.p, c->rank.p,
+                               d_src_nodes);
+    } else if (relabel) {
+        if (num_seeds > 0)
+            hipLaunchKernelGGL(k_sample_mark_seeds, dim3(blocks_of(num_seeds)), dim3(256), 0, st, d_seeds, num_seeds, c->V, c->map.p, d_src_nodes);
+        if (n > 0)
+            hipLaunchKernelGGL(k_sample_mark_edges, dim3(blocks_of(n)), dim3(256), 0, st, d_blk_ptr, num_seeds, cap_e, d_blk_idx, c->V, c->map.p);
+        hipLaunchKernelGGL(k_sample_flags, dim3(blocks_of(n + 1)), dim3(256), 0, st, d_blk_ptr, num_seeds, cap_e, d_blk_idx, c->V, c->map.p, n, c->flag.p);
+        if ((rc = prims::scan<prims::OpSum, true>(c->flag.p, c->rank.p, (long)n + 1, c->scan_tmp, st))) return rc;
+        if (n > 0)
+            hipLaunchKernelGGL(k_sample_relabel, dim3(blocks_of(n)), dim3(256), 0, st, d_blk_ptr, num_seeds, cap_e, d_blk_idx, c->V, c->map.p, c->rank.p,
+                               d_src_nodes);
+        if (m > 0)
+            hipLaunchKernelGGL(k_sample_restore, dim3(blocks_of(m)), dim3(256), 0, st, d_src_nodes, num_seeds, c->rank.p, n, c->V, c->map.p);
+    }
+    hipLaunchKernelGGL(k_sample_finish, dim3(1), dim3(1), 0, st, d_blk_ptr, num_seeds, relabel ? c->rank.p : nullptr, n, c->V, d_counts);
+    HIP_TRY(hipGetLastError());
+    return GNNAGG_OK;
+}
+
+}  // namespace
+}  // namespace gnnagg
+
+using namespace gnnagg;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int gnnagg_sampler_create(const int *d_ptr, const int *d_idx, int num_v, int num_e, gnnagg_sampler *out)
+{
+    if (!out) return fail(GNNAGG_ERR_ARG, "null output handle");
+    *out = 0;
+    if (num_v < 0 || num_e < 0) return fail(GNNAGG_ERR_ARG, "negative graph size");
+    if (!d_ptr || (num_e > 0 && !d_idx)) return fail(GNNAGG_ERR_ARG, "null CSR pointer");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(GNNAGG_ERR_HIP, "no HIP device available: libgnnagg has no CPU fallback (gnnagg_sample_block_host is the host sampler)");
+    Sampler *c = new Sampler;
+    c->d_ptr = d_ptr; c->d_idx = d_idx; c->V = num_v; c->E = num_e;
+    if (const char *e = getenv("GNNAGG_SAMPLE_RELABEL")) c->relabel_by_sort = std::string(e) == "sort";
+    int rc = c->map.alloc((size_t)num_v);
+    if (!rc && num_v > 0) {
+        hipLaunchKernelGGL(k_sample_fill, dim3(blocks_of(num_v)), dim3(256), 0, nullptr, c->map.p, (long long)num_v, kUnseen);
+        const hipError_t e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) rc = fail(GNNAGG_ERR_HIP, std::string("sampler map: ") + hipGetErrorString(e));
+    }
+    if (rc) { delete c; return rc; }
+    {
+        std::lock_guard<std::mutex> lk(g_sampler_mu);
+        g_samplers.insert(c);
+    }
+    *out = reinterpret_cast<gnnagg_sampler>(c);
+    return GNNAGG_OK;
+}
+
+int gnnagg_sampler_destroy(gnnagg_sampler h)
+{
+    Sampler *c;
+    {
+        std::lock_guard<std::mutex> lk(g_sampler_mu);
+        c = reinterpret_cast<Sampler *>(h);
+        if (!g_samplers.count(c)) return fail(GNNAGG_ERR_ARG, "invalid or destroyed sampler");
+        g_samplers.erase(c);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    delete c;
+    return GNNAGG_OK;
+}
+
+int gnnagg_sampler_set_stream(gnnagg_sampler h, void *hip_stream)
+{
+    Sampler *c = lookup_sampler(h);
+    if (!c) return fail(GNNAGG_ERR_ARG, "invalid or destroyed sampler");
+    c->stream = (hipStream_t)hip_stream;
+    return GNNAGG_OK;
+}
+
+int gnnagg_sampler_sample(gnnagg_sampler h, const int *d_seeds, int num_seeds, int fanout, unsigned long long seed, int *d_blk_ptr, int *d_blk_idx,
+                          int *d_blk_eid, long long cap_e, int *d_src_nodes, int *d_counts)
+{
+    Sampler *c = lookup_sampler(h);
+    if (!c) return fail(GNNAGG_ERR_ARG, "invalid or destroyed sampler");
+    return sampler_sample(c, d_seeds, num_seeds, fanout, seed, d_blk_ptr, d_blk_idx, d_blk_eid, cap_e, d_src_nodes, d_counts);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -849,6 +849,70 @@ int gnnagg_dist_step_gat(gnnagg_dist_step_t step, float *d_x_ext, float *d_att_e
                          float *d_den, float *d_y, int feat, int heads, float slope, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * F. Neighbour sampling: seeds + fanout -> a relabelled CSR block (csrc/sample.hip; the host twin in csrc/host_graph.cpp)
+ * ------------------------------------------------------------------------------------------- */
+/* One call takes a device CSR, a list of seed rows, a fanout and a 64-bit seed and returns a message-flow block: one row per seed, at
+ * most `fanout` neighbours per row drawn uniformly without replacement, neighbours kept in CSR order; optionally relabelled to compact
+ * source ids (seeds first), optionally with the position of every kept edge in the full CSR.  The block is a rectangular CSR: an
+ * aggregator created over (d_blk_ptr, d_blk_idx) gathers from a feature matrix with one row per source id.
+ *
+ * The specification.  Row i of the CSR lists the rows that row i aggregates from.  For a seed row r with the d edges at positions
+ * p in [ptr[r], ptr[r+1]):
+ *   fanout = -1, or d <= fanout   every edge is kept
+ *   d > fanout >= 1               the kept edges are the `fanout` edges with the smallest key(seed, p)
+ *   fanout = 0 or < -1            GNNAGG_ERR_ARG
+ * Kept edges appear in increasing p: a sampled row is a subsequence of the full row.  key depends on the seed and on the edge's position
+ * in the full CSR only -- not on the batch, the row's place in it, the launch geometry or the device -- so row r gets the same sample in
+ * every batch that holds it.  The key is built from murmur3's 32-bit finalizer, all arithmetic uint32 with wrap-around:
+ *   fmix(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ *   s   = fmix(fmix(lo32(seed) + 0x9E3779B9) ^ hi32(seed))          once per call
+ *   key = fmix(fmix(p ^ s) + s)
+ * For a fixed seed this is a bijection of p: two edges never tie and there is no tie rule.  Known answers:
+ *   s(seed = 0) = 0xaa3e5b61   s(seed = 1) = 0x70f6c6d8
+ *   key(1, p = 0) = 0x34d106be   key(1, p = 1) = 0x00486268   key(1, p = 2) = 0x62a55a72   key(1, p = 3) = 0xb34bc796
+ *
+ * Relabelling (d_src_nodes given): src_nodes[i] = seeds[i] for i < num_seeds (x_dst = x_src[:num_seeds], as DGL's to_block); every other
+ * distinct neighbour id follows in the order of its first appearance in the block's edge list; blk_idx holds positions in src_nodes.
+ * Duplicate seeds are allowed: each is a row of its own, and an edge to a duplicated seed is relabelled to its first occurrence.  Without
+ * d_src_nodes, blk_idx holds global ids (the reference's CSRSubGraph with vertexset = the seeds).
+ *
+ * gnnagg_sampler_create borrows the CSR (it must outlive the sampler) and allocates a num_v-entry map that is "unseen" between calls.
+ * gnnagg_sampler_sample:
+ *   d_blk_ptr [num_seeds + 1], d_blk_idx [cap_e], d_blk_eid NULL or [cap_e], d_src_nodes NULL or [num_seeds + cap_e],
+ *   d_counts device int[2]: edges kept, source rows (num_v without relabelling)
+ *   - everything is enqueued on the sampler's stream (gnnagg_sampler_set_stream; the null stream at first); the call makes no host
+ *     synchronisation once the sampler's scratch has its size (it grows with num_seeds and cap_e, never shrinks).  Not capturable into a
+ *     HIP graph: sizes are data-dependent and the caller reads d_counts back.
+ *   - the sampler's map and scratch belong to the handle: calls on ONE sampler must be ordered.  Calls on one stream are; a caller that
+ *     changes the stream between two calls synchronises, or orders the new stream behind the old one with an event, before the second
+ *     call.  Two samplers over the same CSR are independent.
+ *   - data-dependent sizes stay on the device in d_counts and d_blk_ptr[num_seeds]
+ *   - with fanout >= 1, cap_e = num_seeds * fanout always suffices
+ *   - if more edges are kept than cap_e, d_blk_ptr and d_counts[0] are still complete and say what was needed; nothing is written past
+ *     any capacity and the other outputs are unspecified.  The kept edges of one call must stay below 2^31.
+ *   - GNNAGG_ERR_ARG: a null pointer (d_seeds with num_seeds > 0, d_blk_ptr, d_blk_idx with cap_e > 0, d_counts), num_seeds < 0, a bad
+ *     fanout, cap_e < 0, num_seeds + cap_e >= 2^31, a handle that is no live sampler.  A refused call leaves the sampler as it was.
+ *   - num_seeds = 0 is a valid call that writes blk_ptr[0] = 0 and the counts
+ *   - a seed that is no row of the graph is a row without edges (the host twin refuses it: GNNAGG_ERR_ARG)
+ *   - no atomics touch the outputs: the result is a function of the arguments, bit for bit
+ *   - GNNAGG_SAMPLE_RELABEL=sort in the environment when a sampler is created makes it relabel by a stable sort of (id, position) pairs
+ *     in place of the map's integer min-atomics: the same outputs, bit for bit; the form the shipped one was measured against
+ * gnnagg_sample_block_host is the same function of the same arguments on host arrays (OpenMP over the rows, a serial relabel): the
+ * library's CPU path for data-loader workers, usable without a GPU.
+ * The reference's sampleVertex* signatures are out of scope: they expand active flags over the globals n, m and no driver calls them;
+ * the global-id form above is what a later shim would forward to.
+ * (tests/test_sampling_host.py, tests/test_gpu_sampling.py, tests/test_gpu_sampling_forward.py; DESIGN.md "Neighbour sampling") */
+typedef int64_t gnnagg_sampler;
+int gnnagg_sampler_create(const int *d_ptr, const int *d_idx, int num_v, int num_e, gnnagg_sampler *out);
+int gnnagg_sampler_destroy(gnnagg_sampler s);
+int gnnagg_sampler_set_stream(gnnagg_sampler s, void *hip_stream);
+int gnnagg_sampler_sample(gnnagg_sampler s, const int *d_seeds, int num_seeds, int fanout, unsigned long long seed,
+                          int *d_blk_ptr, int *d_blk_idx, int *d_blk_eid, long long cap_e, int *d_src_nodes, int *d_counts);
+int gnnagg_sample_block_host(const int *h_ptr, const int *h_idx, int num_v, const int *h_seeds, int num_seeds, int fanout,
+                             unsigned long long seed, int *h_blk_ptr, int *h_blk_idx, int *h_blk_eid, long long cap_e,
+                             int *h_src_nodes, int *h_counts);
+
+/* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
  * ------------------------------------------------------------------------------------------- */
