@@ -2,7 +2,10 @@
 """Mini-batch GraphSAGE forward (2 layers, mean aggregation) over sampled blocks: sample on the device (gnc.NeighborSampler), gather the
 input rows, and per layer h_dst' = relu(h_dst . W_self + mean_{kept neighbours}(h_src) . W_neigh) with the library's aggregation and GEMM.
 
-    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20]
+    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted]
+
+--weighted draws the neighbours in proportion to a per-edge weight (NeighborSampler(prob=); a third of the edges have weight 0 and are never
+drawn) and aggregates the weighted sum with the kept edges' own weights, full_val[blk.eid].
 
 Prints one JSON line with the per-stage times (medians over the batches, microseconds, each stage closed by a device synchronisation).  A
 block is a new graph, so every batch creates its aggregators: the "aggregate" stage holds handle creation, plan and run."""
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--fanouts", default="15,10", help="input layer first")
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--weighted", action="store_true", help="sample by a per-edge weight and aggregate with it")
     args = ap.parse_args()
     fanouts = tuple(int(f) for f in args.fanouts.split(","))
     assert len(fanouts) == 2, "this example has two layers"
@@ -39,7 +43,12 @@ def main():
     x = torch.randn(num_v, DIMS[0], generator=gen).to(dev)
     w_self = [(torch.randn(DIMS[k], DIMS[k + 1], generator=gen) / DIMS[k] ** 0.5).to(dev) for k in range(2)]
     w_neigh = [(torch.randn(DIMS[k], DIMS[k + 1], generator=gen) / DIMS[k] ** 0.5).to(dev) for k in range(2)]
-    sampler = gnc.NeighborSampler(ptrs, idxs)
+    full_val = None
+    if args.weighted:
+        full_val = torch.exp2(12.0 * torch.rand(idxs.numel(), generator=gen) - 6.0)
+        full_val[torch.rand(idxs.numel(), generator=gen) < 1.0 / 3.0] = 0.0
+        full_val = full_val.to(dev)
+    sampler = gnc.NeighborSampler(ptrs, idxs, prob=full_val)
     perm = torch.randperm(num_v, generator=gen).to(torch.int32).to(dev)
     stages = {"sample": [], "gather": [], "aggregate": [], "dense": []}
 
@@ -55,15 +64,15 @@ def main():
     for b in range(args.batches + 1):            # (batch 0 warms the allocator and the kernels up; its times are dropped)
         seeds = perm[(b * args.batch) % num_v:][:args.batch].contiguous()
         # the sample of a row depends on (seed, row) only: a new seed per batch draws a new sample
-        blocks, t_sample = timed(lambda: sampler.sample_layers(seeds, fanouts, seed=args.seed + 2 * b))
+        blocks, t_sample = timed(lambda: sampler.sample_layers(seeds, fanouts, seed=args.seed + 2 * b, return_eid=args.weighted))
         h, t_gather = timed(lambda: x[blocks[0].src_nodes.long()])
         t_agg = t_dense = 0.0
         for k, blk in enumerate(blocks):
 
             def aggregate():
                 y = torch.empty((blk.num_dst, h.shape[1]), device=dev)
-                agg = blk.gcn()
-                agg.run(h, y, 512, 0, reduce="mean")
+                agg = blk.gcn(full_val[blk.eid.long()].contiguous() if args.weighted else None)
+                agg.run(h, y, 512, 0, reduce="sum" if args.weighted else "mean")
                 return y, agg
 
             (y, agg), dt = timed(aggregate)
@@ -75,7 +84,7 @@ def main():
             for stage, dt in (("sample", t_sample), ("gather", t_gather), ("aggregate", t_agg), ("dense", t_dense)):
                 stages[stage].append(dt)
         out = h
-    rec = {"model": "sage_minibatch", "dataset": args.dataset, "num_v": num_v, "num_e": idxs.numel(), "batch": args.batch, "fanouts": list(fanouts),
+    rec = {"model": "sage_minibatch", "dataset": args.dataset, "num_v": num_v, "num_e": idxs.numel(), "batch": args.batch, "fanouts": list(fanouts), "weighted": args.weighted,
            "batches": args.batches, "last_blocks": [[blk.num_dst, blk.num_src, blk.num_edges] for blk in blocks],
            "finite": bool(torch.isfinite(out).all().item())}
     rec.update({k + "_us": statistics.median(v) for k, v in stages.items()})

@@ -198,5 +198,23 @@ int gnnagg_sample_block_host(const int *h_ptr, const int *h_idx, int num_v, cons
     return sample_block_host(h_ptr, h_idx, num_v, h_seeds, num_seeds, fanout, seed, h_blk_ptr, h_blk_idx, h_blk_eid, cap_e, h_src_nodes, h_counts);
 }
 
+// its weighted form: the same refusals, then the weights (NULL: the call above)
+int gnnagg_sample_block_host_weighted(const int *h_ptr, const int *h_idx, const float *h_w, int num_v, const int *h_seeds, int num_seeds, int fanout,
+                                      unsigned long long seed, int *h_blk_ptr, int *h_blk_idx, int *h_blk_eid, long long cap_e, int *h_src_nodes,
+                                      int *h_counts)
+{
+    if (!h_w)
+        return gnnagg_sample_block_host(h_ptr, h_idx, num_v, h_seeds, num_seeds, fanout, seed, h_blk_ptr, h_blk_idx, h_blk_eid, cap_e, h_src_nodes,
+                                        h_counts);
+    if (num_v < 0 || num_seeds < 0) return fail(GNNAGG_ERR_ARG, "sample_block_host: negative size");
+    if (fanout == 0 || fanout < -1) return fail(GNNAGG_ERR_ARG, "sample_block_host: fanout must be -1 (every edge) or >= 1");
+    if (cap_e < 0) return fail(GNNAGG_ERR_ARG, "sample_block_host: cap_e < 0");
+    if ((long long)num_seeds + cap_e >= (1ll << 31)) return fail(GNNAGG_ERR_ARG, "sample_block_host: num_seeds + cap_e must stay below 2^31");
+    if (!h_ptr || !h_blk_ptr || !h_counts || (num_seeds > 0 && !h_seeds) || (cap_e > 0 && (!h_idx || !h_blk_idx)))
+        return fail(GNNAGG_ERR_ARG, "sample_block_host: null pointer");
+    return sample_block_host_weighted(h_ptr, h_idx, h_w, num_v, h_seeds, num_seeds, fanout, seed, h_blk_ptr, h_blk_idx, h_blk_eid, cap_e, h_src_nodes,
+                                      h_counts);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

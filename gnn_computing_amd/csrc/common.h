@@ -28,6 +28,8 @@ void halo_stage_plan_recv(const long long *recv_rows, int world, int rank, int m
 void halo_stage_plan_send(const long long *send_rows, int world, int rank, int mode, int k, long long *stage_send, int *order);
 int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, int num_seeds, int fanout, unsigned long long seed, int *blk_ptr,
                       int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts);
+int sample_block_host_weighted(const int *ptr, const int *idx, const float *w, int V, const int *seeds, int num_seeds, int fanout,
+                               unsigned long long seed, int *blk_ptr, int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts);
 
 // ---- reorder.cpp
 int cluster_reorder(const int *ptr, const int *idx, int V, double threshold, int num_perm, int cap, uint64_t seed,

@@ -396,6 +396,29 @@ int halo_plan(const int *ptr, const int *idx, int V, const int *bounds, int npar
     return halo_plan_slice(ptr + r0, idx + ptr[r0], V, bounds, nparts, rank, lptr, lidx, halo_ids_o, halo_counts, num_halo);
 }
 
+// the serial first-appearance relabel of a block's `total` kept edges (src_nodes == nullptr: global ids stay)
+static int relabel_block_host(int V, const int *seeds, int num_seeds, long long total, int *blk_idx, int *src_nodes, int *counts)
+{
+    if (!src_nodes) return GNNAGG_OK;
+    std::vector<int> local((size_t)V, -1);
+    for (int i = 0; i < num_seeds; ++i) {
+        src_nodes[i] = seeds[i];
+        if (local[seeds[i]] < 0) local[seeds[i]] = i;
+    }
+    int n_src = num_seeds;
+    for (long long q = 0; q < total; ++q) {
+        const int v = blk_idx[q];
+        if (v < 0 || v >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a neighbour id is no row of the graph");
+        if (local[v] < 0) {
+            local[v] = n_src;
+            src_nodes[n_src++] = v;
+        }
+        blk_idx[q] = local[v];
+    }
+    counts[1] = n_src;
+    return GNNAGG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Neighbour sampling on the host (gnnagg.h "Neighbour sampling"): the specification of csrc/sample.hip, bit for bit.  Rows in parallel
 // (the fanout-th smallest key of a row by nth_element, then the kept edges in CSR order), first-appearance relabel serial.
@@ -437,25 +460,63 @@ int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, i
                 }
         }
     }
-    if (src_nodes) {
-        std::vector<int> local((size_t)V, -1);
-        for (int i = 0; i < num_seeds; ++i) {
-            src_nodes[i] = seeds[i];
-            if (local[seeds[i]] < 0) local[seeds[i]] = i;
-        }
-        int n_src = num_seeds;
-        for (long long q = 0; q < total; ++q) {
-            const int v = blk_idx[q];
-            if (v < 0 || v >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a neighbour id is no row of the graph");
-            if (local[v] < 0) {
-                local[v] = n_src;
-                src_nodes[n_src++] = v;
-            }
-            blk_idx[q] = local[v];
-        }
-        counts[1] = n_src;
+    return relabel_block_host(V, seeds, num_seeds, total, blk_idx, src_nodes, counts);
+}
+
+// The weighted form (gnnagg.h "Weighted sampling"): a row keeps min(d+, fanout) of its d+ eligible edges (w > 0), the ones with the smallest
+// (wkey, p) pairs -- wkey is no bijection, so the position breaks ties.  w == nullptr: the function above.
+int sample_block_host_weighted(const int *ptr, const int *idx, const float *w, int V, const int *seeds, int num_seeds, int fanout,
+                               unsigned long long seed, int *blk_ptr, int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts)
+{
+    if (!w) return sample_block_host(ptr, idx, V, seeds, num_seeds, fanout, seed, blk_ptr, blk_idx, blk_eid, cap_e, src_nodes, counts);
+    for (int i = 0; i < num_seeds; ++i)
+        if (seeds[i] < 0 || seeds[i] >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a seed is no row of the graph");
+    const uint32_t s = sample_seed_mix(seed);
+    blk_ptr[0] = 0;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int i = 0; i < num_seeds; ++i) {
+        int dplus = 0;
+        for (int p = ptr[seeds[i]]; p < ptr[seeds[i] + 1]; ++p) dplus += w[p] > 0.0f;
+        blk_ptr[i + 1] = fanout < 0 ? dplus : std::min(dplus, fanout);   // (the row's count; the running sum follows)
     }
-    return GNNAGG_OK;
+    long long total = 0;
+    for (int i = 0; i < num_seeds; ++i) {
+        total += blk_ptr[i + 1];
+        blk_ptr[i + 1] = (int)total;
+    }
+    counts[0] = (int)total;
+    counts[1] = src_nodes ? num_seeds : V;
+    if (total > cap_e || total >= (1ll << 31)) return GNNAGG_OK;   // blk_ptr and counts[0] say what was needed; nothing else is written
+#pragma omp parallel
+    {
+        std::vector<std::pair<uint32_t, int>> keys;   // (wkey, p) of the eligible edges
+#pragma omp for schedule(dynamic, 64)
+        for (int i = 0; i < num_seeds; ++i) {
+            const int beg = ptr[seeds[i]], end = ptr[seeds[i] + 1], k = blk_ptr[i + 1] - blk_ptr[i];
+            int q = blk_ptr[i];
+            if (k == 0) continue;
+            keys.clear();
+            for (int p = beg; p < end; ++p)
+                if (w[p] > 0.0f) keys.emplace_back(sample_wkey(sample_key((uint32_t)p, s), w[p]), p);
+            if (k < (int)keys.size()) {
+                std::nth_element(keys.begin(), keys.begin() + (k - 1), keys.end());
+                const std::pair<uint32_t, int> T = keys[k - 1];
+                for (int p = beg; p < end; ++p)
+                    if (w[p] > 0.0f && std::make_pair(sample_wkey(sample_key((uint32_t)p, s), w[p]), p) <= T) {
+                        blk_idx[q] = idx[p];
+                        if (blk_eid) blk_eid[q] = p;
+                        ++q;
+                    }
+            } else {
+                for (const auto &kp : keys) {   // every eligible edge, in CSR order
+                    blk_idx[q] = idx[kp.second];
+                    if (blk_eid) blk_eid[q] = kp.second;
+                    ++q;
+                }
+            }
+        }
+    }
+    return relabel_block_host(V, seeds, num_seeds, total, blk_idx, src_nodes, counts);
 }
 
 }  // namespace gnnagg

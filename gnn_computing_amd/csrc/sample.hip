@@ -17,6 +17,9 @@
 //                     pass relabels and writes src_nodes; a last pass puts kUnseen back at the entries src_nodes names: O(batch).
 //                     (GNNAGG_SAMPLE_RELABEL=sort at creation: a stable sort of (id, position) pairs in its place, the same bits; the
 //                     measurement that chose between them is in DESIGN.md.)  The scans read one buffer and write another.
+//   weights           gnnagg_sampler_set_weights: the <true> instantiations of the counts and select kernels.  The key is sample_wkey (the
+//                     bits of E / w, E the integer -log2 of the uniform key; no bijection), a row's count is min(eligible edges, fanout) from a per-row count made
+//                     once per weight vector, and the emission keeps key < T plus the first `quota` edges with key == T in position order.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -51,18 +54,50 @@ __device__ __forceinline__ void row_extent(const int *__restrict__ ptr, int num_
     }
 }
 
+// WEIGHTED: d is the row's number of eligible edges, counted once per weight vector (k_sample_eligible)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_sample_counts(const int *__restrict__ ptr, int num_v, int num_e, const int *__restrict__ seeds, int num_seeds,
-                                                       int fanout, int *__restrict__ cnt /* [num_seeds + 1] */)
+                                                       int fanout, int *__restrict__ cnt /* [num_seeds + 1] */, const int *__restrict__ elig /* [num_v] */)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i > num_seeds) return;
     int c = 0;
     if (i < num_seeds) {
         int beg, d;
-        row_extent(ptr, num_v, num_e, seeds[i], beg, d);
+        if (WEIGHTED) {
+            const int r = seeds[i];
+            d = (unsigned)r < (unsigned)num_v ? elig[r] : 0;
+        } else row_extent(ptr, num_v, num_e, seeds[i], beg, d);
         c = fanout < 0 ? d : (d < fanout ? d : fanout);
     }
     cnt[i] = c;
+}
+
+// ---- the eligible edges of every row, once per weight vector: flags, one scan over the edges, a difference at the row boundaries (a hub
+// row costs what its edges cost anywhere else)
+__global__ __launch_bounds__(256) void k_sample_wflags(const float *__restrict__ w, long long num_e, int *__restrict__ flag /* [num_e + 1] */)
+{
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p <= num_e) flag[p] = p < num_e && w[p] > 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_sample_eligible(const int *__restrict__ ptr, int num_v, int num_e, const int *__restrict__ before /* [num_e + 1] */,
+                                                         int *__restrict__ elig)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= num_v) return;
+    int beg, d;
+    row_extent(ptr, num_v, num_e, r, beg, d);
+    elig[r] = before[beg + d] - before[beg];
+}
+
+// the key the select orders a row by: the uniform key, or the weighted key built from it and the edge's weight
+template <bool WEIGHTED>
+__device__ __forceinline__ unsigned edge_key(unsigned p, unsigned s, const float *__restrict__ w)
+{
+    const unsigned u = sample_key(p, s);
+    if (!WEIGHTED) return u;
+    return sample_wkey(u, w[p]);
 }
 
 // LDS traffic of ONE wavefront (its own histogram): orders the wavefront's LDS atomics and loads for the compiler; the hardware runs a
@@ -119,9 +154,10 @@ __device__ __forceinline__ int pick_digit(const int *hist, int lane, int &k)
 
 // the k-th smallest (k >= 1) of the keys of positions [beg, beg + d): four passes of 8-bit digit histograms, most significant digit first.
 // BLOCK = false: one wavefront and its own histogram; BLOCK = true: the whole workgroup on one shared histogram (every wavefront reads the
-// same bins and comes to the same digit).  `tid` is the thread's index in the group of `GROUP` threads that walks the row.
-template <bool BLOCK>
-__device__ unsigned select_threshold_lds(int beg, int d, int k, unsigned s, int *hist /* [256] */, int tid, int lane)
+// same bins and comes to the same digit).  `tid` is the thread's index in the group of `GROUP` threads that walks the row.  On return k is
+// the rank of the k-th smallest among the keys EQUAL to it: 1 for the uniform keys, the number of tied edges to keep for the weighted ones.
+template <bool BLOCK, bool WEIGHTED>
+__device__ unsigned select_threshold_lds(int beg, int d, int &k, unsigned s, const float *__restrict__ w, int *hist /* [256] */, int tid, int lane)
 {
     constexpr unsigned GROUP = BLOCK ? kSelBlock : 64;
     unsigned prefix = 0;
@@ -133,7 +169,7 @@ __device__ unsigned select_threshold_lds(int beg, int d, int k, unsigned s, int 
         }
         if (BLOCK) __syncthreads(); else wave_lds_sync();
         for (unsigned t = (unsigned)tid; t < (unsigned)d; t += GROUP) {
-            const unsigned key = sample_key((unsigned)beg + t, s);
+            const unsigned key = edge_key<WEIGHTED>((unsigned)beg + t, s, w);
             if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
         }
         if (BLOCK) __syncthreads(); else wave_lds_sync();
@@ -147,6 +183,7 @@ __device__ unsigned select_threshold_lds(int beg, int d, int k, unsigned s, int 
 // Hub rows (the whole workgroup): a row much longer than k is walked ONCE for the select.  The keys below 2^(32 - c), c chosen so that
 // 1024 .. 2047 of them are expected, are buffered in LDS (their order there does not matter: only the k-th smallest is taken from them), and
 // the radix select runs over the buffer.  Fewer than k candidates, or more than the buffer holds: the four walks of select_threshold_lds.
+// (Uniform keys only: the prefilter rests on their distribution.  Weighted hub rows take the four walks.)
 constexpr int kCand = (kSelBlock / 64) * 256;   // the wavefronts' own histograms, idle by then, are the buffer
 __device__ unsigned select_threshold_hub(int beg, int d, int k, unsigned s, int *hist /* shared [256] */, int *buf /* shared [kCand] */, int *cand_n,
                                          int tid, int lane)
@@ -165,7 +202,7 @@ __device__ unsigned select_threshold_hub(int beg, int d, int k, unsigned s, int 
     __syncthreads();
     const int n = *cand_n;
     __syncthreads();
-    if (n < k || n > kCand) return select_threshold_lds<true>(beg, d, k, s, hist, tid, lane);   // (the same for every thread)
+    if (n < k || n > kCand) return select_threshold_lds<true, false>(beg, d, k, s, nullptr, hist, tid, lane);   // (the same for every thread)
     unsigned prefix = 0;
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
@@ -186,9 +223,13 @@ __device__ unsigned select_threshold_hub(int beg, int d, int k, unsigned s, int 
     return prefix;
 }
 
+// WEIGHTED: keys are edge_key<true> (no bijection), a row's count is min(d+, fanout) and may be 0 .. d; the kept edges are the ones with
+// key < T and the first `quota` edges with key == T in position order, quota being what the select leaves of k inside T's bin.  An
+// ineligible edge's key is above every T.  Output position = (keys < T before it) + min(keys == T before it, quota): still ballot ranks.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restrict__ ptr, const int *__restrict__ idx, int num_v, int num_e,
                                                              const int *__restrict__ seeds, int num_seeds, unsigned s,
-                                                             const int *__restrict__ blk_ptr, SampleOut out)
+                                                             const int *__restrict__ blk_ptr, SampleOut out, const float *__restrict__ w)
 {
     constexpr int kWaves = kSelBlock / 64;
     __shared__ int hist_all[kWaves][256];
@@ -208,8 +249,9 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
     s_beg[tid] = beg; s_d[tid] = d; s_out0[tid] = out0; s_cnt[tid] = cnt;
     __syncthreads();   // (hub_n = 0 is seen by everyone before the first append)
     const bool small_copy = d > 0 && cnt == d && d <= 64;
-    const bool hub = d > kHubEdges;
-    const bool by_wave = d > 0 && !small_copy && !hub;
+    const bool some = !WEIGHTED || cnt > 0;   // (a weighted row may keep nothing)
+    const bool hub = d > kHubEdges && some;
+    const bool by_wave = d > 0 && !small_copy && !(d > kHubEdges) && some;
     const unsigned long long m_small = __ballot(small_copy);
     unsigned long long m_wave = __ballot(by_wave);
     const unsigned long long m_hub = __ballot(hub);
@@ -241,7 +283,9 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
         }
         if (dd <= 64) {   // keys in registers; the k-th smallest bit by bit, most significant first
             const bool valid = lane < dd;
-            const unsigned key = sample_key((unsigned)(b + lane), s);
+            unsigned key;
+            if (WEIGHTED) key = valid ? edge_key<true>((unsigned)(b + lane), s, w) : kSampleIneligible;   // (no weight is read past the row)
+            else key = sample_key((unsigned)(b + lane), s);
             unsigned long long cand = __ballot(valid);
             int kk = k;
             for (int bit = 31; bit >= 0; --bit) {
@@ -251,21 +295,37 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
                 if (kk <= c0) cand = zeros;
                 else { kk -= c0; cand &= ones; }
             }
-            // cand is the single lane that holds the k-th smallest key
+            // cand is the single lane that holds the k-th smallest key (WEIGHTED: every lane that holds it, kk of them to keep)
             const unsigned T = (unsigned)wave_bcast((int)key, __ffsll((long long)cand) - 1);
-            const bool keep = valid && key <= T;
+            const unsigned long long below = (1ull << lane) - 1ull;
+            bool keep;
+            if (WEIGHTED) keep = valid && (key < T || (((cand >> lane) & 1ull) && __popcll(cand & below) < kk));
+            else keep = valid && key <= T;
             const unsigned long long bal = __ballot(keep);
-            if (keep) emit(out, idx, (long long)o + __popcll(bal & ((1ull << lane) - 1ull)), b + lane);
+            if (keep) emit(out, idx, (long long)o + __popcll(bal & below), b + lane);
             continue;
         }
-        const unsigned T = select_threshold_lds<false>(b, dd, k, s, hist, lane, lane);
-        int run = 0;
+        int quota = k;
+        const unsigned T = select_threshold_lds<false, WEIGHTED>(b, dd, quota, s, w, hist, lane, lane);
+        int run = 0, ties = 0;   // kept edges / (WEIGHTED) edges below T, and edges equal to T, of the rounds before this one
         for (int base = 0; base < dd; base += 64) {   // (k > 64: the emission takes several rounds all the same)
             const int t = base + lane;
-            const bool keep = t < dd && sample_key((unsigned)(b + t), s) <= T;
-            const unsigned long long bal = __ballot(keep);
-            if (keep) emit(out, idx, (long long)o + run + __popcll(bal & ((1ull << lane) - 1ull)), b + t);
-            run += __popcll(bal);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if (WEIGHTED) {
+                const unsigned key = t < dd ? edge_key<true>((unsigned)(b + t), s, w) : kSampleIneligible;
+                // (T is an eligible edge's key, below kSampleIneligible -- unless the weights changed under the sampler: no lane past the row)
+                const unsigned long long lt = __ballot(key < T), eq = __ballot(t < dd && key == T);
+                const int tied = ties + __popcll(eq & below);
+                if (key < T || (((eq >> lane) & 1ull) && tied < quota))
+                    emit(out, idx, (long long)o + run + __popcll(lt & below) + (tied < quota ? tied : quota), b + t);
+                run += __popcll(lt);
+                ties += __popcll(eq);
+            } else {
+                const bool keep = t < dd && sample_key((unsigned)(b + t), s) <= T;
+                const unsigned long long bal = __ballot(keep);
+                if (keep) emit(out, idx, (long long)o + run + __popcll(bal & below), b + t);
+                run += __popcll(bal);
+            }
         }
     }
 
@@ -277,6 +337,33 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
         const int b = s_beg[j], dd = s_d[j], o = s_out0[j], k = s_cnt[j];
         if (k == dd) {
             for (unsigned t = (unsigned)tid; t < (unsigned)dd; t += kSelBlock) emit(out, idx, (long long)o + t, b + (int)t);
+            continue;
+        }
+        if (WEIGHTED) {
+            int quota = k;
+            const unsigned T = select_threshold_lds<true, true>(b, dd, quota, s, w, hub_hist, tid, lane);
+            int run = 0, ties = 0;
+            for (unsigned base = 0; base < (unsigned)dd; base += kSelBlock) {
+                const unsigned t = base + (unsigned)tid;
+                const unsigned long long below = (1ull << lane) - 1ull;
+                const unsigned key = t < (unsigned)dd ? edge_key<true>((unsigned)b + t, s, w) : kSampleIneligible;
+                const unsigned long long lt = __ballot(key < T), eq = __ballot(t < (unsigned)dd && key == T);
+                if (lane == 0) wcount[wave] = __popcll(lt) | (__popcll(eq) << 16);   // (both <= 64 a wavefront, <= 1024 a round)
+                __syncthreads();
+                int before = 0, total = 0;
+#pragma unroll
+                for (int v = 0; v < kWaves; ++v) {
+                    const int c = wcount[v];
+                    if (v < wave) before += c;
+                    total += c;
+                }
+                const int tied = ties + (before >> 16) + __popcll(eq & below);
+                if (key < T || (((eq >> lane) & 1ull) && tied < quota))
+                    emit(out, idx, (long long)o + run + (before & 0xffff) + __popcll(lt & below) + (tied < quota ? tied : quota), b + (int)t);
+                run += total & 0xffff;
+                ties += total >> 16;
+                __syncthreads();
+            }
             continue;
         }
         const unsigned T = select_threshold_hub(b, dd, k, s, hub_hist, &hist_all[0][0], &cand_n, tid, lane);
@@ -439,6 +526,8 @@ struct Sampler {
     hipStream_t stream = nullptr;
     bool relabel_by_sort = false;   // GNNAGG_SAMPLE_RELABEL=sort at creation (a measurement aid: DESIGN.md "Neighbour sampling")
     DevBuf<int> map, cnt, flag, rank, scan_tmp;
+    const float *d_w = nullptr;     // gnnagg_sampler_set_weights: borrowed [E], nullptr = uniform sampling
+    DevBuf<int> elig;               // [V] eligible edges (w > 0) of every row, of d_w
     DevBuf<int> keys_a, keys_b, vals_a, vals_b, first, sort_counts;   // the sort form only
 };
 
@@ -476,13 +565,22 @@ int sampler_sample(Sampler *c, const int *d_seeds, int num_seeds, int fanout, un
     hipStream_t st = c->stream;
     const unsigned s = sample_seed_mix(seed);
 
-    hipLaunchKernelGGL(k_sample_counts, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds, fanout,
-                       c->cnt.p);
+    if (c->d_w)
+        hipLaunchKernelGGL(k_sample_counts<true>, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds,
+                           fanout, c->cnt.p, c->elig.p);
+    else
+        hipLaunchKernelGGL(k_sample_counts<false>, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds,
+                           fanout, c->cnt.p, nullptr);
     if ((rc = prims::scan<prims::OpSum, true>(c->cnt.p, d_blk_ptr, (long)num_seeds + 1, c->scan_tmp, st))) return rc;
     if (num_seeds > 0) {
         const SampleOut out{d_blk_idx, d_blk_eid, cap_e};
-        hipLaunchKernelGGL(k_sample_select, dim3((unsigned)((num_seeds + kSelBlock - 1) / kSelBlock)), dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s,
-                           d_blk_ptr, out);
+        const dim3 grid((unsigned)((num_seeds + kSelBlock - 1) / kSelBlock));
+        if (c->d_w)
+            hipLaunchKernelGGL(k_sample_select<true>, grid, dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s, d_blk_ptr, out,
+                               c->d_w);
+        else
+            hipLaunchKernelGGL(k_sample_select<false>, grid, dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s, d_blk_ptr, out,
+                               nullptr);
     }
     if (relabel && c->relabel_by_sort) {
         if (m > 0) {
@@ -519,6 +617,27 @@ int sampler_sample(Sampler *c, const int *d_seeds, int num_seeds, int fanout, un
     }
     hipLaunchKernelGGL(k_sample_finish, dim3(1), dim3(1), 0, st, d_blk_ptr, num_seeds, relabel ? c->rank.p : nullptr, n, c->V, d_counts);
     HIP_TRY(hipGetLastError());
+    return GNNAGG_OK;
+}
+
+// the eligible count of every row for the weights d_w, on the sampler's stream; the sampler changes only once everything has succeeded
+int sampler_set_weights(Sampler *c, const float *d_w)
+{
+    if (!d_w) {
+        c->d_w = nullptr;   // (elig keeps its room for the next weight vector)
+        return GNNAGG_OK;
+    }
+    DevBuf<int> elig, before, tmp;   // (scratch of num_e + 1 ints, released before the call returns)
+    int rc;
+    if ((rc = elig.alloc((size_t)c->V)) || (rc = before.alloc((size_t)c->E + 1))) return rc;
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_sample_wflags, dim3(blocks_of((long long)c->E + 1)), dim3(256), 0, st, d_w, (long long)c->E, before.p);
+    if ((rc = prims::scan<prims::OpSum, true>(before.p, before.p, (long)c->E + 1, tmp, st))) return rc;
+    if (c->V > 0) hipLaunchKernelGGL(k_sample_eligible, dim3(blocks_of(c->V)), dim3(256), 0, st, c->d_ptr, c->V, c->E, before.p, elig.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the scratch goes away with this scope, and a sample in flight may still read the old counts)
+    c->elig.swap(elig);
+    c->d_w = d_w;
     return GNNAGG_OK;
 }
 
@@ -577,6 +696,13 @@ int gnnagg_sampler_set_stream(gnnagg_sampler h, void *hip_stream)
     if (!c) return fail(GNNAGG_ERR_ARG, "invalid or destroyed sampler");
     c->stream = (hipStream_t)hip_stream;
     return GNNAGG_OK;
+}
+
+int gnnagg_sampler_set_weights(gnnagg_sampler h, const float *d_w)
+{
+    Sampler *c = lookup_sampler(h);
+    if (!c) return fail(GNNAGG_ERR_ARG, "invalid or destroyed sampler");
+    return sampler_set_weights(c, d_w);
 }
 
 int gnnagg_sampler_sample(gnnagg_sampler h, const int *d_seeds, int num_seeds, int fanout, unsigned long long seed, int *d_blk_ptr, int *d_blk_idx,

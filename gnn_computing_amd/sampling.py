@@ -38,15 +38,35 @@ def _check_fanout(fanout):
 
 
 class NeighborSampler:
-    """gnnagg_sampler over a device CSR (int32 tensors, kept alive by this object)."""
+    """gnnagg_sampler over a device CSR (int32 tensors, kept alive by this object).  prob: None (uniform sampling) or one float32 weight
+    per edge of the full CSR (device tensor [num_e], kept alive too): neighbours are drawn without replacement in proportion to it, and an
+    edge whose weight is not > 0 is never kept (set_prob)."""
 
-    def __init__(self, ptr, idx):
+    def __init__(self, ptr, idx, prob=None):
         self.ptr, self.idx = ptr, idx
+        self.prob = None
         self.num_v = int(ptr.numel()) - 1
         self.num_e = int(idx.numel())
         self._h = ctypes.c_int64(0)
         check(lib().gnnagg_sampler_create(_dev_ptr(ptr, torch.int32, "ptr"), _dev_ptr(idx, torch.int32, "idx"), self.num_v, self.num_e,
                                           ctypes.byref(self._h)))
+        if prob is not None:
+            self.set_prob(prob)
+
+    def set_prob(self, prob):
+        """gnnagg_sampler_set_weights: the per-edge weights of every later sample (None: uniform sampling again).  Checked by dtype and
+        size only.  Counts every row's eligible edges once, on torch's current stream, and waits for it."""
+        L = lib()
+        if prob is None:
+            check(L.gnnagg_sampler_set_weights(self._h, None))
+            self.prob = None
+            return
+        p = _dev_ptr(prob, torch.float32, "prob")
+        if prob.dim() != 1 or int(prob.numel()) != self.num_e:
+            raise ValueError("prob must hold one weight per edge: [%d], got %s" % (self.num_e, tuple(prob.shape)))
+        check(L.gnnagg_sampler_set_stream(self._h, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        check(L.gnnagg_sampler_set_weights(self._h, p))   # (a graph without edges: a null pointer, and nothing to weigh)
+        self.prob = prob
 
     def close(self):
         if self._h.value:
@@ -103,8 +123,9 @@ class NeighborSampler:
         return blocks
 
 
-def sample_block_host(ptr, idx, seeds, fanout, seed=0, relabel=True, return_eid=False):
-    """gnnagg_sample_block_host: numpy int32 arrays in, a Block of numpy arrays out -- the device sampler's specification, bit for bit."""
+def sample_block_host(ptr, idx, seeds, fanout, seed=0, relabel=True, return_eid=False, prob=None):
+    """gnnagg_sample_block_host: numpy int32 arrays in, a Block of numpy arrays out -- the device sampler's specification, bit for bit.
+    prob: None or one float32 weight per edge (gnnagg_sample_block_host_weighted)."""
     fanout = _check_fanout(fanout)
     ptr, idx, seeds = (np.ascontiguousarray(a, dtype=np.int32) for a in (ptr, idx, seeds))
     if ptr.ndim != 1 or idx.ndim != 1 or seeds.ndim != 1 or ptr.size < 1:
@@ -119,7 +140,16 @@ def sample_block_host(ptr, idx, seeds, fanout, seed=0, relabel=True, return_eid=
     src = np.empty(max(n + cap, 1), np.int32) if relabel else None
     counts = np.zeros(2, np.int32)
     p = lambda a: None if a is None else a.ctypes.data
-    check(lib().gnnagg_sample_block_host(p(ptr), p(idx), num_v, p(seeds), n, fanout, int(seed) & _U64, p(blk_ptr), p(blk_idx), p(eid), cap, p(src),
-                                         p(counts)))
+    if prob is None:
+        check(lib().gnnagg_sample_block_host(p(ptr), p(idx), num_v, p(seeds), n, fanout, int(seed) & _U64, p(blk_ptr), p(blk_idx), p(eid), cap,
+                                             p(src), p(counts)))
+    else:
+        prob = np.ascontiguousarray(prob, dtype=np.float32)
+        if prob.ndim != 1 or prob.size != idx.size:
+            raise ValueError("prob must hold one weight per edge: [%d], got %s" % (idx.size, prob.shape))
+        if prob.size == 0:
+            prob = np.zeros(1, np.float32)   # (an empty array has no address; no edge reads it)
+        check(lib().gnnagg_sample_block_host_weighted(p(ptr), p(idx), p(prob), num_v, p(seeds), n, fanout, int(seed) & _U64, p(blk_ptr), p(blk_idx),
+                                                      p(eid), cap, p(src), p(counts)))
     num_edges, num_src = int(counts[0]), int(counts[1])
     return Block(blk_ptr, blk_idx[:num_edges], src[:num_src] if relabel else None, eid[:num_edges] if return_eid else None, n, num_src, num_edges)

@@ -901,7 +901,45 @@ int gnnagg_dist_step_gat(gnnagg_dist_step_t step, float *d_x_ext, float *d_att_e
  * library's CPU path for data-loader workers, usable without a GPU.
  * The reference's sampleVertex* signatures are out of scope: they expand active flags over the globals n, m and no driver calls them;
  * the global-id form above is what a later shim would forward to.
- * (tests/test_sampling_host.py, tests/test_gpu_sampling.py, tests/test_gpu_sampling_forward.py; DESIGN.md "Neighbour sampling") */
+ * (tests/test_sampling_host.py, tests/test_gpu_sampling.py, tests/test_gpu_sampling_forward.py; DESIGN.md "Neighbour sampling")
+ *
+ * Weighted sampling.  A sampler may carry one weight per edge, w[p], float32, indexed by the edge's position p in the full CSR like val,
+ * bias and ef (DGL's sample_neighbors(prob=), PyG's NeighborLoader(weight_attr=)): neighbours are drawn without replacement with
+ * probability proportional to w (Efraimidis-Spirakis: the smallest keys -log(u) / w), and an edge of weight zero is never drawn.
+ *   Eligibility   an edge is eligible iff w[p] > 0: true for +Inf; false for 0, -0, negative values and NaN.  An ineligible edge is
+ *                 never kept, at any fanout.
+ *   Rows          a row with d+ eligible edges keeps min(d+, fanout) of them; fanout = -1 keeps every eligible edge.  Kept edges stay
+ *                 in CSR order.  Relabelling, eid, capacities, refusals and streams are as above.
+ *   Key           from the uniform key u = key(seed, p) above, in integer arithmetic and ONE IEEE division:
+ *                   b    = bit length of u                        (0 for u = 0, else 32 - clz(u); 0 ... 32)
+ *                   fr   = low 32 bits of ((2u + 1) << (32 - b))  (the fraction of (2u + 1) / 2^b - 1, Q32)
+ *                   i    = fr >> 24;   r = (fr >> 8) & 0xFFFF
+ *                   lg   = L[i] + (((L[i+1] - L[i]) * r) >> 16)   (64-bit product)
+ *                   E    = ((33 - b) << 26) - lg                  uint32, Q6.26:  -log2((u + 1/2) / 2^32)
+ *                   q    = float32(E) / w[p]                      conversion and division correctly rounded (to nearest), float32;
+ *                                                                 +Inf and denormal quotients are kept as they are
+ *                   wkey = the bit pattern of q as uint32 (q >= 0, so uint32 order is float order); 0xFFFFFFFF for an ineligible edge
+ *                 L[i] = round(2^26 * log2(1 + i/256)), i = 0 ... 256: 257 integer literals in csrc/sample_key.h, the one text the
+ *                 device and the host share.  Every 2^26 * log2(1 + i/256) lies at least 0.0029 from a half-integer, so the literals
+ *                 do not depend on the libm that produced them.  E / 2^26 is within 2.9e-6 of the exact value.
+ *   Selection     the kept edges of a row with d+ > fanout are the `fanout` eligible edges with the smallest wkey.  wkey is no bijection:
+ *                 among equal keys the lower position p wins.
+ *   Nothing else is floating point: no library log or exp, nothing that depends on FMA contraction, no tolerance.  Known answers:
+ *     L[1] = 377457   L[128] = 39256169   L[256] = 67108864
+ *     E(u = 0) = 2214592512   E(u = 0x80000000) = 67108864   E(u = 0xFFFFFFFF) = 3
+ *     wkey(seed = 1, p, w = 1.5), p = 0 ... 3:  0x4cc24fa9  0x4dd18b60  0x4c6ace39  0x4baf60af   (E = 152812522, 659169777, 92329303,
+ *     34480653)
+ *   - constant weights give a valid uniform sample, but NOT the unweighted call's sample: E decreases in u, and quantisation ties go to
+ *     the lower position
+ *   - weights are not scale-invariant bit for bit (2w rounds other quotients than w)
+ *   - +Inf weights all tie at key 0: such a row keeps its first `fanout` +Inf edges in CSR order
+ * gnnagg_sampler_set_weights(s, d_w): d_w [num_e] is borrowed like the CSR; NULL returns the sampler to uniform sampling (it then launches
+ * the kernels it launched before).  The call counts the eligible edges of every row on the sampler's stream (flags, one scan, a
+ * difference at the row boundaries: num_e + 1 ints of scratch, released before it returns) and waits for the count: the per-call work
+ * stays O(1) per seed before the select.  The weights are read again by every sample: whoever changes them in place calls
+ * set_weights again.  GNNAGG_ERR_ARG: a handle that is no live sampler.  A refused or failed call leaves the sampler as it was.
+ * gnnagg_sample_block_host_weighted is gnnagg_sample_block_host with h_w [num_e] (NULL: that function itself).
+ * (tests/sampling_weighted_ref.py, tests/test_sampling_weighted_host.py, tests/test_gpu_sampling_weighted.py) */
 typedef int64_t gnnagg_sampler;
 int gnnagg_sampler_create(const int *d_ptr, const int *d_idx, int num_v, int num_e, gnnagg_sampler *out);
 int gnnagg_sampler_destroy(gnnagg_sampler s);
@@ -911,6 +949,10 @@ int gnnagg_sampler_sample(gnnagg_sampler s, const int *d_seeds, int num_seeds, i
 int gnnagg_sample_block_host(const int *h_ptr, const int *h_idx, int num_v, const int *h_seeds, int num_seeds, int fanout,
                              unsigned long long seed, int *h_blk_ptr, int *h_blk_idx, int *h_blk_eid, long long cap_e,
                              int *h_src_nodes, int *h_counts);
+int gnnagg_sampler_set_weights(gnnagg_sampler s, const float *d_w);
+int gnnagg_sample_block_host_weighted(const int *h_ptr, const int *h_idx, const float *h_w, int num_v, const int *h_seeds, int num_seeds,
+                                      int fanout, unsigned long long seed, int *h_blk_ptr, int *h_blk_idx, int *h_blk_eid,
+                                      long long cap_e, int *h_src_nodes, int *h_counts);
 
 /* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
