@@ -422,22 +422,43 @@ static int relabel_block_host(int V, const int *seeds, int num_seeds, long long 
 // ---------------------------------------------------------------------------------------------
 // Neighbour sampling on the host (gnnagg.h "Neighbour sampling"): the specification of csrc/sample.hip, bit for bit.  Rows in parallel
 // (the fanout-th smallest key of a row by nth_element, then the kept edges in CSR order), first-appearance relabel serial.
-int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, int num_seeds, int fanout, unsigned long long seed, int *blk_ptr,
-                      int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts)
+static int check_seeds_host(const int *seeds, int num_seeds, int V)
 {
     for (int i = 0; i < num_seeds; ++i)
         if (seeds[i] < 0 || seeds[i] >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a seed is no row of the graph");
-    const uint32_t s = sample_seed_mix(seed);
+    return GNNAGG_OK;
+}
+
+// blk_ptr[i + 1] holds row i's count on entry and the running sum on return; counts[] as it stands before the relabel.  false: the block
+// does not fit -- blk_ptr and counts[0] say what was needed, and nothing else is written (true: counts[0] is the total, below 2^31)
+static bool close_block_ptr_host(int *blk_ptr, int num_seeds, long long cap_e, int num_src, int *counts)
+{
     long long total = 0;
     blk_ptr[0] = 0;
     for (int i = 0; i < num_seeds; ++i) {
-        const int d = ptr[seeds[i] + 1] - ptr[seeds[i]];
-        total += fanout < 0 ? d : std::min(d, fanout);
+        total += blk_ptr[i + 1];
         blk_ptr[i + 1] = (int)total;
     }
-    counts[0] = (int)total;
-    counts[1] = src_nodes ? num_seeds : V;
-    if (total > cap_e || total >= (1ll << 31)) return GNNAGG_OK;   // blk_ptr and counts[0] say what was needed; nothing else is written
+    counts[0] = (int)total; counts[1] = num_src;
+    return !(total > cap_e || total >= (1ll << 31));
+}
+
+static inline void emit_edge_host(const int *idx, int p, int *blk_idx, int *blk_eid, int &q)
+{
+    if (blk_eid) blk_eid[q] = p;
+    blk_idx[q++] = idx[p];
+}
+
+int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, int num_seeds, int fanout, unsigned long long seed, int *blk_ptr,
+                      int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts)
+{
+    if (int rc = check_seeds_host(seeds, num_seeds, V)) return rc;
+    const uint32_t s = sample_seed_mix(seed);
+    for (int i = 0; i < num_seeds; ++i) {
+        const int d = ptr[seeds[i] + 1] - ptr[seeds[i]];
+        blk_ptr[i + 1] = fanout < 0 ? d : std::min(d, fanout);
+    }
+    if (!close_block_ptr_host(blk_ptr, num_seeds, cap_e, src_nodes ? num_seeds : V, counts)) return GNNAGG_OK;
 #pragma omp parallel
     {
         std::vector<uint32_t> keys;
@@ -453,14 +474,10 @@ int sample_block_host(const int *ptr, const int *idx, int V, const int *seeds, i
                 T = keys[k - 1];
             }
             for (int t = 0; t < d; ++t)
-                if (k == d || sample_key((uint32_t)(beg + t), s) <= T) {
-                    blk_idx[q] = idx[beg + t];
-                    if (blk_eid) blk_eid[q] = beg + t;
-                    ++q;
-                }
+                if (k == d || sample_key((uint32_t)(beg + t), s) <= T) emit_edge_host(idx, beg + t, blk_idx, blk_eid, q);
         }
     }
-    return relabel_block_host(V, seeds, num_seeds, total, blk_idx, src_nodes, counts);
+    return relabel_block_host(V, seeds, num_seeds, counts[0], blk_idx, src_nodes, counts);
 }
 
 // The weighted form (gnnagg.h "Weighted sampling"): a row keeps min(d+, fanout) of its d+ eligible edges (w > 0), the ones with the smallest
@@ -469,24 +486,15 @@ int sample_block_host_weighted(const int *ptr, const int *idx, const float *w, i
                                unsigned long long seed, int *blk_ptr, int *blk_idx, int *blk_eid, long long cap_e, int *src_nodes, int *counts)
 {
     if (!w) return sample_block_host(ptr, idx, V, seeds, num_seeds, fanout, seed, blk_ptr, blk_idx, blk_eid, cap_e, src_nodes, counts);
-    for (int i = 0; i < num_seeds; ++i)
-        if (seeds[i] < 0 || seeds[i] >= V) return fail(GNNAGG_ERR_ARG, "sample_block_host: a seed is no row of the graph");
+    if (int rc = check_seeds_host(seeds, num_seeds, V)) return rc;
     const uint32_t s = sample_seed_mix(seed);
-    blk_ptr[0] = 0;
 #pragma omp parallel for schedule(dynamic, 64)
     for (int i = 0; i < num_seeds; ++i) {
         int dplus = 0;
         for (int p = ptr[seeds[i]]; p < ptr[seeds[i] + 1]; ++p) dplus += w[p] > 0.0f;
-        blk_ptr[i + 1] = fanout < 0 ? dplus : std::min(dplus, fanout);   // (the row's count; the running sum follows)
+        blk_ptr[i + 1] = fanout < 0 ? dplus : std::min(dplus, fanout);
     }
-    long long total = 0;
-    for (int i = 0; i < num_seeds; ++i) {
-        total += blk_ptr[i + 1];
-        blk_ptr[i + 1] = (int)total;
-    }
-    counts[0] = (int)total;
-    counts[1] = src_nodes ? num_seeds : V;
-    if (total > cap_e || total >= (1ll << 31)) return GNNAGG_OK;   // blk_ptr and counts[0] say what was needed; nothing else is written
+    if (!close_block_ptr_host(blk_ptr, num_seeds, cap_e, src_nodes ? num_seeds : V, counts)) return GNNAGG_OK;
 #pragma omp parallel
     {
         std::vector<std::pair<uint32_t, int>> keys;   // (wkey, p) of the eligible edges
@@ -502,21 +510,13 @@ int sample_block_host_weighted(const int *ptr, const int *idx, const float *w, i
                 std::nth_element(keys.begin(), keys.begin() + (k - 1), keys.end());
                 const std::pair<uint32_t, int> T = keys[k - 1];
                 for (int p = beg; p < end; ++p)
-                    if (w[p] > 0.0f && std::make_pair(sample_wkey(sample_key((uint32_t)p, s), w[p]), p) <= T) {
-                        blk_idx[q] = idx[p];
-                        if (blk_eid) blk_eid[q] = p;
-                        ++q;
-                    }
+                    if (w[p] > 0.0f && std::make_pair(sample_wkey(sample_key((uint32_t)p, s), w[p]), p) <= T) emit_edge_host(idx, p, blk_idx, blk_eid, q);
             } else {
-                for (const auto &kp : keys) {   // every eligible edge, in CSR order
-                    blk_idx[q] = idx[kp.second];
-                    if (blk_eid) blk_eid[q] = kp.second;
-                    ++q;
-                }
+                for (const auto &kp : keys) emit_edge_host(idx, kp.second, blk_idx, blk_eid, q);   // every eligible edge, in CSR order
             }
         }
     }
-    return relabel_block_host(V, seeds, num_seeds, total, blk_idx, src_nodes, counts);
+    return relabel_block_host(V, seeds, num_seeds, counts[0], blk_idx, src_nodes, counts);
 }
 
 }  // namespace gnnagg

@@ -9,21 +9,23 @@
 //                     every other row by the whole wavefront: d <= 64 keys in registers, T by a 32-step radix select over ballots (ONE key
 //                     evaluation per edge); d > 64 four passes of 8-bit digit histograms in this wavefront's 1 KB of LDS, then the
 //                     emission in rounds of 64 edges (FIVE key evaluations per edge); rows above kHubEdges edges are queued and walked by
-//                     the whole workgroup, their candidate keys buffered in LDS (TWO evaluations per edge: select_threshold_hub).  Output positions are ballot prefix ranks: no
-//                     atomics touch the output, and nothing is loaded but ptr and the kept idx entries.
+//                     the whole workgroup, their candidate keys buffered in LDS (TWO evaluations per edge: select_threshold_hub).  The
+//                     four passes are radix_select, whoever walks and wherever the keys come from (a position, or the LDS buffer); the
+//                     emission is emit_row for a wavefront and for the workgroup.  Output positions are ballot prefix ranks: no atomics
+//                     touch the output, and nothing is loaded but ptr and the kept idx entries.
 //   relabelling       the sampler's num_v-entry map is kUnseen between calls.  Seeds atomicMin (i - num_seeds) < 0, kept edges atomicMin
 //                     their block position >= 0: the lowest seed index / first appearance wins whatever the order of the atomics.  An
 //                     edge whose entry equals its position is a first appearance; a scan of those flags numbers the new source rows; one
 //                     pass relabels and writes src_nodes; a last pass puts kUnseen back at the entries src_nodes names: O(batch).
-//                     (GNNAGG_SAMPLE_RELABEL=sort at creation: a stable sort of (id, position) pairs in its place, the same bits; the
-//                     measurement that chose between them is in DESIGN.md.)  The scans read one buffer and write another.
+//                     The scans read one buffer and write another.
 //   weights           gnnagg_sampler_set_weights: the <true> instantiations of the counts and select kernels.  The key is sample_wkey (the
 //                     bits of E / w, E the integer -log2 of the uniform key; no bijection), a row's count is min(eligible edges, fanout) from a per-row count made
-//                     once per weight vector, and the emission keeps key < T plus the first `quota` edges with key == T in position order.
+//                     once per weight vector, and the emission keeps key < T plus the first `quota` edges with key == T in position order
+//                     (the uniform rule, key <= T, is that rule without ties).  A weighted hub row takes the four walks: the candidate
+//                     buffer rests on the distribution of the uniform keys.
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdlib>
 #include <mutex>
 #include <set>
 
@@ -152,12 +154,12 @@ __device__ __forceinline__ int pick_digit(const int *hist, int lane, int &k)
     return wave_bcast(digit, src);
 }
 
-// the k-th smallest (k >= 1) of the keys of positions [beg, beg + d): four passes of 8-bit digit histograms, most significant digit first.
+// the k-th smallest (k >= 1) of the n keys key_at(0 .. n - 1): four passes of 8-bit digit histograms, most significant digit first.
 // BLOCK = false: one wavefront and its own histogram; BLOCK = true: the whole workgroup on one shared histogram (every wavefront reads the
-// same bins and comes to the same digit).  `tid` is the thread's index in the group of `GROUP` threads that walks the row.  On return k is
+// same bins and comes to the same digit).  `tid` is the thread's index in the group of `GROUP` threads that walks the keys.  On return k is
 // the rank of the k-th smallest among the keys EQUAL to it: 1 for the uniform keys, the number of tied edges to keep for the weighted ones.
-template <bool BLOCK, bool WEIGHTED>
-__device__ unsigned select_threshold_lds(int beg, int d, int &k, unsigned s, const float *__restrict__ w, int *hist /* [256] */, int tid, int lane)
+template <bool BLOCK, class KeyAt>
+__device__ unsigned radix_select(unsigned n, KeyAt key_at, int &k, int *hist /* [256] */, int tid, int lane)
 {
     constexpr unsigned GROUP = BLOCK ? kSelBlock : 64;
     unsigned prefix = 0;
@@ -168,8 +170,8 @@ __device__ unsigned select_threshold_lds(int beg, int d, int &k, unsigned s, con
             for (int b = 0; b < 4; ++b) hist[tid * 4 + b] = 0;
         }
         if (BLOCK) __syncthreads(); else wave_lds_sync();
-        for (unsigned t = (unsigned)tid; t < (unsigned)d; t += GROUP) {
-            const unsigned key = edge_key<WEIGHTED>((unsigned)beg + t, s, w);
+        for (unsigned t = (unsigned)tid; t < n; t += GROUP) {
+            const unsigned key = key_at(t);
             if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
         }
         if (BLOCK) __syncthreads(); else wave_lds_sync();
@@ -178,6 +180,13 @@ __device__ unsigned select_threshold_lds(int beg, int d, int &k, unsigned s, con
         if (BLOCK) __syncthreads(); else wave_lds_sync();
     }
     return prefix;
+}
+
+// the k-th smallest key of positions [beg, beg + d), every key evaluated in each of the four passes
+template <bool BLOCK, bool WEIGHTED>
+__device__ unsigned select_threshold_lds(int beg, int d, int &k, unsigned s, const float *__restrict__ w, int *hist /* [256] */, int tid, int lane)
+{
+    return radix_select<BLOCK>((unsigned)d, [=](unsigned t) { return edge_key<WEIGHTED>((unsigned)beg + t, s, w); }, k, hist, tid, lane);
 }
 
 // Hub rows (the whole workgroup): a row much longer than k is walked ONCE for the select.  The keys below 2^(32 - c), c chosen so that
@@ -203,29 +212,67 @@ __device__ unsigned select_threshold_hub(int beg, int d, int k, unsigned s, int 
     const int n = *cand_n;
     __syncthreads();
     if (n < k || n > kCand) return select_threshold_lds<true, false>(beg, d, k, s, nullptr, hist, tid, lane);   // (the same for every thread)
-    unsigned prefix = 0;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        if (tid < 64) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) hist[tid * 4 + b] = 0;
-        }
-        __syncthreads();
-        for (int j = tid; j < n; j += kSelBlock) {
-            const unsigned key = (unsigned)buf[j];
-            if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        const int digit = pick_digit(hist, lane, k);
-        prefix = (prefix << 8) | (unsigned)digit;
-        __syncthreads();
-    }
-    return prefix;
+    return radix_select<true>((unsigned)n, [=](unsigned j) { return (unsigned)buf[j]; }, k, hist, tid, lane);
 }
 
-// WEIGHTED: keys are edge_key<true> (no bijection), a row's count is min(d+, fanout) and may be 0 .. d; the kept edges are the ones with
-// key < T and the first `quota` edges with key == T in position order, quota being what the select leaves of k inside T's bin.  An
-// ineligible edge's key is above every T.  Output position = (keys < T before it) + min(keys == T before it, quota): still ballot ranks.
+// The ordered emission of row [b, b + dd) under its threshold T, to out[o ..], in rounds of one edge per thread.  BLOCK = false: one
+// wavefront (tid = lane); BLOCK = true: the whole workgroup, whose wavefronts exchange their counts of a round through wcount[kWaves].  dd, T
+// and quota are the same for every thread that enters, so the loop and its barriers are uniform.
+// Uniform keys: an edge is kept when key <= T, at o + (kept edges before it).  WEIGHTED: when key < T, or key == T and fewer than `quota`
+// edges equal to T lie before it; at o + (keys < T before it) + min(keys == T before it, quota).  "Before it" is the rounds so far (run,
+// ties), the wavefronts below this one in the round (their counts packed as lt | eq << 16: both <= 64 a wavefront, <= 1024 a round) and
+// the lanes below this one (ballot ranks).
+template <bool BLOCK, bool WEIGHTED>
+__device__ __forceinline__ void emit_row(const SampleOut &out, const int *__restrict__ idx, int b, int dd, int o, unsigned T, int quota, unsigned s,
+                                         const float *__restrict__ w, int *wcount, int tid, int lane, int wave)
+{
+    constexpr unsigned GROUP = BLOCK ? kSelBlock : 64;
+    constexpr int kWaves = kSelBlock / 64;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int run = 0, ties = 0;
+    for (unsigned base = 0; base < (unsigned)dd; base += GROUP) {
+        const unsigned t = base + (unsigned)tid;
+        unsigned key = 0;
+        bool keep = false;
+        unsigned long long lt, eq = 0;
+        if (WEIGHTED) {
+            // (no weight is read past the row; T is an eligible edge's key, below kSampleIneligible -- unless the weights changed under
+            // the sampler, hence t < dd in eq)
+            key = t < (unsigned)dd ? edge_key<true>((unsigned)b + t, s, w) : kSampleIneligible;
+            lt = __ballot(key < T);
+            eq = __ballot(t < (unsigned)dd && key == T);
+        } else {
+            keep = t < (unsigned)dd && sample_key((unsigned)b + t, s) <= T;
+            lt = __ballot(keep);
+        }
+        int before = 0, total = WEIGHTED ? __popcll(lt) | (__popcll(eq) << 16) : __popcll(lt);
+        if (BLOCK) {
+            if (lane == 0) wcount[wave] = total;
+            __syncthreads();
+            total = 0;
+#pragma unroll
+            for (int v = 0; v < kWaves; ++v) {
+                const int c = wcount[v];
+                if (v < wave) before += c;
+                total += c;
+            }
+        }
+        if (WEIGHTED) {
+            const int tied = ties + (before >> 16) + __popcll(eq & below);
+            if (key < T || (((eq >> lane) & 1ull) && tied < quota))
+                emit(out, idx, (long long)o + run + (before & 0xffff) + __popcll(lt & below) + (tied < quota ? tied : quota), b + (int)t);
+            run += total & 0xffff;
+            ties += total >> 16;
+        } else {
+            if (keep) emit(out, idx, (long long)o + run + before + __popcll(lt & below), b + (int)t);
+            run += total;
+        }
+        if (BLOCK) __syncthreads();
+    }
+}
+
+// WEIGHTED: keys are edge_key<true> (no bijection), a row's count is min(d+, fanout) and may be 0 .. d, and `quota` is what the select leaves
+// of k inside T's bin.  An ineligible edge's key is above every T.
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restrict__ ptr, const int *__restrict__ idx, int num_v, int num_e,
                                                              const int *__restrict__ seeds, int num_seeds, unsigned s,
@@ -307,26 +354,7 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
         }
         int quota = k;
         const unsigned T = select_threshold_lds<false, WEIGHTED>(b, dd, quota, s, w, hist, lane, lane);
-        int run = 0, ties = 0;   // kept edges / (WEIGHTED) edges below T, and edges equal to T, of the rounds before this one
-        for (int base = 0; base < dd; base += 64) {   // (k > 64: the emission takes several rounds all the same)
-            const int t = base + lane;
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (WEIGHTED) {
-                const unsigned key = t < dd ? edge_key<true>((unsigned)(b + t), s, w) : kSampleIneligible;
-                // (T is an eligible edge's key, below kSampleIneligible -- unless the weights changed under the sampler: no lane past the row)
-                const unsigned long long lt = __ballot(key < T), eq = __ballot(t < dd && key == T);
-                const int tied = ties + __popcll(eq & below);
-                if (key < T || (((eq >> lane) & 1ull) && tied < quota))
-                    emit(out, idx, (long long)o + run + __popcll(lt & below) + (tied < quota ? tied : quota), b + t);
-                run += __popcll(lt);
-                ties += __popcll(eq);
-            } else {
-                const bool keep = t < dd && sample_key((unsigned)(b + t), s) <= T;
-                const unsigned long long bal = __ballot(keep);
-                if (keep) emit(out, idx, (long long)o + run + __popcll(bal & below), b + t);
-                run += __popcll(bal);
-            }
-        }
+        emit_row<false, WEIGHTED>(out, idx, b, dd, o, T, quota, s, w, nullptr, lane, lane, 0);
     }
 
     // hub rows (more than kHubEdges edges): the whole workgroup per row, one after the other
@@ -339,52 +367,10 @@ __global__ __launch_bounds__(kSelBlock) void k_sample_select(const int *__restri
             for (unsigned t = (unsigned)tid; t < (unsigned)dd; t += kSelBlock) emit(out, idx, (long long)o + t, b + (int)t);
             continue;
         }
-        if (WEIGHTED) {
-            int quota = k;
-            const unsigned T = select_threshold_lds<true, true>(b, dd, quota, s, w, hub_hist, tid, lane);
-            int run = 0, ties = 0;
-            for (unsigned base = 0; base < (unsigned)dd; base += kSelBlock) {
-                const unsigned t = base + (unsigned)tid;
-                const unsigned long long below = (1ull << lane) - 1ull;
-                const unsigned key = t < (unsigned)dd ? edge_key<true>((unsigned)b + t, s, w) : kSampleIneligible;
-                const unsigned long long lt = __ballot(key < T), eq = __ballot(t < (unsigned)dd && key == T);
-                if (lane == 0) wcount[wave] = __popcll(lt) | (__popcll(eq) << 16);   // (both <= 64 a wavefront, <= 1024 a round)
-                __syncthreads();
-                int before = 0, total = 0;
-#pragma unroll
-                for (int v = 0; v < kWaves; ++v) {
-                    const int c = wcount[v];
-                    if (v < wave) before += c;
-                    total += c;
-                }
-                const int tied = ties + (before >> 16) + __popcll(eq & below);
-                if (key < T || (((eq >> lane) & 1ull) && tied < quota))
-                    emit(out, idx, (long long)o + run + (before & 0xffff) + __popcll(lt & below) + (tied < quota ? tied : quota), b + (int)t);
-                run += total & 0xffff;
-                ties += total >> 16;
-                __syncthreads();
-            }
-            continue;
-        }
-        const unsigned T = select_threshold_hub(b, dd, k, s, hub_hist, &hist_all[0][0], &cand_n, tid, lane);
-        int run = 0;
-        for (unsigned base = 0; base < (unsigned)dd; base += kSelBlock) {
-            const unsigned t = base + (unsigned)tid;
-            const bool keep = t < (unsigned)dd && sample_key((unsigned)b + t, s) <= T;
-            const unsigned long long bal = __ballot(keep);
-            if (lane == 0) wcount[wave] = __popcll(bal);
-            __syncthreads();
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const int c = wcount[w];
-                if (w < wave) before += c;
-                total += c;
-            }
-            if (keep) emit(out, idx, (long long)o + run + before + __popcll(bal & ((1ull << lane) - 1ull)), b + (int)t);
-            run += total;
-            __syncthreads();
-        }
+        int quota = k;
+        const unsigned T = WEIGHTED ? select_threshold_lds<true, true>(b, dd, quota, s, w, hub_hist, tid, lane)
+                                    : select_threshold_hub(b, dd, k, s, hub_hist, &hist_all[0][0], &cand_n, tid, lane);
+        emit_row<true, WEIGHTED>(out, idx, b, dd, o, T, quota, s, w, wcount, tid, lane, wave);
     }
 }
 
@@ -455,58 +441,6 @@ __global__ __launch_bounds__(256) void k_sample_restore(const int *__restrict__ 
     if ((unsigned)v < (unsigned)num_v) map[v] = kUnseen;
 }
 
-// ---- relabelling by a sort of (id, position) pairs (GNNAGG_SAMPLE_RELABEL=sort: the form the atomic map was measured against).  Items
-// j < num_seeds are the seeds, item num_seeds + q is block position q; after the STABLE sort by id the head of every group of equal ids is
-// its lowest item: the first seed of that id, else the first appearance.  No map, nothing to restore.
-__global__ __launch_bounds__(256) void k_sample_pairs(const int *__restrict__ seeds, int num_seeds, const int *__restrict__ blk_ptr, long long cap,
-                                                      const int *__restrict__ blk_idx, int num_v, long long m, unsigned *__restrict__ keys,
-                                                      int *__restrict__ vals, int *__restrict__ src_nodes)
-{
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= m) return;
-    int v = num_v;   // (past the kept edges, or no row of the graph: sorts behind every id)
-    if (j < num_seeds) {
-        v = seeds[j];
-        src_nodes[j] = v;
-    } else if (j - num_seeds < kept_edges(blk_ptr, num_seeds, cap)) v = blk_idx[j - num_seeds];
-    keys[j] = (unsigned)v < (unsigned)num_v ? (unsigned)v : (unsigned)num_v;
-    vals[j] = (int)j;
-}
-
-__global__ __launch_bounds__(256) void k_sample_heads(const unsigned *__restrict__ keys, long long m, int *__restrict__ head)
-{
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j < m) head[j] = (j > 0 && keys[j] != keys[j - 1]) ? (int)j : 0;
-}
-
-// first[item] = the lowest item of its id (-1: no id); flag[q] = 1 where block position q is a first appearance of a row that is no seed
-__global__ __launch_bounds__(256) void k_sample_firsts(const unsigned *__restrict__ keys, const int *__restrict__ vals, const int *__restrict__ headidx,
-                                                       long long m, int num_seeds, int num_v, long long n, int *__restrict__ first, int *__restrict__ flag)
-{
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j == 0) flag[n] = 0;
-    if (j >= m) return;
-    const int item = vals[j];
-    const int lowest = keys[j] == (unsigned)num_v ? -1 : vals[headidx[j]];
-    first[item] = lowest;
-    if (item >= num_seeds) flag[item - num_seeds] = lowest == item;
-}
-
-__global__ __launch_bounds__(256) void k_sample_relabel_sorted(const int *__restrict__ blk_ptr, int num_seeds, long long cap, int *__restrict__ blk_idx,
-                                                               const int *__restrict__ first, const int *__restrict__ first_rank,
-                                                               int *__restrict__ src_nodes)
-{
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (q >= kept_edges(blk_ptr, num_seeds, cap)) return;
-    const int v = blk_idx[q], lowest = first[num_seeds + q];
-    int local = -1;
-    if (lowest >= 0) {
-        local = lowest < num_seeds ? lowest : num_seeds + first_rank[lowest - num_seeds];
-        if (lowest == num_seeds + q) src_nodes[local] = v;
-    }
-    blk_idx[q] = local;
-}
-
 __global__ void k_sample_finish(const int *__restrict__ blk_ptr, int num_seeds, const int *__restrict__ first_rank, long long n, int num_v,
                                 int *__restrict__ counts)
 {
@@ -524,11 +458,9 @@ struct Sampler {
     const int *d_ptr = nullptr, *d_idx = nullptr;
     int V = 0, E = 0;
     hipStream_t stream = nullptr;
-    bool relabel_by_sort = false;   // GNNAGG_SAMPLE_RELABEL=sort at creation (a measurement aid: DESIGN.md "Neighbour sampling")
     DevBuf<int> map, cnt, flag, rank, scan_tmp;
     const float *d_w = nullptr;     // gnnagg_sampler_set_weights: borrowed [E], nullptr = uniform sampling
     DevBuf<int> elig;               // [V] eligible edges (w > 0) of every row, of d_w
-    DevBuf<int> keys_a, keys_b, vals_a, vals_b, first, sort_counts;   // the sort form only
 };
 
 std::mutex g_sampler_mu;
@@ -558,51 +490,22 @@ int sampler_sample(Sampler *c, const int *d_seeds, int num_seeds, int fanout, un
     int rc;
     if ((rc = c->cnt.reserve((size_t)num_seeds + 1))) return rc;
     if (relabel && ((rc = c->flag.reserve((size_t)n + 1)) || (rc = c->rank.reserve((size_t)n + 1)))) return rc;
-    const long long m = (long long)num_seeds + n;   // items of the sort form
-    if (relabel && c->relabel_by_sort && m > 0)
-        for (DevBuf<int> *b : {&c->keys_a, &c->keys_b, &c->vals_a, &c->vals_b, &c->first})
-            if ((rc = b->reserve((size_t)m))) return rc;
+    const long long m = (long long)num_seeds + n;   // (src_nodes has at most that many entries)
     hipStream_t st = c->stream;
     const unsigned s = sample_seed_mix(seed);
 
-    if (c->d_w)
-        hipLaunchKernelGGL(k_sample_counts<true>, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds,
-                           fanout, c->cnt.p, c->elig.p);
-    else
-        hipLaunchKernelGGL(k_sample_counts<false>, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds,
-                           fanout, c->cnt.p, nullptr);
+    // (the <true> instantiations under a weight vector; <false> reads neither elig nor w)
+    const auto counts = c->d_w ? k_sample_counts<true> : k_sample_counts<false>;
+    const auto select = c->d_w ? k_sample_select<true> : k_sample_select<false>;
+    hipLaunchKernelGGL(counts, dim3(blocks_of((long long)num_seeds + 1)), dim3(256), 0, st, c->d_ptr, c->V, c->E, d_seeds, num_seeds, fanout, c->cnt.p,
+                       c->d_w ? c->elig.p : nullptr);
     if ((rc = prims::scan<prims::OpSum, true>(c->cnt.p, d_blk_ptr, (long)num_seeds + 1, c->scan_tmp, st))) return rc;
     if (num_seeds > 0) {
         const SampleOut out{d_blk_idx, d_blk_eid, cap_e};
         const dim3 grid((unsigned)((num_seeds + kSelBlock - 1) / kSelBlock));
-        if (c->d_w)
-            hipLaunchKernelGGL(k_sample_select<true>, grid, dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s, d_blk_ptr, out,
-                               c->d_w);
-        else
-            hipLaunchKernelGGL(k_sample_select<false>, grid, dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s, d_blk_ptr, out,
-                               nullptr);
+        hipLaunchKernelGGL(select, grid, dim3(kSelBlock), 0, st, c->d_ptr, c->d_idx, c->V, c->E, d_seeds, num_seeds, s, d_blk_ptr, out, c->d_w);
     }
-    if (relabel && c->relabel_by_sort) {
-        if (m > 0) {
-            unsigned *ka = reinterpret_cast<unsigned *>(c->keys_a.p), *kb = reinterpret_cast<unsigned *>(c->keys_b.p);
-            int bits = 1;
-            while (bits < 31 && (1ll << bits) <= c->V) ++bits;   // ids 0 .. V (V: no id) fit
-            hipLaunchKernelGGL(k_sample_pairs, dim3(blocks_of(m)), dim3(256), 0, st, d_seeds, num_seeds, d_blk_ptr, cap_e, d_blk_idx, c->V, m, ka,
-                               c->vals_a.p, d_src_nodes);
-            if ((rc = prims::sort_pairs(ka, kb, c->vals_a.p, c->vals_b.p, (long)m, bits, c->sort_counts, c->scan_tmp, st))) return rc;
-            // (the sort clobbered its inputs: keys_a now holds the head marks, vals_a their running maximum = every item's group head)
-            hipLaunchKernelGGL(k_sample_heads, dim3(blocks_of(m)), dim3(256), 0, st, kb, m, c->keys_a.p);
-            if ((rc = prims::scan<prims::OpMax, false>(c->keys_a.p, c->vals_a.p, (long)m, c->scan_tmp, st))) return rc;
-            hipLaunchKernelGGL(k_sample_firsts, dim3(blocks_of(m)), dim3(256), 0, st, kb, c->vals_b.p, c->vals_a.p, m, num_seeds, c->V, n, c->first.p,
-                               c->flag.p);
-        } else {
-            hipLaunchKernelGGL(k_sample_fill, dim3(1), dim3(256), 0, st, c->flag.p, 1ll, 0);
-        }
-        if ((rc = prims::scan<prims::OpSum, true>(c->flag.p, c->rank.p, (long)n + 1, c->scan_tmp, st))) return rc;
-        if (n > 0)
-            hipLaunchKernelGGL(k_sample_relabel_sorted, dim3(blocks_of(n)), dim3(256), 0, st, d_blk_ptr, num_seeds, cap_e, d_blk_idx, c->first.p, c->rank.p,
-                               d_src_nodes);
-    } else if (relabel) {
+    if (relabel) {
         if (num_seeds > 0)
             hipLaunchKernelGGL(k_sample_mark_seeds, dim3(blocks_of(num_seeds)), dim3(256), 0, st, d_seeds, num_seeds, c->V, c->map.p, d_src_nodes);
         if (n > 0)
@@ -660,7 +563,6 @@ int gnnagg_sampler_create(const int *d_ptr, const int *d_idx, int num_v, int num
         return fail(GNNAGG_ERR_HIP, "no HIP device available: libgnnagg has no CPU fallback (gnnagg_sample_block_host is the host sampler)");
     Sampler *c = new Sampler;
     c->d_ptr = d_ptr; c->d_idx = d_idx; c->V = num_v; c->E = num_e;
-    if (const char *e = getenv("GNNAGG_SAMPLE_RELABEL")) c->relabel_by_sort = std::string(e) == "sort";
     int rc = c->map.alloc((size_t)num_v);
     if (!rc && num_v > 0) {
         hipLaunchKernelGGL(k_sample_fill, dim3(blocks_of(num_v)), dim3(256), 0, nullptr, c->map.p, (long long)num_v, kUnseen);

@@ -895,8 +895,6 @@ int gnnagg_dist_step_gat(gnnagg_dist_step_t step, float *d_x_ext, float *d_att_e
  *   - num_seeds = 0 is a valid call that writes blk_ptr[0] = 0 and the counts
  *   - a seed that is no row of the graph is a row without edges (the host twin refuses it: GNNAGG_ERR_ARG)
  *   - no atomics touch the outputs: the result is a function of the arguments, bit for bit
- *   - GNNAGG_SAMPLE_RELABEL=sort in the environment when a sampler is created makes it relabel by a stable sort of (id, position) pairs
- *     in place of the map's integer min-atomics: the same outputs, bit for bit; the form the shipped one was measured against
  * gnnagg_sample_block_host is the same function of the same arguments on host arrays (OpenMP over the rows, a serial relabel): the
  * library's CPU path for data-loader workers, usable without a GPU.
  * The reference's sampleVertex* signatures are out of scope: they expand active flags over the globals n, m and no driver calls them;

@@ -4,8 +4,6 @@ arxiv- and products-shaped graphs, batches of 1 024 and 8 192 seeds and all rows
 
     global      (a) the two blocks WITHOUT relabelling (global ids), over the two seed lists arm (b) samples from
     relabel     (b) sample_layers(seeds, (f, f), return_eid=True): relabelled blocks with edge positions
-    relabel_sort    (b) on a sampler created under GNNAGG_SAMPLE_RELABEL=sort: the relabelling as a stable sort of (id, position) pairs
-                (prims::sort_pairs) in place of the atomicMin map; checked to give the same bits
     torch       (c) the same two blocks composed from torch ops in this process: expand the seed rows, random keys, sort by (row, key), keep
                 rank < fanout, torch.unique with inverse for the relabelling.  Its output is checked to be a VALID block (counts, every kept
                 edge inside its row and kept once, ids consistent); it is sorted-id relabelling, not seeds-first, and rows are not put back
@@ -95,9 +93,6 @@ def main():
         V, E = ptrs.numel() - 1, idxs.numel()
         ptr_np, idx_np = ptrs.cpu().numpy(), idxs.cpu().numpy()
         sampler = gnc.NeighborSampler(ptrs, idxs)
-        os.environ["GNNAGG_SAMPLE_RELABEL"] = "sort"       # (read when a sampler is created)
-        sorter = gnc.NeighborSampler(ptrs, idxs)
-        del os.environ["GNNAGG_SAMPLE_RELABEL"]
         for batch in args.batches.split(","):
             n = V if batch == "all" else min(int(batch), V)
             seeds_np = (np.arange(V) if n == V else np.random.default_rng(11).choice(V, n, replace=False)).astype(np.int32)
@@ -114,12 +109,6 @@ def main():
                     for f in ("ptr", "idx", "src_nodes", "eid"):
                         assert np.array_equal(getattr(b, f).cpu().numpy(), getattr(h, f)), (name, batch, fanout, f)
                 with torch.cuda.stream(stream):
-                    sorted_blocks = sorter.sample_layers(seeds, (fanout, fanout), seed=1, return_eid=True)
-                stream.synchronize()
-                for b, h in zip(blocks, sorted_blocks):
-                    for f in ("ptr", "idx", "src_nodes", "eid"):
-                        assert torch.equal(getattr(b, f), getattr(h, f)), (name, batch, fanout, f, "sort")
-                with torch.cuda.stream(stream):
                     t_low, t_top = torch_layers(ptrs, idxs, seeds, fanout)
                 stream.synchronize()
                 check_torch_block(ptr_np, idx_np, seeds_np, fanout, t_top)
@@ -135,7 +124,6 @@ def main():
 
                 arms = {"global": arm_global,
                         "relabel": lambda: sampler.sample_layers(seeds, (fanout, fanout), seed=1, return_eid=True),
-                        "relabel_sort": lambda: sorter.sample_layers(seeds, (fanout, fanout), seed=1, return_eid=True),
                         "torch": lambda: torch_layers(ptrs, idxs, seeds, fanout)}
                 for fn in arms.values():
                     time_round(fn, 2)
@@ -169,7 +157,7 @@ def main():
                 rec = dict(input="%s-shaped two-layer sampling" % name, library=args.label, V=V, E=E, max_degree=int(np.diff(ptr_np).max()), batch=n, fanout=fanout, rounds=args.rounds,
                            calls=args.calls, host_calls=args.host_calls, host_threads=int(os.environ["OMP_NUM_THREADS"]),
                            edges=[b.num_edges for b in blocks], src_rows=[b.num_src for b in blocks],
-                           torch_over_relabel=med["torch"] / med["relabel"], sort_over_atomic=med["relabel_sort"] / med["relabel"], host_over_relabel=med["host"] / med["relabel"],
+                           torch_over_relabel=med["torch"] / med["relabel"], host_over_relabel=med["host"] / med["relabel"],
                            relabel_beats_torch_by_more_than_the_spread=bool(max(times["relabel"]) < min(times["torch"])),
                            handle_create_first_run_us=statistics.median(first), handle_steady_run_us=statistics.median(steady))
                 for arm, t in times.items():
@@ -177,7 +165,6 @@ def main():
                     rec[arm + "_min_max_us"] = [min(t), max(t)]
                 print(json.dumps(rec), flush=True)
         sampler.close()
-        sorter.close()
 
 
 if __name__ == "__main__":

@@ -122,7 +122,7 @@ def properties(outs, seeds, fanout):
 def test_block_equals_the_restatement_and_has_its_properties(fanout, name):
     seeds = LISTS[name]
     cap = len(seeds) * fanout if fanout > 0 else needed(seeds, fanout)
-    outs = raw(veteran(), seeds, fanout, 5, cap)
+    outs = raw(veteran(), seeds, fanout, 5, cap, shift=1)
     judge(outs, name, fanout, 5, cap=cap)
     properties(outs, seeds, fanout)
     judge(raw(veteran(), seeds, fanout, 5, cap, relabel=False, eid=False), name, fanout, 5, relabel=False, eid=False, cap=cap)
@@ -250,43 +250,6 @@ def test_every_refusal_leaves_the_sampler_as_it_was():
     h = ctypes.c_int64(gone._h.value)
     gone.close()
     assert L.gnnagg_sampler_sample(h, P(d_seeds), n, 5, 5, P(bp), P(bi), P(be), 5 * n, P(sn), P(cn)) == _lib.ERR_ARG
-
-
-@pytest.fixture(scope="module")
-def sorter():
-    """a sampler that relabels by the sort of (id, position) pairs (GNNAGG_SAMPLE_RELABEL=sort, read at creation): the same specification"""
-    import os
-    old = os.environ.get("GNNAGG_SAMPLE_RELABEL")
-    os.environ["GNNAGG_SAMPLE_RELABEL"] = "sort"
-    try:
-        s = gnc.NeighborSampler(*graph())
-    finally:
-        if old is None:
-            del os.environ["GNNAGG_SAMPLE_RELABEL"]
-        else:
-            os.environ["GNNAGG_SAMPLE_RELABEL"] = old
-    yield s
-    s.close()
-
-
-@pytest.mark.parametrize("name", list(LISTS))
-@pytest.mark.parametrize("fanout", sr.FANOUTS)
-def test_sort_relabelling_equals_the_restatement(sorter, fanout, name):
-    seeds = LISTS[name]
-    cap = len(seeds) * fanout if fanout > 0 else needed(seeds, fanout)
-    outs = raw(sorter, seeds, fanout, 5, cap, shift=1)
-    judge(outs, name, fanout, 5, cap=cap)
-    properties(outs, seeds, fanout)
-
-
-def test_sort_relabelling_with_too_little_room(sorter):
-    seeds = LISTS["crafted"]
-    n, total = len(seeds), needed(seeds, 200)
-    for cap in (total - 1, total // 2, 0):
-        bp, bi, be, sn, cn = raw(sorter, seeds, 200, 5, cap)
-        assert np.array_equal(bp[:n + 1], ref("crafted", 200, 5, True)[0]) and cn[0] == total and (cn[2:] == CANARY).all()
-        assert (bp[n + 1:] == CANARY).all() and (bi[cap:] == CANARY).all() and (be[cap:] == CANARY).all() and (sn[n + cap:] == CANARY).all()
-    judge(raw(sorter, seeds, 200, 5, total), "crafted", 200, 5)
 
 
 @pytest.mark.parametrize("fanout", [1100, 2000, 4999])
