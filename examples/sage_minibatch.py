@@ -2,13 +2,17 @@
 """Mini-batch GraphSAGE forward (2 layers, mean aggregation) over sampled blocks: sample on the device (gnc.NeighborSampler), gather the
 input rows, and per layer h_dst' = relu(h_dst . W_self + mean_{kept neighbours}(h_src) . W_neigh) with the library's aggregation and GEMM.
 
-    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted]
+    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted] [--block-run]
 
 --weighted draws the neighbours in proportion to a per-edge weight (NeighborSampler(prob=); a third of the edges have weight 0 and are never
 drawn) and aggregates the weighted sum with the kept edges' own weights, full_val[blk.eid].
 
 Prints one JSON line with the per-stage times (medians over the batches, microseconds, each stage closed by a device synchronisation).  A
-block is a new graph, so every batch creates its aggregators: the "aggregate" stage holds handle creation, plan and run."""
+block is a new graph, so every batch creates its aggregators: the "aggregate" stage holds handle creation, plan and run.
+
+--block-run aggregates every block with one launch instead (Block.aggregate): no handle, no plan, and no gather stage -- the input layer
+reads x in place through blocks[0].src_nodes and returns x_dst beside the aggregate; --weighted then passes the full per-edge values and
+lets the call read them through blk.eid (val_full=True).  The JSON line gains "block_run": true and its "gather_us" is 0."""
 import argparse
 import json
 import os
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--batches", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weighted", action="store_true", help="sample by a per-edge weight and aggregate with it")
+    ap.add_argument("--block-run", action="store_true", help="aggregate each block with one Block.aggregate call: no handle, no gather")
     args = ap.parse_args()
     fanouts = tuple(int(f) for f in args.fanouts.split(","))
     assert len(fanouts) == 2, "this example has two layers"
@@ -65,21 +70,32 @@ def main():
         seeds = perm[(b * args.batch) % num_v:][:args.batch].contiguous()
         # the sample of a row depends on (seed, row) only: a new seed per batch draws a new sample
         blocks, t_sample = timed(lambda: sampler.sample_layers(seeds, fanouts, seed=args.seed + 2 * b, return_eid=args.weighted))
-        h, t_gather = timed(lambda: x[blocks[0].src_nodes.long()])
+        reduce = "sum" if args.weighted else "mean"
+        if args.block_run:
+            h, t_gather = x, 0.0                      # no gather stage: layer 0 reads x in place through src_nodes
+        else:
+            h, t_gather = timed(lambda: x[blocks[0].src_nodes.long()])
         t_agg = t_dense = 0.0
         for k, blk in enumerate(blocks):
 
             def aggregate():
                 y = torch.empty((blk.num_dst, h.shape[1]), device=dev)
                 agg = blk.gcn(full_val[blk.eid.long()].contiguous() if args.weighted else None)
-                agg.run(h, y, 512, 0, reduce="sum" if args.weighted else "mean")
-                return y, agg
+                agg.run(h, y, 512, 0, reduce=reduce)
+                return y, h[:blk.num_dst], agg
 
-            (y, agg), dt = timed(aggregate)
+            def aggregate_block_run():
+                kw = {"val": full_val, "val_full": True} if args.weighted else {}
+                if k == 0:                            # the aggregate and x_dst = x[src_nodes[:num_dst]] from one launch
+                    return blk.aggregate(h, reduce=reduce, return_dst=True, **kw) + (None,)
+                return blk.aggregate(h, reduce=reduce, gathered=True, **kw), h[:blk.num_dst], None
+
+            (y, h_dst, agg), dt = timed(aggregate_block_run if args.block_run else aggregate)
             t_agg += dt
-            h, dt = timed(lambda: F.relu(gnc.matmul_NN(h[:blk.num_dst].contiguous(), w_self[k]) + gnc.matmul_NN(y, w_neigh[k])))
+            h, dt = timed(lambda: F.relu(gnc.matmul_NN(h_dst.contiguous(), w_self[k]) + gnc.matmul_NN(y, w_neigh[k])))
             t_dense += dt
-            agg.close()
+            if agg is not None:
+                agg.close()
         if b > 0:
             for stage, dt in (("sample", t_sample), ("gather", t_gather), ("aggregate", t_agg), ("dense", t_dense)):
                 stages[stage].append(dt)
@@ -87,6 +103,8 @@ def main():
     rec = {"model": "sage_minibatch", "dataset": args.dataset, "num_v": num_v, "num_e": idxs.numel(), "batch": args.batch, "fanouts": list(fanouts), "weighted": args.weighted,
            "batches": args.batches, "last_blocks": [[blk.num_dst, blk.num_src, blk.num_edges] for blk in blocks],
            "finite": bool(torch.isfinite(out).all().item())}
+    if args.block_run:
+        rec["block_run"] = True
     rec.update({k + "_us": statistics.median(v) for k, v in stages.items()})
     rec["total_us"] = sum(rec[k + "_us"] for k in stages)
     print(json.dumps(rec))

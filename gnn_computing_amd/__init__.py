@@ -11,7 +11,7 @@ from .aggregator import (  # noqa: F401
     reorder_csr, neighbor_grouping_schedule, locality_schedule, partition_rows, halo_plan, cluster_reorder, matmul_NN,
     gat_project, last_project_path, gatv2_run, dot_attn_run, gcn_run_multi, pna_delta,
 )
-from .sampling import Block, NeighborSampler, sample_block_host  # noqa: F401
+from .sampling import Block, NeighborSampler, block_gcn_run, sample_block_host  # noqa: F401
 from . import graph  # noqa: F401
 from . import probe  # noqa: F401
 # (gnn_computing_amd.extras -- torch.autograd wrappers over the backward entry points -- needs libgnnagg_extras.so: out of scope per

@@ -148,6 +148,8 @@ SIGNATURES = {
     "gnnagg_sampler_set_weights": (c_int, [c_int64, c_void_p]),
     "gnnagg_sample_block_host_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_ulonglong, c_void_p,
                                                   c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
+    "gnnagg_block_gcn_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p, c_int,
+                                     c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

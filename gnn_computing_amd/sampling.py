@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .aggregator import Aggregator_GAT, Aggregator_GCN, _dev_ptr
+from .aggregator import FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _dev_ptr, _dev_ptr_rows, _feat_dtype
 
 _U64 = (1 << 64) - 1
 
@@ -28,6 +28,88 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
 
     def gat(self):
         return Aggregator_GAT(self.ptr, self.idx)
+
+    def aggregate(self, x, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None, relu=False, return_dst=False):
+        """The GCN / SAGE aggregation of this block in ONE launch on torch's current stream (gnnagg_block_gcn_run): no handle, no plan, no
+        gathered copy of x.  Bit for bit what self.gcn(val).run(x_src, y, 512, 0, reduce) gives.
+          x            float32 or bfloat16 [rows, F]; a row-pitched column view is taken as it is.  gathered=False on a relabelled block: the
+                       matrix the block was sampled from, read through src_nodes.  gathered=True, or a block of global ids: idx indexes x
+                       directly (x[src_nodes], or the previous layer's output).
+          val          None (weight 1) or float32: one value per edge of the block, or -- val_full=True -- per edge of the full CSR, read
+                       through self.eid
+          out          None or a contiguous [num_dst, F] float32 / bfloat16 tensor; out_dtype: the type of the y allocated here (x's by default)
+          return_dst   True (or a contiguous [num_dst, F] tensor of x's dtype to fill): also x_dst = x[src_nodes[:num_dst]], copied by the
+                       same launch; needs gathered=False on a relabelled block
+        Returns y, or (y, x_dst)."""
+        return block_gcn_run(self, x, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out, out_dtype=out_dtype, relu=relu,
+                             return_dst=return_dst)
+
+
+def block_gcn_run(blk, x, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None, relu=False, return_dst=False):
+    """Block.aggregate as a function (the thin form over gnnagg_block_gcn_run); every dtype and shape refusal is raised before device work"""
+    if reduce not in REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (sorted(REDUCE), reduce))
+    mapped = blk.src_nodes is not None and not gathered
+    want_dst = return_dst is not False and return_dst is not None
+    if val_full and blk.eid is None:
+        raise ValueError("val_full=True reads val through blk.eid: sample the block with return_eid=True")
+    if val_full and val is None:
+        raise ValueError("val_full=True needs val")
+    if want_dst and not mapped:
+        raise ValueError("return_dst copies x[src_nodes[:num_dst]]: it needs a relabelled block and gathered=False")
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    shape = (blk.num_dst, feat)
+    if not mapped and int(x.shape[0]) < blk.num_src:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], blk.num_src, bool(gathered)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    x_dst = return_dst if isinstance(return_dst, torch.Tensor) else None
+    if x_dst is not None:
+        if x_dst.dtype != x.dtype:
+            raise TypeError("return_dst must have x's dtype %s, got %s" % (x.dtype, x_dst.dtype))
+        if tuple(x_dst.shape) != shape:
+            raise ValueError("return_dst must be [%d, %d], got %s" % (shape + (tuple(x_dst.shape),)))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full else None
+    p_val = _dev_ptr(val, torch.float32, "val")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    if x_dst is not None:
+        _dev_ptr(x_dst, x.dtype, "return_dst")
+    for name, t in (("blk.ptr", blk.ptr), ("val", val), ("out", out), ("return_dst", x_dst)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype or x.dtype, device=x.device)
+    ydt = FEATURE_DTYPES[out.dtype]
+    if x_dst is None and want_dst:
+        x_dst = torch.empty(shape, dtype=x.dtype, device=x.device)
+    flags = _lib.FLAG_RELU if relu else 0
+    check(lib().gnnagg_block_gcn_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch,
+                                     ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, ydt,
+                                     ctypes.c_void_p(x_dst.data_ptr()) if x_dst is not None and blk.num_dst else None, feat, REDUCE[reduce], flags,
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return (out, x_dst) if x_dst is not None else out
 
 
 def _check_fanout(fanout):

@@ -952,6 +952,45 @@ int gnnagg_sample_block_host_weighted(const int *h_ptr, const int *h_idx, const 
                                       int fanout, unsigned long long seed, int *h_blk_ptr, int *h_blk_idx, int *h_blk_eid,
                                       long long cap_e, int *h_src_nodes, int *h_counts);
 
+/* Block aggregation: the GCN / SAGE aggregation of one sampled block in one launch, straight from (d_blk_ptr, d_blk_idx) -- no handle, no
+ * plan, no gathered copy of the source rows (csrc/agg_block.hip).  A block is used once and its rows hold at most `fanout` edges: there is
+ * nothing a plan could balance, and creating one costs more than the run.  For destination row i < num_dst and column c < feat, over the
+ * edges p in [blk_ptr[i], blk_ptr[i+1]) in increasing p:
+ *   s(p) = d_src_nodes ? d_src_nodes[blk_idx[p]] : blk_idx[p]          the row of x
+ *   w(p) = !d_val ? 1.0f : d_eid ? d_val[d_eid[p]] : d_val[p]
+ *   sum    acc = 0.0f;  acc = fmaf(widen(x[s(p)][c]), w(p), acc)       one fp32 chain per (row, column), CSR order
+ *   mean   the sum, then acc / (float)deg where deg > 0                deg = the row's edges IN THE BLOCK
+ *   max    acc = -inf;  t = widen(x) * w;  acc = t > acc ? t : acc;    0 for a row without edges
+ *   then ReLU if flagged (a NaN stays a NaN); y[i][c] = acc            a bf16 y is ONE round-to-nearest-even at the store
+ *   x_dst (optional): x_dst[i][:] = x[d_src_nodes[i]][:]               the row copied as it is, no arithmetic
+ * These are the operations and the order of the handle's rows mode: for fp32 the result is, bit for bit, what a GCN aggregator created
+ * over (d_blk_ptr, d_blk_idx, val) gives in GNNAGG_MODE_ROWS on x[src_nodes].
+ *   operands     d_x holds rows of `feat` elements of x_dtype, x_pitch ELEMENTS apart (x_pitch >= feat, as the pitches of
+ *                gnnagg_dot_attn_run): the matrix the block was sampled from, read through d_src_nodes, or -- d_src_nodes NULL -- the
+ *                rows blk_idx names directly (x[src_nodes], the previous layer's output, or a block of global ids).  d_val NULL: weight 1;
+ *                d_val without d_eid: one value per edge of the block; with d_eid: d_val holds one value per edge of the full CSR and
+ *                d_eid [edges of the block] the position of every block edge in it (the sampler's d_blk_eid).  d_y and d_x_dst are dense
+ *                [num_dst, feat] of y_dtype / x_dtype and alias no input.
+ *   types        GNNAGG_DTYPE_F32 and GNNAGG_DTYPE_BF16 for x and y, all four pairs; accumulation is fp32.  A bf16 x gives the fp32 call
+ *                on x widened (exact).
+ *   determinism  the bits depend on the arguments only, never on alignment, pitch or lane geometry (lanes are as wide as feat, x_pitch
+ *                and the alignment of x, y and x_dst allow).  No atomics.
+ *   non-finite   +-Inf / NaN reach exactly the rows that hold them as neighbours (no padding lane multiplies a real source row by zero);
+ *                GNNAGG_REDUCE_MAX over a NaN operand is unspecified.
+ *   flags        GNNAGG_FLAG_RELU only.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream; capturable into a HIP graph
+ *                (num_dst is the caller's, the edge count is read from d_blk_ptr on the device).  num_dst = 0 is a valid call that
+ *                launches nothing.  Ids are not validated, as everywhere else.
+ *   rows         a row of any length is walked by its one lane group: the chain cannot be split without changing its bits, and a
+ *                sampled row is short.  For blocks taken with fanout = -1 that hold hub rows a handle's rows mode remains the fast path.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: a null d_blk_ptr, d_x or d_y with num_dst > 0;
+ *                num_dst < 0; feat < 1; x_pitch < feat; an unknown x_dtype, y_dtype or reduce; any flag but GNNAGG_FLAG_RELU; d_eid
+ *                without d_val; d_x_dst without d_src_nodes.
+ * (tests/block_run_ref.py, tests/test_block_run_host.py, tests/test_gpu_block_run.py; DESIGN.md "Block aggregation") */
+int gnnagg_block_gcn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const float *d_val,
+                         const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, void *d_y, int y_dtype, void *d_x_dst,
+                         int feat, int reduce, int flags, void *hip_stream);
+
 /* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
