@@ -2,7 +2,7 @@
 """Mini-batch GraphSAGE forward (2 layers, mean aggregation) over sampled blocks: sample on the device (gnc.NeighborSampler), gather the
 input rows, and per layer h_dst' = relu(h_dst . W_self + mean_{kept neighbours}(h_src) . W_neigh) with the library's aggregation and GEMM.
 
-    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted] [--block-run]
+    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted] [--block-run] [--fused-layer]
 
 --weighted draws the neighbours in proportion to a per-edge weight (NeighborSampler(prob=); a third of the edges have weight 0 and are never
 drawn) and aggregates the weighted sum with the kept edges' own weights, full_val[blk.eid].
@@ -12,7 +12,10 @@ block is a new graph, so every batch creates its aggregators: the "aggregate" st
 
 --block-run aggregates every block with one launch instead (Block.aggregate): no handle, no plan, and no gather stage -- the input layer
 reads x in place through blocks[0].src_nodes and returns x_dst beside the aggregate; --weighted then passes the full per-edge values and
-lets the call read them through blk.eid (val_full=True).  The JSON line gains "block_run": true and its "gather_us" is 0."""
+lets the call read them through blk.eid (val_full=True).  The JSON line gains "block_run": true and its "gather_us" is 0.
+
+--fused-layer (implies --block-run) runs every layer as ONE launch, Block.sage: aggregation, both products, and the ReLU, with no aggregate
+and no x_dst in memory.  The JSON line gains "fused_layer": true and a "layer_us" stage; its "aggregate_us" and "dense_us" are 0."""
 import argparse
 import json
 import os
@@ -38,7 +41,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weighted", action="store_true", help="sample by a per-edge weight and aggregate with it")
     ap.add_argument("--block-run", action="store_true", help="aggregate each block with one Block.aggregate call: no handle, no gather")
+    ap.add_argument("--fused-layer", action="store_true", help="run each layer as one Block.sage call (implies --block-run)")
     args = ap.parse_args()
+    args.block_run = args.block_run or args.fused_layer
     fanouts = tuple(int(f) for f in args.fanouts.split(","))
     assert len(fanouts) == 2, "this example has two layers"
     dev = torch.device("cuda", 0)
@@ -56,6 +61,8 @@ def main():
     sampler = gnc.NeighborSampler(ptrs, idxs, prob=full_val)
     perm = torch.randperm(num_v, generator=gen).to(torch.int32).to(dev)
     stages = {"sample": [], "gather": [], "aggregate": [], "dense": []}
+    if args.fused_layer:
+        stages["layer"] = []
 
     def timed(fn):
         """(result, microseconds), closed by a device synchronisation"""
@@ -75,8 +82,13 @@ def main():
             h, t_gather = x, 0.0                      # no gather stage: layer 0 reads x in place through src_nodes
         else:
             h, t_gather = timed(lambda: x[blocks[0].src_nodes.long()])
-        t_agg = t_dense = 0.0
+        t_agg = t_dense = t_layer = 0.0
         for k, blk in enumerate(blocks):
+            if args.fused_layer:
+                kw = {"val": full_val, "val_full": True} if args.weighted else {}
+                h, dt = timed(lambda: blk.sage(h, w_neigh[k], w_self[k], reduce=reduce, relu=True, gathered=k > 0, fused=True, **kw))
+                t_layer += dt
+                continue
 
             def aggregate():
                 y = torch.empty((blk.num_dst, h.shape[1]), device=dev)
@@ -97,14 +109,17 @@ def main():
             if agg is not None:
                 agg.close()
         if b > 0:
-            for stage, dt in (("sample", t_sample), ("gather", t_gather), ("aggregate", t_agg), ("dense", t_dense)):
-                stages[stage].append(dt)
+            for stage, dt in (("sample", t_sample), ("gather", t_gather), ("aggregate", t_agg), ("dense", t_dense), ("layer", t_layer)):
+                if stage in stages:
+                    stages[stage].append(dt)
         out = h
     rec = {"model": "sage_minibatch", "dataset": args.dataset, "num_v": num_v, "num_e": idxs.numel(), "batch": args.batch, "fanouts": list(fanouts), "weighted": args.weighted,
            "batches": args.batches, "last_blocks": [[blk.num_dst, blk.num_src, blk.num_edges] for blk in blocks],
            "finite": bool(torch.isfinite(out).all().item())}
     if args.block_run:
         rec["block_run"] = True
+    if args.fused_layer:
+        rec["fused_layer"] = True
     rec.update({k + "_us": statistics.median(v) for k, v in stages.items()})
     rec["total_us"] = sum(rec[k + "_us"] for k in stages)
     print(json.dumps(rec))

@@ -150,6 +150,10 @@ SIGNATURES = {
                                                   c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "gnnagg_block_gcn_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_block_sage_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_block_sage_supported": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_block_sage_grid_cap": (c_int, [c_int, c_int, c_int]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .aggregator import FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _dev_ptr, _dev_ptr_rows, _feat_dtype
+from .aggregator import FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _dev_ptr, _dev_ptr_rows, _feat_dtype, matmul_NN
 
 _U64 = (1 << 64) - 1
 
@@ -43,6 +43,22 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         Returns y, or (y, x_dst)."""
         return block_gcn_run(self, x, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out, out_dtype=out_dtype, relu=relu,
                              return_dst=return_dst)
+
+    def sage(self, x, w_neigh, w_self=None, bias=None, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None,
+             relu=False, fused=None):
+        """A SAGE layer on this block, out = act(x_dst @ w_self + aggregate(x) @ w_neigh + bias), in ONE launch on torch's current stream
+        (gnnagg_block_sage_run): the aggregate is never stored, x_dst never copied.  x, reduce, val, val_full, gathered: as in aggregate().
+          w_neigh, w_self   contiguous [F, n_out] tensors of x's dtype; w_self None: no self term (a GCN layer, out = aggregate(x) @ w_neigh).
+                            The self row of destination i is x[src_nodes[i]], or x[i] (gathered=True, or a block of global ids).
+          bias              None or float32 [n_out]
+          out               None or a contiguous [num_dst, n_out] tensor: float32 for a float32 x, float32 or bfloat16 for a bfloat16 x;
+                            out_dtype: the type of the out allocated here (x's by default)
+          fused             True: the kernel, ValueError where gnnagg_block_sage_supported says no.  False: the composition of existing
+                            calls (aggregate, cat, matmul_NN, bias, ReLU) -- for float32 the same bits.  None: the kernel where it is
+                            supported and was not measured slower (sage_prefers_fused).
+        Returns out."""
+        return block_sage_run(self, x, w_neigh, w_self=w_self, bias=bias, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
+                              out_dtype=out_dtype, relu=relu, fused=fused)
 
 
 def block_gcn_run(blk, x, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None, relu=False, return_dst=False):
@@ -110,6 +126,109 @@ def block_gcn_run(blk, x, reduce="mean", val=None, val_full=False, gathered=Fals
                                      ctypes.c_void_p(x_dst.data_ptr()) if x_dst is not None and blk.num_dst else None, feat, REDUCE[reduce], flags,
                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return (out, x_dst) if x_dst is not None else out
+
+
+def block_sage_supported(feat, n_out, dtype):
+    """gnnagg_block_sage_supported: does the fused kernel of Block.sage serve [feat] -> [n_out] with operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_sage_supported(int(feat), int(n_out), FEATURE_DTYPES[dtype]))
+
+
+def sage_prefers_fused(num_dst, feat, n_out, dtype):
+    """The fused=None rule of Block.sage: the kernel wherever it is supported.  (profiles/block_sage/rule_measurements.txt: the shapes
+    measured and what each arm took.)"""
+    return block_sage_supported(feat, n_out, dtype)
+
+
+def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None,
+                   relu=False, fused=None):
+    """Block.sage as a function (the thin form over gnnagg_block_sage_run); every dtype and shape refusal is raised before device work"""
+    if reduce not in REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (sorted(REDUCE), reduce))
+    mapped = blk.src_nodes is not None and not gathered
+    if val_full and blk.eid is None:
+        raise ValueError("val_full=True reads val through blk.eid: sample the block with return_eid=True")
+    if val_full and val is None:
+        raise ValueError("val_full=True needs val")
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = blk.num_src if not mapped else 0
+    if w_self is not None and not mapped:
+        need_rows = max(need_rows, blk.num_dst)
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    for name, w in (("w_neigh", w_neigh), ("w_self", w_self)):
+        if w is None and name == "w_self":
+            continue
+        if not isinstance(w, torch.Tensor) or w.dtype != x.dtype:
+            raise TypeError("%s must be a tensor of x's dtype %s, got %s" % (name, x.dtype, getattr(w, "dtype", type(w).__name__)))
+        if w.dim() != 2 or int(w.shape[0]) != feat or int(w.shape[1]) < 1 or w.shape != w_neigh.shape:
+            raise ValueError("%s must be [%d, n_out] with n_out >= 1%s, got %s" % (name, feat, "" if w is w_neigh else ", as w_neigh", tuple(w.shape)))
+    n_out = int(w_neigh.shape[1])
+    shape = (blk.num_dst, n_out)
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a torch.float32 tensor or None")
+        if tuple(bias.shape) != (n_out,):
+            raise ValueError("bias must be [%d], got %s" % (n_out, tuple(bias.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_sage_supported(feat, n_out, x.dtype):
+        raise ValueError("fused=True: gnnagg_block_sage_supported(feat=%d, n_out=%d, %s) says no" % (feat, n_out, x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full else None
+    p_val = _dev_ptr(val, torch.float32, "val")
+    p_wn, p_ws, p_b = _dev_ptr(w_neigh, x.dtype, "w_neigh"), _dev_ptr(w_self, x.dtype, "w_self"), _dev_ptr(bias, torch.float32, "bias")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("val", val), ("w_neigh", w_neigh), ("w_self", w_self), ("bias", bias), ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = sage_prefers_fused(blk.num_dst, feat, n_out, x.dtype)
+    if not fused:   # the composition a caller writes with the existing calls
+        y = block_gcn_run(blk, x, reduce=reduce, val=val, val_full=val_full, gathered=gathered, return_dst=mapped and w_self is not None)
+        if w_self is not None:
+            y, x_dst = y if mapped else (y, x[:blk.num_dst])
+            res = matmul_NN(torch.cat([x_dst, y], 1), torch.cat([w_self, w_neigh], 0), out_dtype=torch.float32)
+        else:
+            res = matmul_NN(y, w_neigh, out_dtype=torch.float32)
+        if bias is not None:
+            res = res + bias
+        if relu:
+            res = res.clamp_min(0)
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    check(lib().gnnagg_block_sage_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, p_ws, p_wn,
+                                      p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
+                                      REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
 
 
 def _check_fanout(fanout):

@@ -991,6 +991,45 @@ int gnnagg_block_gcn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst
                          const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, void *d_y, int y_dtype, void *d_x_dst,
                          int feat, int reduce, int flags, void *hip_stream);
 
+/* Block SAGE layer: DGL's / PyG's SAGEConv on one sampled block in one launch (csrc/agg_block_sage.hip) --
+ *   out[i] = act( x_dst[i] . W_self + aggr_{p in row i}(x_src) . W_neigh + bias )
+ * with no y in memory, no copy of x_dst, no concatenation and no second GEMM.
+ *   aggregation  a[i][0..feat) is the row gnnagg_block_gcn_run would store for the same (blk, src_nodes, val, eid, x, reduce) into a y of
+ *                the OPERANDS' type (x_dtype), whatever out_dtype is: the same chain in CSR order, the same mean division, 0 for a row
+ *                without edges; with bf16 operands a is rounded to bf16 once, exactly as a bf16 y store.  GNNAGG_FLAG_RELU applies to
+ *                out, not to a.
+ *   self row     s[i] = x[d_src_nodes ? d_src_nodes[i] : i], taken as it is.
+ *   combine      out[i][n] = act( sum_k s[i][k] W_self[k][n] (k ascending), then sum_k a[i][k] W_neigh[k][n] (k ascending), all in ONE
+ *                fp32 accumulator, + bias[n] ).  d_w_self NULL skips the first sum (a GCN layer on a block, out = a . W_neigh); d_bias
+ *                NULL adds nothing; ReLU as GNNAGG_FLAG_RELU everywhere: a NaN stays a NaN.
+ *   types        x, W_self and W_neigh share x_dtype (GNNAGG_DTYPE_F32 or GNNAGG_DTYPE_BF16); bias is fp32; both weights are
+ *                [feat, n_out], row-major and dense; out is dense [num_dst, n_out]: fp32 for fp32 operands, fp32 or bf16 for bf16
+ *                operands (one round-to-nearest-even at the store).  out aliases no input.
+ *   fp32         the accumulator is the ascending-k fmaf chain on v_mfma_f32_16x16x4_f32 of gnnagg_matmul_nn: out equals, bit for bit,
+ *                relu(matmul_nn(cat([x_dst, y], 1), cat([W_self, W_neigh], 0)) + bias) with y of gnnagg_block_gcn_run.  (The zero
+ *                columns that pad feat to a multiple of 4 between the halves change no bit: an accumulator that started at +0 is never -0.)
+ *   bf16         the product runs on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the contract of gnnagg_matmul_nn_typed
+ *                (|out - out64| <= 1e-5 * sum_k |operand| |w| over the stored operands, before the one rounding of a bf16 out).
+ *   determinism  the bits depend on the arguments only, never on alignment, pitch or lane geometry.  No atomics.
+ *   non-finite   +-Inf / NaN reach exactly the rows of out that hold them as a neighbour or as their self row.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_dst = 0 is a valid call that launches nothing.  Rows of any length are walked by one lane group, as in
+ *                gnnagg_block_gcn_run.  Workgroups walk tiles of 16 rows; a launch holds at most gnnagg_block_sage_grid_cap workgroups.
+ *   range        gnnagg_block_sage_supported(feat, n_out, x_dtype) is the one place the rule lives: 1 <= feat, n_out <= 256 and the
+ *                row tile plus (bf16) the image of both weights inside the 160 KB of LDS of a CU -- every fp32 shape up to 256 x 256;
+ *                bf16 e.g. 128 x 256, 256 x 128.  gnnagg_block_sage_grid_cap: the workgroups a launch of that shape is capped at on the
+ *                current device, 0 outside the range.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; feat < 1; n_out < 1; x_pitch < feat;
+ *                an unknown x_dtype, out_dtype or reduce; fp32 operands with a bf16 out; any flag but GNNAGG_FLAG_RELU; d_eid without
+ *                d_val; a shape outside the supported range; a null d_blk_ptr, d_x, d_w_neigh or d_out with num_dst > 0.
+ * (tests/test_block_sage_host.py, tests/test_gpu_block_sage.py; DESIGN.md "Block SAGE layer") */
+int gnnagg_block_sage_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes,
+                          const float *d_val, const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, int feat,
+                          const void *d_w_self, const void *d_w_neigh, const float *d_bias, int n_out,
+                          void *d_out, int out_dtype, int reduce, int flags, void *hip_stream);
+int gnnagg_block_sage_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_sage_grid_cap(int feat, int n_out, int x_dtype);
+
 /* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
