@@ -12,7 +12,7 @@ from .aggregator import (  # noqa: F401
     gat_project, last_project_path, gatv2_run, dot_attn_run, gcn_run_multi, pna_delta,
 )
 from .sampling import (  # noqa: F401
-    Block, NeighborSampler, block_gcn_run, block_sage_run, block_sage_supported, sage_prefers_fused, sample_block_host,
+    Block, NeighborSampler, block_attn_run, block_gcn_run, block_sage_run, block_sage_supported, sage_prefers_fused, sample_block_host,
 )
 from . import graph  # noqa: F401
 from . import probe  # noqa: F401

@@ -16,6 +16,7 @@ MODE_ROWS, MODE_SCHEDULED, MODE_BALANCED = 0, 1, 2
 FLAG_ACCUMULATE = 1
 FLAG_RELU = 2
 DTYPE_F32, DTYPE_BF16 = 0, 1
+ATTN_DOT, ATTN_GATV2 = 0, 1   # gnnagg_block_attn_run
 AGGR_SUM, AGGR_MEAN, AGGR_MIN, AGGR_MAX, AGGR_VAR, AGGR_STD = 1, 2, 4, 8, 16, 32   # gnnagg_gcn_run_multi
 SCALER_IDENTITY, SCALER_AMPLIFICATION, SCALER_ATTENUATION = 1, 2, 4
 
@@ -154,6 +155,9 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_block_sage_supported": (c_int, [c_int, c_int, c_int]),
     "gnnagg_block_sage_grid_cap": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_block_attn_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p,
+                                      ctypes.c_longlong, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p,
+                                      c_int, c_int, c_int, c_void_p]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

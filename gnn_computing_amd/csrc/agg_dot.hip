@@ -31,11 +31,7 @@ struct DotArgs : Gatv2Args {   // q is xd, k is xs (a and slope are unused); wha
     float scale;
 };
 
-// the batch of the geometries with kDotWideNf or more fragments per lane
-static constexpr int kDotWideBatch = kGatv2Batch / 2;
-static constexpr int kDotWideNf = 2;
-template <int NF>
-constexpr int dot_batch() { return NF >= kDotWideNf ? kDotWideBatch : kGatv2Batch; }
+// (dot_batch: gatv2_shared.cuh -- the block kernel walks the same batches)
 static_assert(kGatv2Batch % dot_batch<kDotWideNf>() == 0, "a segment's chunks are cut at multiples of kGatv2Batch");
 
 struct DotEdgeArgs : DotArgs {

@@ -23,6 +23,13 @@ struct Gatv2Args {
     float *stat;        // ... with [V, heads, 2] = every (row, head)'s final (maximum, denominator); launch_attn_finish makes weights of them
 };
 
+// The batch of the dot-product walks (agg_dot.hip: dot_walk; agg_block_attn.hip): kGatv2Batch edges, halved for the geometries with
+// kDotWideNf or more fragments per lane -- a batch holds k AND v fragments.  The batches are part of the arithmetic.
+static constexpr int kDotWideBatch = kGatv2Batch / 2;
+static constexpr int kDotWideNf = 2;
+template <int NF>
+constexpr int dot_batch() { return NF >= kDotWideNf ? kDotWideBatch : kGatv2Batch; }
+
 // Whether fragment f of this lane starts its head (column hf * dhead): the one lane that stores the head's score and (m, den)
 __device__ __forceinline__ bool gatv2_head_owner(const Gatv2Args &a, int col, int hf) { return hf >= 0 && col == hf * a.dhead; }
 

@@ -4,13 +4,15 @@ either path, bit for bit.  Sampling is not capturable into a HIP graph (sizes ar
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, lib
-from .aggregator import FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _dev_ptr, _dev_ptr_rows, _feat_dtype, matmul_NN
+from .aggregator import (FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _bias_heads, _dev_ptr, _dev_ptr_rows, _edge_rows, _feat_dtype,
+                         matmul_NN)
 
 _U64 = (1 << 64) - 1
 
@@ -59,6 +61,28 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         Returns out."""
         return block_sage_run(self, x, w_neigh, w_self=w_self, bias=bias, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                               out_dtype=out_dtype, relu=relu, fused=fused)
+
+    def attend(self, q, k, v=None, kind="dot", a=None, heads=1, scale=None, slope=0.2, bias=None, bias_full=False, edge=None, edge_full=False,
+               gathered=False, out=None, out_dtype=None):
+        """Edge attention on this block in ONE launch on torch's current stream (gnnagg_block_attn_run): no handle, no plan, no gathered
+        copy of any operand.  Rows of at most 128 edges have, bit for bit, what self.gat().run_dot / run_v2 gives on the gathered operands;
+        a longer row (fanout = -1 on a hub) is walked by one lane group and holds the float64 bound of those calls instead -- there the
+        handle's segmented rows remain the fast path.
+          kind="dot"    y[i] = sum_p softmax_p(scale * q[d(i)] . k[s(p)]) v[s(p)] per head; scale=None is 1 / sqrt(F / heads)
+          kind="gatv2"  q is xd, k is xs: y[i] = sum_p softmax_p(a[h] . leaky(q[d(i)] + k[s(p)])) k[s(p)]; needs a (float32, heads * D
+                        elements) and refuses v
+          q, k, v       float32 or bfloat16 [rows, F], one dtype; row-pitched column views (stride(1) == 1) are taken as they are, k and v
+                        share stride(0).  gathered=False on a relabelled block: the matrices of the graph the block was sampled from, read
+                        through src_nodes (s(p) = src_nodes[idx[p]], d(i) = src_nodes[i]).  gathered=True, or a block of global ids:
+                        idx and the row number index them directly.
+          bias          None or float32 [E], [E, 1] or [E, heads], added to the score (-inf masks the edge): one row per edge of the block,
+                        or -- bias_full=True -- per edge of the full CSR, read through self.eid
+          edge          None or [E, F] of q's dtype (stride(1) == 1), added to the scored row (and, for kind="dot", to the summed row):
+                        one row per edge of the block, or -- edge_full=True -- per edge of the full CSR, read through self.eid
+          out           None or a contiguous [num_dst, F] float32 / bfloat16 tensor; out_dtype: the type of the y allocated here (q's by default)
+        Rows without edges are +0.  Returns y."""
+        return block_attn_run(self, q, k, v, kind=kind, a=a, heads=heads, scale=scale, slope=slope, bias=bias, bias_full=bias_full, edge=edge,
+                              edge_full=edge_full, gathered=gathered, out=out, out_dtype=out_dtype)
 
 
 def block_gcn_run(blk, x, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None, relu=False, return_dst=False):
@@ -227,6 +251,103 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
     check(lib().gnnagg_block_sage_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, p_ws, p_wn,
                                       p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
                                       REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+ATTN_KINDS = {"dot": _lib.ATTN_DOT, "gatv2": _lib.ATTN_GATV2}
+
+
+def block_attn_run(blk, q, k, v=None, kind="dot", a=None, heads=1, scale=None, slope=0.2, bias=None, bias_full=False, edge=None,
+                   edge_full=False, gathered=False, out=None, out_dtype=None):
+    """Block.attend as a function (the thin form over gnnagg_block_attn_run); every dtype and shape refusal is raised before device work"""
+    if kind not in ATTN_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(ATTN_KINDS), kind))
+    dot = kind == "dot"
+    mapped = blk.src_nodes is not None and not gathered
+    for flag, name, t in ((bias_full, "bias", bias), (edge_full, "edge", edge)):
+        if flag and blk.eid is None:
+            raise ValueError("%s_full=True reads %s through blk.eid: sample the block with return_eid=True" % (name, name))
+        if flag and t is None:
+            raise ValueError("%s_full=True needs %s" % (name, name))
+    if bias is not None and edge is not None and bool(bias_full) != bool(edge_full):
+        raise ValueError("bias and edge are both per edge of the block or both per edge of the full CSR (one eid serves both)")
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    if dot and v is None:
+        raise ValueError("kind='dot' needs v (the rows to sum)")
+    if not dot and v is not None:
+        raise ValueError("kind='gatv2' sums the rows it scores (k): v must be None")
+    if dot and a is not None:
+        raise ValueError("kind='dot' takes no a")
+    # types and shapes
+    xdt = _feat_dtype(q, "q")
+    ops = (("q", q), ("k", k)) + ((("v", v),) if dot else ())
+    for name, t in ops[1:]:
+        if _feat_dtype(t, name) != xdt:
+            raise TypeError("%s (%s) must have q's dtype %s" % (name, t.dtype, q.dtype))
+    for name, t in ops:
+        if t.dim() != 2 or t.shape[1] < 1:
+            raise ValueError("%s must be 2-D [rows, F] with F >= 1, got %s" % (name, tuple(t.shape)))
+    feat, heads = int(q.shape[1]), int(heads)
+    if heads < 1 or feat % heads != 0:
+        raise ValueError("heads = %d does not divide F = %d" % (heads, feat))
+    if feat > Aggregator_GAT.GATV2_MAX_FEAT:
+        raise ValueError("F = %d is above the kernel's limit of %d columns" % (feat, Aggregator_GAT.GATV2_MAX_FEAT))
+    for name, t in ops[1:]:
+        if int(t.shape[1]) != feat:
+            raise ValueError("%s has %d columns, q has %d" % (name, t.shape[1], feat))
+    if dot and (tuple(k.shape) != tuple(v.shape) or (k.shape[0] > 1 and k.stride(0) != v.stride(0))):
+        raise ValueError("k %s and v %s must have one shape and share one row pitch (stride(0) = %d and %d)" %
+                         (tuple(k.shape), tuple(v.shape), k.stride(0), v.stride(0)))
+    if not mapped and (int(k.shape[0]) < blk.num_src or int(q.shape[0]) < blk.num_dst):
+        raise ValueError("q has %d rows and k %d, the block's ids index %d and %d (gathered=%s)" %
+                         (q.shape[0], k.shape[0], blk.num_dst, blk.num_src, bool(gathered)))
+    if not dot:
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32:
+            raise TypeError("kind='gatv2' needs a: a torch.float32 tensor of heads * D elements")
+        if int(a.numel()) != feat:
+            raise ValueError("a %s does not hold [heads = %d, D = %d]" % (tuple(a.shape), heads, feat // heads))
+        if not 0.0 <= float(slope) <= 1.0:
+            raise ValueError("slope = %r is outside [0, 1]" % (slope,))
+    scale = 1.0 / math.sqrt(feat // heads) if scale is None else float(scale)
+    if not math.isfinite(scale) or not math.isfinite(ctypes.c_float(scale).value):
+        raise ValueError("scale = %r is not finite (in fp32)" % (scale,))
+    bias_heads = 1
+    if bias is not None:
+        bias_heads = _bias_heads(bias, int(bias.shape[0]) if bias_full and isinstance(bias, torch.Tensor) and bias.dim() else blk.num_edges, heads,
+                                 q, "Block.attend")
+    ef = None
+    if edge is not None:
+        ef = _edge_rows(edge, int(edge.shape[0]) if edge_full and isinstance(edge, torch.Tensor) and edge.dim() else blk.num_edges, feat, q,
+                        "Block.attend")
+    shape = (blk.num_dst, feat)
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    # device tensors, contiguous where the call wants them dense
+    (pq, q_pitch), (pk, kv_pitch) = _dev_ptr_rows(q, q.dtype, "q"), _dev_ptr_rows(k, k.dtype, "k")
+    pv = _dev_ptr_rows(v, v.dtype, "v")[0] if dot else None
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if bias_full or edge_full else None
+    p_a, p_bias = _dev_ptr(a, torch.float32, "a"), _dev_ptr(bias, torch.float32, "bias")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in ops[1:] + (("blk.ptr", blk.ptr), ("a", a), ("out", out)):
+        if t is not None and t.device != q.device:
+            raise ValueError("%s lives on %s, q on %s" % (name, t.device, q.device))
+    # ---- device work
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype or q.dtype, device=q.device)
+    has_e = blk.num_edges > 0
+    check(lib().gnnagg_block_attn_run(p_ptr, p_idx if has_e else None, blk.num_dst, p_src, p_eid if has_e else None, ATTN_KINDS[kind], pq, q_pitch, pk, pv, kv_pitch,
+                                      p_a, ctypes.c_float(slope), ctypes.c_float(scale), p_bias if has_e else None, bias_heads,
+                                      ef[0] if ef is not None and has_e else None, ef[1] if ef is not None else 0, xdt,
+                                      ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype], feat, heads,
                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 

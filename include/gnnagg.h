@@ -1030,6 +1030,42 @@ int gnnagg_block_sage_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
 int gnnagg_block_sage_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_sage_grid_cap(int feat, int n_out, int x_dtype);
 
+/* Block attention: scaled dot-product (gnnagg_dot_attn_run) or GATv2 (gnnagg_gatv2_run) attention on one sampled block in one launch
+ * (csrc/agg_block_attn.hip), with the operands read where they live --
+ *   s(p) = d_src_nodes ? d_src_nodes[d_blk_idx[p]] : d_blk_idx[p]      the source row of block edge p
+ *   d(i) = d_src_nodes ? d_src_nodes[i] : i                            the row of destination i
+ *   t(p) = d_eid ? d_eid[p] : p                                        the position of block edge p's per-edge operands
+ *   GNNAGG_ATTN_DOT    e_p = scale * q[d(i)] . (k[s(p)] (+ ef[t(p)])) (+ bias[t(p)(, h)]);  y[i] = sum_p softmax_p(e) (v[s(p)] (+ ef[t(p)]))
+ *   GNNAGG_ATTN_GATV2  e_p = a[h] . leaky(xd[d(i)] + (xs[s(p)] (+ ef[t(p)]))) (+ bias[t(p)(, h)]);  y[i] = sum_p softmax_p(e) xs[s(p)]
+ *                      with d_q as xd and d_k as xs; d_v stays NULL
+ * per head of feat / heads columns; the formulas, the bias, the masks (-inf) and the edge rows are those of the handle's calls.
+ *   operands     d_q rows are q_pitch ELEMENTS apart, d_k and d_v rows kv_pitch, d_ef rows ef_pitch (each >= feat): column views of one
+ *                projection serve.  With d_src_nodes they are the matrices of the graph the block was sampled from; without, the rows
+ *                blk_idx and the row number name directly.  d_bias (NULL: none) is fp32 [., bias_heads], bias_heads 1 or heads; d_ef (NULL:
+ *                none) holds rows of feat elements of x_dtype.  Without d_eid both hold one row per edge of the block; with d_eid one row
+ *                per edge of the full CSR, d_eid [edges of the block] being the sampler's d_blk_eid.  d_a: fp32 [heads, feat / heads].
+ *   types        GNNAGG_DTYPE_F32 and GNNAGG_DTYPE_BF16 operands, an fp32 or bf16 y (ONE rounding of the fp32 result), dense
+ *                [num_dst, feat]; feat <= 1024 and heads divides feat.  A row without edges is exactly +0.
+ *   bits         the walk is the handle's online softmax (the same batches, rescale rule, head reduction and CSR order): a row of at most
+ *                128 edges has, bit for bit, what gnnagg_dot_attn_run(_bias, _edge) / gnnagg_gatv2_run(_bias, _edge) give on a GAT
+ *                aggregator over (d_blk_ptr, d_blk_idx) with the operands gathered.  A LONGER row (fanout = -1 on a hub) is walked by its
+ *                one lane group where the handle folds segments: it differs from the handle in the last bits and holds the float64
+ *                bound of those calls, 1e-5 (1 + L) S.  The bits never depend on alignment, pitch or lane geometry.  No atomics.
+ *   the call     stateless: no handle, no plan, no allocation, no LDS, no scratch, ONE launch on hip_stream; capturable into a HIP graph.
+ *                num_dst = 0 is a valid call that launches nothing.  Ids are not validated.  There are no attention weights or row
+ *                statistics out.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; an unknown kind, x_dtype or y_dtype;
+ *                heads not dividing feat; feat above 1024; q_pitch, kv_pitch or (with d_ef) ef_pitch below feat; a non-finite scale (dot);
+ *                a slope outside [0, 1] (GATv2); bias_heads neither 1 nor heads; d_eid with neither d_bias nor d_ef; d_v given for GATv2
+ *                or NULL for the dot product; a null d_blk_ptr, d_q, d_k, d_a (GATv2) or d_y with num_dst > 0.
+ * (tests/test_block_attn_host.py, tests/test_gpu_block_attn.py; DESIGN.md "Block attention") */
+#define GNNAGG_ATTN_DOT 0
+#define GNNAGG_ATTN_GATV2 1
+int gnnagg_block_attn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const int *d_eid, int kind,
+                          const void *d_q, long long q_pitch, const void *d_k, const void *d_v, long long kv_pitch, const float *d_a,
+                          float slope, float scale, const float *d_bias, int bias_heads, const void *d_ef, long long ef_pitch, int x_dtype,
+                          void *d_y, int y_dtype, int feat, int heads, void *hip_stream);
+
 /* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
