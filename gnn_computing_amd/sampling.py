@@ -62,6 +62,23 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         return block_sage_run(self, x, w_neigh, w_self=w_self, bias=bias, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                               out_dtype=out_dtype, relu=relu, fused=fused)
 
+    def rgcn(self, x, w_rel, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False, gathered=False, out=None,
+             out_dtype=None, relu=False, fused=None):
+        """A relational (typed-edge) GCN layer on this block -- RGCNConv / RelGraphConv without a weight decomposition --
+        out = act(x_dst @ w_self + sum_r aggregate_r(x) @ w_rel[r] + bias) in ONE launch on torch's current stream (gnnagg_block_rgcn_run):
+        aggregate_r runs over the row's edges of type r only; no sub-block is built, no aggregate stored.  x, val, val_full, gathered, bias,
+        out, out_dtype, relu: as in sage().
+          w_rel        contiguous [R, F, n_out] of x's dtype; w_self None or contiguous [F, n_out] of x's dtype
+          etype        int32, one type per edge of the block, or -- etype_full=True -- per edge of the full CSR, read through self.eid.
+                       An edge whose type lies outside [0, R) is skipped: the block with that edge deleted.
+          reduce       "sum" or "mean"; the mean is per (row, relation), over the row's edges of that relation
+          fused        True: the kernel, ValueError where gnnagg_block_rgcn_supported says no.  False: the composition of existing calls
+                       (one filtered sub-block and one aggregate per relation, cat, matmul_NN, bias, ReLU) -- for float32 the same
+                       bits.  None: the kernel where it is supported and was not measured slower (rgcn_prefers_fused).
+        Returns out."""
+        return block_rgcn_run(self, x, w_rel, etype, w_self=w_self, bias=bias, reduce=reduce, etype_full=etype_full, val=val, val_full=val_full,
+                              gathered=gathered, out=out, out_dtype=out_dtype, relu=relu, fused=fused)
+
     def attend(self, q, k, v=None, kind="dot", a=None, heads=1, scale=None, slope=0.2, bias=None, bias_full=False, edge=None, edge_full=False,
                gathered=False, out=None, out_dtype=None):
         """Edge attention on this block in ONE launch on torch's current stream (gnnagg_block_attn_run): no handle, no plan, no gathered
@@ -250,6 +267,144 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
         out = torch.empty(shape, dtype=odt, device=x.device)
     check(lib().gnnagg_block_sage_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, p_ws, p_wn,
                                       p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
+                                      REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+RGCN_REDUCE = ("sum", "mean")
+
+
+def block_rgcn_supported(feat, n_out, num_rel, dtype):
+    """gnnagg_block_rgcn_supported: does the fused kernel of Block.rgcn serve [feat] -> [n_out] over num_rel relations with operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_rgcn_supported(int(feat), int(n_out), int(num_rel), FEATURE_DTYPES[dtype]))
+
+
+def rgcn_prefers_fused(num_dst, feat, n_out, num_rel, dtype):
+    """The fused=None rule of Block.rgcn: the kernel wherever it is supported.  (profiles/block_rgcn/rule_measurements.txt: the shapes
+    measured and what each arm took.)"""
+    return block_rgcn_supported(feat, n_out, num_rel, dtype)
+
+
+def _relation_block(blk, row_of_edge, keep):
+    """the sub-block of the edges `keep` marks, in CSR order (a stable filter): what the composition of Block.rgcn aggregates per relation"""
+    deg = torch.bincount(row_of_edge[keep], minlength=blk.num_dst)
+    ptr = torch.zeros(blk.num_dst + 1, dtype=torch.int32, device=blk.ptr.device)
+    ptr[1:] = deg.cumsum(0)
+    idx = blk.idx[keep].contiguous()
+    return Block(ptr, idx, blk.src_nodes, None, blk.num_dst, blk.num_src, int(idx.numel()))
+
+
+def block_rgcn_run(blk, x, w_rel, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False, gathered=False,
+                   out=None, out_dtype=None, relu=False, fused=None):
+    """Block.rgcn as a function (the thin form over gnnagg_block_rgcn_run); every dtype and shape refusal is raised before device work"""
+    if reduce not in RGCN_REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (list(RGCN_REDUCE), reduce))
+    mapped = blk.src_nodes is not None and not gathered
+    for flag, name, t in ((etype_full, "etype", etype), (val_full, "val", val)):
+        if flag and blk.eid is None:
+            raise ValueError("%s_full=True reads %s through blk.eid: sample the block with return_eid=True" % (name, name))
+        if flag and t is None:
+            raise ValueError("%s_full=True needs %s" % (name, name))
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = blk.num_src if not mapped else 0
+    if w_self is not None and not mapped:
+        need_rows = max(need_rows, blk.num_dst)
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    if not isinstance(etype, torch.Tensor) or etype.dtype != torch.int32:
+        raise TypeError("etype must be a torch.int32 tensor, got %s" % (getattr(etype, "dtype", type(etype).__name__),))
+    if etype.dim() != 1 or (not etype_full and int(etype.numel()) != blk.num_edges):
+        raise ValueError("etype must be 1-D%s, got %s" % ("" if etype_full else " with one type per edge of the block: [%d]" % blk.num_edges,
+                                                           tuple(etype.shape)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    if not isinstance(w_rel, torch.Tensor) or w_rel.dtype != x.dtype:
+        raise TypeError("w_rel must be a tensor of x's dtype %s, got %s" % (x.dtype, getattr(w_rel, "dtype", type(w_rel).__name__)))
+    if w_rel.dim() != 3 or int(w_rel.shape[0]) < 1 or int(w_rel.shape[1]) != feat or int(w_rel.shape[2]) < 1:
+        raise ValueError("w_rel must be [R, %d, n_out] with R >= 1 and n_out >= 1, got %s" % (feat, tuple(w_rel.shape)))
+    num_rel, n_out = int(w_rel.shape[0]), int(w_rel.shape[2])
+    if w_self is not None:
+        if not isinstance(w_self, torch.Tensor) or w_self.dtype != x.dtype:
+            raise TypeError("w_self must be a tensor of x's dtype %s, got %s" % (x.dtype, getattr(w_self, "dtype", type(w_self).__name__)))
+        if tuple(w_self.shape) != (feat, n_out):
+            raise ValueError("w_self must be [%d, %d], as a relation of w_rel, got %s" % (feat, n_out, tuple(w_self.shape)))
+    shape = (blk.num_dst, n_out)
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a torch.float32 tensor or None")
+        if tuple(bias.shape) != (n_out,):
+            raise ValueError("bias must be [%d], got %s" % (n_out, tuple(bias.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_rgcn_supported(feat, n_out, num_rel, x.dtype):
+        raise ValueError("fused=True: gnnagg_block_rgcn_supported(feat=%d, n_out=%d, num_rel=%d, %s) says no" % (feat, n_out, num_rel, x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full or etype_full else None
+    p_et, p_val = _dev_ptr(etype, torch.int32, "etype"), _dev_ptr(val, torch.float32, "val")
+    p_wr, p_ws, p_b = _dev_ptr(w_rel, x.dtype, "w_rel"), _dev_ptr(w_self, x.dtype, "w_self"), _dev_ptr(bias, torch.float32, "bias")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("etype", etype), ("val", val), ("w_rel", w_rel), ("w_self", w_self), ("bias", bias), ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = rgcn_prefers_fused(blk.num_dst, feat, n_out, num_rel, x.dtype)
+    if not fused:   # the composition a caller writes with the existing calls: R filtered sub-blocks, R aggregations, a cat, a GEMM
+        t_e = etype[blk.eid.long()] if etype_full else etype
+        v_e = val[blk.eid.long()] if val_full else val
+        row_of_edge = torch.searchsorted(blk.ptr[1:].long().contiguous(), torch.arange(blk.num_edges, device=x.device), right=True)
+        parts = []
+        for r in range(num_rel):
+            keep = t_e == r
+            sub = _relation_block(blk, row_of_edge, keep)
+            y = block_gcn_run(sub, x, reduce=reduce, val=None if v_e is None else v_e[keep].contiguous(), gathered=gathered,
+                              return_dst=mapped and w_self is not None and r == 0)
+            if isinstance(y, tuple):
+                y, x_dst = y
+                parts.append(x_dst)
+            elif w_self is not None and r == 0:
+                parts.append(x[:blk.num_dst])
+            parts.append(y)
+        ws = [] if w_self is None else [w_self]
+        res = matmul_NN(torch.cat(parts, 1), torch.cat(ws + list(w_rel.unbind(0)), 0), out_dtype=torch.float32)
+        if bias is not None:
+            res = res + bias
+        if relu:
+            res = res.clamp_min(0)
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    has_e = blk.num_edges > 0
+    if not int(etype.numel()):   # (an empty tensor has a null pointer and the call wants an address: one element nobody reads)
+        p_et = _dev_ptr(torch.zeros(1, dtype=torch.int32, device=x.device), torch.int32, "etype")
+    check(lib().gnnagg_block_rgcn_run(p_ptr, p_idx if has_e else None, blk.num_dst, p_src, p_et, p_eid if etype_full else None, p_val,
+                                      p_eid if val_full else None, px, xdt, pitch, feat, p_ws, p_wr, num_rel, p_b, n_out,
+                                      ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
                                       REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out

@@ -1030,6 +1030,49 @@ int gnnagg_block_sage_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
 int gnnagg_block_sage_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_sage_grid_cap(int feat, int n_out, int x_dtype);
 
+/* Block R-GCN layer: a relational (typed-edge) GCN layer -- PyG's RGCNConv, DGL's RelGraphConv without a weight decomposition -- on one
+ * sampled block in one launch (csrc/agg_block_rgcn.hip).  With num_rel relations,
+ *   out[i] = act( x_dst[i] . W_self + sum_{r < num_rel} aggr_{p in row i, t(p) == r}( w(p) x[s(p)] ) . W_rel[r] + bias )
+ * with no filtered sub-block, no per-relation y in memory, no concatenation and no GEMM launch.
+ *   edge types   t(p) = d_etype_eid ? d_etype[d_etype_eid[p]] : d_etype[p]: one int32 per edge of the block, or -- with d_etype_eid, the
+ *                sampler's d_blk_eid -- per edge of the full CSR.  An edge with t(p) outside [0, num_rel) is skipped: its row of x is
+ *                never read, it is never counted; the result is that of the block with the edge deleted.
+ *   aggregation  s(p) as in gnnagg_block_gcn_run; w(p) = !d_val ? 1.0f : d_val_eid ? d_val[d_val_eid[p]] : d_val[p].  a_r[i][0..feat) is
+ *                the row gnnagg_block_gcn_run would store for the sub-block that keeps, in CSR order, the edges with t(p) == r, into a y
+ *                of the OPERANDS' type: per (row, relation, column) one fp32 chain acc = 0; acc = fmaf(widen(x), w, acc) in increasing p;
+ *                GNNAGG_REDUCE_MEAN then divides by (float) of the number of edges of relation r IN THE ROW where that is > 0 (RGCNConv's
+ *                aggr="mean"); a (row, relation) without edges is +0.  With bf16 operands a_r is rounded to bf16 once, as a bf16 y store.
+ *                There is no GNNAGG_REDUCE_MAX.
+ *   self row     x[d_src_nodes ? d_src_nodes[i] : i], taken as it is; d_w_self NULL: no self term.
+ *   combine      ONE fp32 accumulator, k ascending over the self row and W_self, then over a_0 and W_rel[0], ..., a_{R-1} and W_rel[R-1];
+ *                + bias[n] (d_bias NULL adds nothing); ReLU with GNNAGG_FLAG_RELU: a NaN stays a NaN.
+ *   types        x, W_self [feat, n_out] and W_rel [num_rel, feat, n_out] share x_dtype (GNNAGG_DTYPE_F32 or GNNAGG_DTYPE_BF16), row-major
+ *                and dense; bias is fp32; out is dense [num_dst, n_out]: fp32 for fp32 operands, fp32 or bf16 for bf16 operands (one
+ *                round-to-nearest-even at the store).  out aliases no input.  d_x rows are x_pitch ELEMENTS apart.
+ *   fp32         bit for bit relu(matmul_nn(cat([x_dst, y_0, ..., y_{R-1}], 1), cat([W_self, W_rel[0], ..., W_rel[R-1]], 0)) + bias)
+ *                with y_r of gnnagg_block_gcn_run on the sub-block of relation r (v_mfma_f32_16x16x4_f32, the ascending-k fmaf chain).
+ *   bf16         v_mfma_f32_16x16x32_bf16 with fp32 accumulation: the contract of gnnagg_matmul_nn_typed over the stored operands
+ *                (|out - out64| <= 1e-5 * sum_k |operand| |w|, before the one rounding of a bf16 out).
+ *   determinism  the bits depend on the arguments only, never on alignment, pitch, lane geometry or how the types interleave.  No atomics.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_dst = 0 is a valid call that launches nothing.  Rows of any length are walked once by one lane group.  Workgroups
+ *                walk tiles of 16 rows; a launch holds at most gnnagg_block_rgcn_grid_cap workgroups (0 outside the range).
+ *   range        gnnagg_block_rgcn_supported(feat, n_out, num_rel, x_dtype) is the one place the rule lives: 1 <= feat, n_out <= 256,
+ *                num_rel >= 1 and the row tile of num_rel + 1 slots, the counts and (bf16) the fp32 running sums and the image of the
+ *                stacked weights inside the 160 KB of LDS of a CU -- fp32 e.g. 256 columns x 8 relations, 128 x 18; bf16 e.g.
+ *                128 -> 64 with 4 relations.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; feat < 1; n_out < 1; num_rel < 1;
+ *                x_pitch < feat; an unknown x_dtype or out_dtype; fp32 operands with a bf16 out; a reduce that is neither sum nor mean;
+ *                any flag but GNNAGG_FLAG_RELU; d_val_eid without d_val; d_etype_eid without d_etype; a shape outside the supported
+ *                range; a null d_blk_ptr, d_etype, d_x, d_w_rel or d_out with num_dst > 0.
+ * (tests/test_block_rgcn_host.py, tests/test_gpu_block_rgcn.py; DESIGN.md "Block R-GCN layer") */
+int gnnagg_block_rgcn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const int *d_etype,
+                          const int *d_etype_eid, const float *d_val, const int *d_val_eid, const void *d_x, int x_dtype, long long x_pitch,
+                          int feat, const void *d_w_self, const void *d_w_rel, int num_rel, const float *d_bias, int n_out, void *d_out,
+                          int out_dtype, int reduce, int flags, void *hip_stream);
+int gnnagg_block_rgcn_supported(int feat, int n_out, int num_rel, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_rgcn_grid_cap(int feat, int n_out, int num_rel, int x_dtype);
+
 /* Block attention: scaled dot-product (gnnagg_dot_attn_run) or GATv2 (gnnagg_gatv2_run) attention on one sampled block in one launch
  * (csrc/agg_block_attn.hip), with the operands read where they live --
  *   s(p) = d_src_nodes ? d_src_nodes[d_blk_idx[p]] : d_blk_idx[p]      the source row of block edge p
