@@ -160,6 +160,11 @@ SIGNATURES = {
                                       c_void_p]),
     "gnnagg_block_rgcn_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "gnnagg_block_rgcn_grid_cap": (c_int, [c_int, c_int, c_int, c_int]),
+    "gnnagg_block_rgcn_basis_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                            ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                            c_int, c_int, c_int, c_void_p]),
+    "gnnagg_block_rgcn_basis_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "gnnagg_block_rgcn_basis_grid_cap": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "gnnagg_block_attn_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p,
                                       ctypes.c_longlong, c_void_p, c_float, c_float, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p,
                                       c_int, c_int, c_int, c_void_p]),

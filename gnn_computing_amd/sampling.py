@@ -79,6 +79,22 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         return block_rgcn_run(self, x, w_rel, etype, w_self=w_self, bias=bias, reduce=reduce, etype_full=etype_full, val=val, val_full=val_full,
                               gathered=gathered, out=out, out_dtype=out_dtype, relu=relu, fused=fused)
 
+    def rgcn_basis(self, x, bases, comp, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False, gathered=False,
+                   out=None, out_dtype=None, relu=False, fused=None):
+        """rgcn() with the basis decomposition w_rel[r] = sum_b comp[r, b] * bases[b] -- RGCNConv(num_bases=B), RelGraphConv(regularizer=
+        "basis") -- in ONE launch on torch's current stream (gnnagg_block_rgcn_basis_run), for graphs with many relations:
+        out = act(x_dst @ w_self + sum_b g_b @ bases[b] + bias), g_b[i] = sum over the row's edges of comp[t, b] * s * x_src with s = val
+        (sum) or val / (the row's edges of type t) (mean).  No w_rel is built, and the kernel's LDS holds B + 1 slots per row whatever R is.
+        x, etype, etype_full, val, val_full, gathered, w_self, bias, out, out_dtype, relu: as in rgcn().
+          bases        contiguous [B, F, n_out] of x's dtype
+          comp         contiguous float32 [R, B]
+          fused        True: the kernel, ValueError where gnnagg_block_rgcn_basis_supported says no.  False: the route without this call
+                       (w_rel = einsum(comp, bases) in x's dtype, then rgcn(..., fused=None)).  None: the kernel where it is supported
+                       and was not measured slower -- where rgcn()'s own kernel cannot hold R relations (rgcn_basis_prefers_fused).
+        Returns out."""
+        return block_rgcn_basis_run(self, x, bases, comp, etype, w_self=w_self, bias=bias, reduce=reduce, etype_full=etype_full, val=val,
+                                    val_full=val_full, gathered=gathered, out=out, out_dtype=out_dtype, relu=relu, fused=fused)
+
     def attend(self, q, k, v=None, kind="dot", a=None, heads=1, scale=None, slope=0.2, bias=None, bias_full=False, edge=None, edge_full=False,
                gathered=False, out=None, out_dtype=None):
         """Edge attention on this block in ONE launch on torch's current stream (gnnagg_block_attn_run): no handle, no plan, no gathered
@@ -407,6 +423,128 @@ def block_rgcn_run(blk, x, w_rel, etype, w_self=None, bias=None, reduce="mean", 
                                       ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
                                       REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+# bases a lane of the basis kernel accumulates in one pass over a row, by the lane's width in columns (basis_chunk, agg_block_rgcn_basis.hip)
+RGCN_BASIS_CHUNK = {1: 16, 2: 16, 4: 16, 8: 8}
+
+
+def block_rgcn_basis_supported(feat, n_out, num_rel, num_bases, dtype):
+    """gnnagg_block_rgcn_basis_supported: does the fused kernel of Block.rgcn_basis serve [feat] -> [n_out] over num_rel relations and
+    num_bases bases with operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_rgcn_basis_supported(int(feat), int(n_out), int(num_rel), int(num_bases),
+                                                                                    FEATURE_DTYPES[dtype]))
+
+
+def rgcn_basis_prefers_fused(num_dst, feat, n_out, num_rel, num_bases, dtype):
+    """The fused=None rule of Block.rgcn_basis: the kernel where it is supported and Block.rgcn's kernel does NOT serve the materialised
+    [num_rel, feat, n_out] weights -- there it was 5 to 120 x faster than the per-relation composition at every measured shape.  Where
+    Block.rgcn's kernel fits (few relations), einsum + that kernel was as fast or faster at most shapes (up to 8 x at 30 bases: the basis
+    walk pays one pass per 16 bases) and is taken.  (profiles/block_rgcn_basis/rule_measurements.txt: the shapes measured and what each
+    arm took.)"""
+    return block_rgcn_basis_supported(feat, n_out, num_rel, num_bases, dtype) and not block_rgcn_supported(feat, n_out, num_rel, dtype)
+
+
+def block_rgcn_basis_run(blk, x, bases, comp, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False,
+                         gathered=False, out=None, out_dtype=None, relu=False, fused=None):
+    """Block.rgcn_basis as a function (the thin form over gnnagg_block_rgcn_basis_run); every dtype and shape refusal is raised before
+    device work"""
+    if reduce not in RGCN_REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (list(RGCN_REDUCE), reduce))
+    mapped = blk.src_nodes is not None and not gathered
+    for flag, name, t in ((etype_full, "etype", etype), (val_full, "val", val)):
+        if flag and blk.eid is None:
+            raise ValueError("%s_full=True reads %s through blk.eid: sample the block with return_eid=True" % (name, name))
+        if flag and t is None:
+            raise ValueError("%s_full=True needs %s" % (name, name))
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = blk.num_src if not mapped else 0
+    if w_self is not None and not mapped:
+        need_rows = max(need_rows, blk.num_dst)
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    if not isinstance(etype, torch.Tensor) or etype.dtype != torch.int32:
+        raise TypeError("etype must be a torch.int32 tensor, got %s" % (getattr(etype, "dtype", type(etype).__name__),))
+    if etype.dim() != 1 or (not etype_full and int(etype.numel()) != blk.num_edges):
+        raise ValueError("etype must be 1-D%s, got %s" % ("" if etype_full else " with one type per edge of the block: [%d]" % blk.num_edges,
+                                                           tuple(etype.shape)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    if not isinstance(bases, torch.Tensor) or bases.dtype != x.dtype:
+        raise TypeError("bases must be a tensor of x's dtype %s, got %s" % (x.dtype, getattr(bases, "dtype", type(bases).__name__)))
+    if bases.dim() != 3 or int(bases.shape[0]) < 1 or int(bases.shape[1]) != feat or int(bases.shape[2]) < 1:
+        raise ValueError("bases must be [B, %d, n_out] with B >= 1 and n_out >= 1, got %s" % (feat, tuple(bases.shape)))
+    num_bases, n_out = int(bases.shape[0]), int(bases.shape[2])
+    if not isinstance(comp, torch.Tensor) or comp.dtype != torch.float32:
+        raise TypeError("comp must be a torch.float32 tensor, got %s" % (getattr(comp, "dtype", type(comp).__name__),))
+    if comp.dim() != 2 or int(comp.shape[0]) < 1 or int(comp.shape[1]) != num_bases:
+        raise ValueError("comp must be [R, %d] with R >= 1, one column per basis, got %s" % (num_bases, tuple(comp.shape)))
+    num_rel = int(comp.shape[0])
+    if w_self is not None:
+        if not isinstance(w_self, torch.Tensor) or w_self.dtype != x.dtype:
+            raise TypeError("w_self must be a tensor of x's dtype %s, got %s" % (x.dtype, getattr(w_self, "dtype", type(w_self).__name__)))
+        if tuple(w_self.shape) != (feat, n_out):
+            raise ValueError("w_self must be [%d, %d], as a basis of bases, got %s" % (feat, n_out, tuple(w_self.shape)))
+    shape = (blk.num_dst, n_out)
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a torch.float32 tensor or None")
+        if tuple(bias.shape) != (n_out,):
+            raise ValueError("bias must be [%d], got %s" % (n_out, tuple(bias.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_rgcn_basis_supported(feat, n_out, num_rel, num_bases, x.dtype):
+        raise ValueError("fused=True: gnnagg_block_rgcn_basis_supported(feat=%d, n_out=%d, num_rel=%d, num_bases=%d, %s) says no" %
+                         (feat, n_out, num_rel, num_bases, x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full or etype_full else None
+    p_et, p_val = _dev_ptr(etype, torch.int32, "etype"), _dev_ptr(val, torch.float32, "val")
+    p_v, p_c = _dev_ptr(bases, x.dtype, "bases"), _dev_ptr(comp, torch.float32, "comp")
+    p_ws, p_b = _dev_ptr(w_self, x.dtype, "w_self"), _dev_ptr(bias, torch.float32, "bias")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("etype", etype), ("val", val), ("bases", bases), ("comp", comp), ("w_self", w_self), ("bias", bias),
+                    ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = rgcn_basis_prefers_fused(blk.num_dst, feat, n_out, num_rel, num_bases, x.dtype)
+    if not fused:   # the route a caller had before this call: materialise W_rel, then Block.rgcn with its own rule
+        w_rel = torch.einsum("rb,bfn->rfn", comp, bases.float()).to(x.dtype)
+        return block_rgcn_run(blk, x, w_rel, etype, w_self=w_self, bias=bias, reduce=reduce, etype_full=etype_full, val=val, val_full=val_full,
+                              gathered=gathered, out=out, out_dtype=out_dtype, relu=relu, fused=None)
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    has_e = blk.num_edges > 0
+    if not int(etype.numel()):   # (an empty tensor has a null pointer and the call wants an address: one element nobody reads)
+        p_et = _dev_ptr(torch.zeros(1, dtype=torch.int32, device=x.device), torch.int32, "etype")
+    check(lib().gnnagg_block_rgcn_basis_run(p_ptr, p_idx if has_e else None, blk.num_dst, p_src, p_et, p_eid if etype_full else None, p_val,
+                                            p_eid if val_full else None, px, xdt, pitch, feat, p_ws, p_v, p_c, num_rel, num_bases, p_b, n_out,
+                                            ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
+                                            REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
+                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

@@ -1073,6 +1073,41 @@ int gnnagg_block_rgcn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
 int gnnagg_block_rgcn_supported(int feat, int n_out, int num_rel, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_rgcn_grid_cap(int feat, int n_out, int num_rel, int x_dtype);
 
+/* Block R-GCN layer, basis decomposition: the layer above with W_rel[r] = sum_{b < num_bases} comp[r][b] V_b -- PyG's
+ * RGCNConv(num_bases = B), DGL's RelGraphConv(regularizer = "basis") -- on one sampled block in one launch
+ * (csrc/agg_block_rgcn_basis.hip).  The sum over relations moves in front of the matrix product:
+ *   out[i] = act( x_dst[i] . W_self + sum_{b < num_bases} g_b[i] . V_b + bias )
+ *   g_b[i] = sum_{p in row i, 0 <= t(p) < num_rel}  comp[t(p)][b] * s_p * x[s(p)]
+ *   s_p    = w(p)                                    GNNAGG_REDUCE_SUM
+ *   s_p    = w(p) / n(i, t(p))                       GNNAGG_REDUCE_MEAN, n(i, t) = the number of edges of type t in row i
+ * so the LDS of a launch holds num_bases + 1 slots per row whatever num_rel is (MUTAG, AIFB, BGS, AM: 46 to 266 relations).  No W_rel is
+ * materialised.  t(p), s(p), w(p), the skipped types, the self row, the types of the operands, bias, ReLU, determinism and the shape of
+ * the call are those of gnnagg_block_rgcn_run; what differs:
+ *   operands     d_bases: V [num_bases, feat, n_out] of x_dtype, row-major and dense; d_comp: fp32 [num_rel, num_bases], contiguous.
+ *   arithmetic   per edge p in increasing p, in fp32: s_p (mean: ONE IEEE division w(p) / (float) n); per basis c = comp[t(p)][b] * s_p
+ *                (ONE multiply); per column acc_b = fmaf(widen(x), c, acc_b), from acc_b = 0.  g_b is that chain: a (row, basis) without
+ *                edges is +0; with bf16 operands g_b is rounded to bf16 once, as a bf16 y store.  n(i, t) is counted with integer adds.
+ *   combine      ONE fp32 accumulator, k ascending over the self row and W_self, then over g_0 and V_0, ..., g_{B-1} and V_{B-1}; fp32
+ *                v_mfma_f32_16x16x4_f32, bf16 v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  With num_bases = num_rel, comp the
+ *                identity, GNNAGG_REDUCE_SUM and finite operands the bits are those of gnnagg_block_rgcn_run with W_rel = V.
+ *   bound        against float64 over the stored operands, with A = |x_dst| |W_self| + sum_b (sum_p |comp| |s_p| |x|) |V_b| + |bias|:
+ *                |out - out64| <= (gamma_n + 1e-5) A, gamma_n = n u / (1 - n u), u = 2^-24, n = the longest row + (B + 1) Fp + 4;
+ *                bf16 operands add 2^-9 (1 + gamma_n) A for the rounding of g_b, a bf16 out its one rounding.
+ *   range        gnnagg_block_rgcn_basis_supported(feat, n_out, num_rel, num_bases, x_dtype) is the one place the rule lives:
+ *                1 <= feat, n_out <= 256, num_rel >= 1, num_bases >= 1 and [16 ints][counts: 16 x num_rel ints][comp][tile: 16 rows of
+ *                num_bases + 1 slots][bf16: the image of the stacked weights] inside the 160 KB of LDS of a CU -- fp32 e.g. 128 -> 64
+ *                with 266 relations and 8 bases; bf16 64 -> 64 with 200 relations and 8 bases.  A launch holds at most
+ *                gnnagg_block_rgcn_basis_grid_cap workgroups (0 outside the range).
+ *   refusals     those of gnnagg_block_rgcn_run, and num_bases < 1, a null d_bases or d_comp with num_dst > 0.
+ * (tests/test_block_rgcn_basis_host.py, tests/test_gpu_block_rgcn_basis.py; DESIGN.md "Block R-GCN layer, basis decomposition") */
+int gnnagg_block_rgcn_basis_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const int *d_etype,
+                                const int *d_etype_eid, const float *d_val, const int *d_val_eid, const void *d_x, int x_dtype,
+                                long long x_pitch, int feat, const void *d_w_self, const void *d_bases, const float *d_comp, int num_rel,
+                                int num_bases, const float *d_bias, int n_out, void *d_out, int out_dtype, int reduce, int flags,
+                                void *hip_stream);
+int gnnagg_block_rgcn_basis_supported(int feat, int n_out, int num_rel, int num_bases, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_rgcn_basis_grid_cap(int feat, int n_out, int num_rel, int num_bases, int x_dtype);
+
 /* Block attention: scaled dot-product (gnnagg_dot_attn_run) or GATv2 (gnnagg_gatv2_run) attention on one sampled block in one launch
  * (csrc/agg_block_attn.hip), with the operands read where they live --
  *   s(p) = d_src_nodes ? d_src_nodes[d_blk_idx[p]] : d_blk_idx[p]      the source row of block edge p
