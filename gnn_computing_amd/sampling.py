@@ -62,6 +62,23 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         return block_sage_run(self, x, w_neigh, w_self=w_self, bias=bias, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                               out_dtype=out_dtype, relu=relu, fused=fused)
 
+    def gin(self, x, w1, w2, b1=None, b2=None, eps=0.0, reduce="sum", val=None, val_full=False, gathered=False, out=None, out_dtype=None,
+            relu=False, fused=None):
+        """A GIN layer on this block -- GINConv with a two-layer MLP --
+        out = act(relu(((1 + eps) * x_dst + aggregate(x)) @ w1 + b1) @ w2 + b2) in ONE launch on torch's current stream
+        (gnnagg_block_gin_run): neither the aggregate nor the hidden activations are stored, x_dst is never copied.  x, reduce ("sum",
+        "mean" or "max"), val, val_full, gathered, out, out_dtype: as in sage().
+          w1, w2       contiguous [F, hidden] and [hidden, n_out] tensors of x's dtype
+          b1, b2       None or float32 [hidden] / [n_out]
+          eps          the layer's epsilon; the kernel is given float32(1 + eps)
+          relu         the activation of out; the hidden ReLU is always applied
+          fused        True: the kernel, ValueError where gnnagg_block_gin_supported says no.  False: the composition of existing calls
+                       (aggregate, a product and a sum, matmul_NN, bias, ReLU, matmul_NN, bias, ReLU) -- for float32 the same bits.
+                       None: the kernel where it is supported and was not measured slower (gin_prefers_fused).
+        Returns out."""
+        return block_gin_run(self, x, w1, w2, b1=b1, b2=b2, eps=eps, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
+                             out_dtype=out_dtype, relu=relu, fused=fused)
+
     def rgcn(self, x, w_rel, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False, gathered=False, out=None,
              out_dtype=None, relu=False, fused=None):
         """A relational (typed-edge) GCN layer on this block -- RGCNConv / RelGraphConv without a weight decomposition --
@@ -285,6 +302,119 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
                                       p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
                                       REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def block_gin_supported(feat, hidden, n_out, dtype):
+    """gnnagg_block_gin_supported: does the fused kernel of Block.gin serve [feat] -> [hidden] -> [n_out] with operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_gin_supported(int(feat), int(hidden), int(n_out), FEATURE_DTYPES[dtype]))
+
+
+def gin_prefers_fused(num_dst, feat, hidden, n_out, dtype):
+    """The fused=None rule of Block.gin: the kernel wherever it is supported.  (profiles/block_gin/rule_measurements.txt: the shapes
+    measured and what each arm took.)"""
+    return block_gin_supported(feat, hidden, n_out, dtype)
+
+
+def block_gin_run(blk, x, w1, w2, b1=None, b2=None, eps=0.0, reduce="sum", val=None, val_full=False, gathered=False, out=None, out_dtype=None,
+                  relu=False, fused=None):
+    """Block.gin as a function (the thin form over gnnagg_block_gin_run); every dtype and shape refusal is raised before device work"""
+    if reduce not in REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (sorted(REDUCE), reduce))
+    mapped = blk.src_nodes is not None and not gathered
+    if val_full and blk.eid is None:
+        raise ValueError("val_full=True reads val through blk.eid: sample the block with return_eid=True")
+    if val_full and val is None:
+        raise ValueError("val_full=True needs val")
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    with np.errstate(over="ignore"):
+        self_scale = float(np.float32(1.0 + eps))
+    if not math.isfinite(self_scale):
+        raise ValueError("eps = %r: 1 + eps must be a finite float32" % (eps,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = max(blk.num_src, blk.num_dst) if not mapped else 0
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    for name, w in (("w1", w1), ("w2", w2)):
+        if not isinstance(w, torch.Tensor) or w.dtype != x.dtype:
+            raise TypeError("%s must be a tensor of x's dtype %s, got %s" % (name, x.dtype, getattr(w, "dtype", type(w).__name__)))
+    if w1.dim() != 2 or int(w1.shape[0]) != feat or int(w1.shape[1]) < 1:
+        raise ValueError("w1 must be [%d, hidden] with hidden >= 1, got %s" % (feat, tuple(w1.shape)))
+    hidden = int(w1.shape[1])
+    if w2.dim() != 2 or int(w2.shape[0]) != hidden or int(w2.shape[1]) < 1:
+        raise ValueError("w2 must be [%d, n_out] with n_out >= 1, got %s" % (hidden, tuple(w2.shape)))
+    n_out = int(w2.shape[1])
+    shape = (blk.num_dst, n_out)
+    for name, b, n in (("b1", b1, hidden), ("b2", b2, n_out)):
+        if b is None:
+            continue
+        if not isinstance(b, torch.Tensor) or b.dtype != torch.float32:
+            raise TypeError("%s must be a torch.float32 tensor or None" % name)
+        if tuple(b.shape) != (n,):
+            raise ValueError("%s must be [%d], got %s" % (name, n, tuple(b.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_gin_supported(feat, hidden, n_out, x.dtype):
+        raise ValueError("fused=True: gnnagg_block_gin_supported(feat=%d, hidden=%d, n_out=%d, %s) says no" % (feat, hidden, n_out, x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full else None
+    p_val = _dev_ptr(val, torch.float32, "val")
+    p_w1, p_w2 = _dev_ptr(w1, x.dtype, "w1"), _dev_ptr(w2, x.dtype, "w2")
+    p_b1, p_b2 = _dev_ptr(b1, torch.float32, "b1"), _dev_ptr(b2, torch.float32, "b2")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("val", val), ("w1", w1), ("w2", w2), ("b1", b1), ("b2", b2), ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = gin_prefers_fused(blk.num_dst, feat, hidden, n_out, x.dtype)
+    if not fused:   # the composition a caller writes with the existing calls
+        if mapped:
+            y, x_dst = block_gcn_run(blk, x, reduce=reduce, val=val, val_full=val_full, return_dst=True)
+        else:
+            y, x_dst = block_gcn_run(blk, x, reduce=reduce, val=val, val_full=val_full, gathered=gathered), x[:blk.num_dst]
+        h = y + x_dst * self_scale      # a product, then a sum, each rounded to x's dtype (not add(alpha=): that is one fma)
+        z = matmul_NN(h, w1, out_dtype=torch.float32)
+        if b1 is not None:
+            z = z + b1
+        z = z.clamp_min(0).to(x.dtype)
+        res = matmul_NN(z, w2, out_dtype=torch.float32)
+        if b2 is not None:
+            res = res + b2
+        if relu:
+            res = res.clamp_min(0)
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    check(lib().gnnagg_block_gin_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, self_scale,
+                                     p_w1, p_b1, hidden, p_w2, p_b2, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None,
+                                     FEATURE_DTYPES[out.dtype], REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

@@ -1030,6 +1030,55 @@ int gnnagg_block_sage_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
 int gnnagg_block_sage_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_sage_grid_cap(int feat, int n_out, int x_dtype);
 
+/* Block GIN layer: PyG's GINConv(nn = Sequential(Linear, ReLU, Linear), eps) / DGL's GINConv(apply_func = MLP, aggregator_type = sum |
+ * mean | max) on one sampled block in one launch (csrc/agg_block_gin.hip) --
+ *   h[i]   = self_scale * x_dst[i] + aggr_{p in row i}(val_p * x_src(p))       [feat]
+ *   z[i]   = relu( h[i] . W1 + b1 )                                            [hidden]
+ *   out[i] = act( z[i] . W2 + b2 )                                             [n_out]
+ * with no y, no h and no z in memory, no copy of x_dst and no GEMM launch: both products run per tile of 16 rows, z held in LDS.
+ *   aggregation  a[i][0..feat) is the fp32 row gnnagg_block_gcn_run forms for the same (blk, src_nodes, val, eid, x, reduce) before its
+ *                store: the same chain in CSR order, the same mean division, 0 for a row without edges.
+ *   self row     s[i] = x[d_src_nodes ? d_src_nodes[i] : i]; self_scale = 1 + eps is formed by the caller and must be finite.
+ *   h            h = fadd(a, fmul(self_scale, s)) in fp32: TWO roundings, never contracted into one fma -- for fp32 operands the bits of
+ *                y + x_dst * self_scale with y of gnnagg_block_gcn_run.  With bf16 operands h is then rounded to bf16 ONCE (a itself is
+ *                not rounded first).
+ *   hidden       z[i][m] = relu( sum_k h[i][k] W1[k][m] (k ascending, one fp32 accumulator) + b1[m] ), always with the ReLU; with bf16
+ *                operands z is rounded to bf16 ONCE, after the ReLU.  d_b1 NULL adds nothing.
+ *   out          out[i][n] = act( sum_k z[i][k] W2[k][n] (k ascending, one fp32 accumulator) + b2[n] ); GNNAGG_FLAG_RELU is the activation
+ *                of out and the only flag; d_b2 NULL adds nothing.  A bf16 out is rounded ONCE at the store.  ReLU as GNNAGG_FLAG_RELU
+ *                everywhere: a NaN stays a NaN.
+ *   types        x, W1 and W2 share x_dtype (GNNAGG_DTYPE_F32 or GNNAGG_DTYPE_BF16); b1 [hidden] and b2 [n_out] are fp32; W1 is
+ *                [feat, hidden], W2 [hidden, n_out], row-major and dense; out is dense [num_dst, n_out]: fp32 for fp32 operands, fp32 or
+ *                bf16 for bf16 operands.  out aliases no input.  d_x rows are x_pitch ELEMENTS apart.
+ *   fp32         both accumulators are the ascending-k fmaf chain on v_mfma_f32_16x16x4_f32 of gnnagg_matmul_nn: out equals, bit for bit,
+ *                act(matmul_nn(relu(matmul_nn(y + x_dst * self_scale, W1) + b1), W2) + b2).
+ *   bf16         both products run on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  Against float64 over the stored operands, with
+ *                A_h = |self_scale| |x_dst| + sum_p |s_p| |x_src(p)|, A_1 = A_h |W1| + |b1|, A_2 = A_1 |W2| + |b2|, u = 2^-24, u16 = 2^-8:
+ *                |out - out64| <= ((1 + gamma_n)(1 + u16)^2 - 1 + 1e-5) A_2, gamma_n = n u / (1 - n u), n = the longest row + Fp + Hp + 8
+ *                (Fp, Hp: feat, hidden rounded up to 32); a bf16 out adds its one rounding.
+ *   determinism  the bits depend on the arguments only, never on alignment, pitch or lane geometry.  No atomics.
+ *   non-finite   +-Inf / NaN reach exactly the rows of out that hold them as a neighbour or as their self row.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_dst = 0 is a valid call that launches nothing.  Rows of any length are walked by one lane group, as in
+ *                gnnagg_block_gcn_run.  Workgroups walk tiles of 16 rows; a launch holds at most gnnagg_block_gin_grid_cap workgroups.
+ *   range        gnnagg_block_gin_supported(feat, hidden, n_out, x_dtype) is the one place the rule lives: 1 <= feat, hidden, n_out <= 256
+ *                and [2 x 16 ints][h tile: 16 rows][z tile: 16 rows][bf16: the images of W1 and W2] inside the 160 KB of LDS of a CU --
+ *                every fp32 shape up to 256 -> 256 -> 256 (33 KB); bf16 e.g. 128 -> 128 -> 128 (77 KB), 256 -> 128 -> 64, not
+ *                256 -> 256 -> 64.  gnnagg_block_gin_grid_cap: the workgroups a launch of that shape is capped at on the current device,
+ *                0 outside the range.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; feat < 1; hidden < 1; n_out < 1;
+ *                x_pitch < feat; an unknown x_dtype, out_dtype or reduce; fp32 operands with a bf16 out; any flag but GNNAGG_FLAG_RELU; a
+ *                self_scale that is not finite; d_eid without d_val; a shape outside the supported range; a null d_blk_ptr, d_x, d_w1,
+ *                d_w2 or d_out with num_dst > 0.
+ * (tests/test_block_gin_host.py, tests/test_gpu_block_gin.py; DESIGN.md "Block GIN layer") */
+int gnnagg_block_gin_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const float *d_val,
+                         const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, int feat,
+                         float self_scale,                      /* 1 + eps, formed by the caller */
+                         const void *d_w1, const float *d_b1, int hidden, const void *d_w2, const float *d_b2, int n_out,
+                         void *d_out, int out_dtype, int reduce, int flags, void *hip_stream);
+int gnnagg_block_gin_supported(int feat, int hidden, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_gin_grid_cap(int feat, int hidden, int n_out, int x_dtype);
+
 /* Block R-GCN layer: a relational (typed-edge) GCN layer -- PyG's RGCNConv, DGL's RelGraphConv without a weight decomposition -- on one
  * sampled block in one launch (csrc/agg_block_rgcn.hip).  With num_rel relations,
  *   out[i] = act( x_dst[i] . W_self + sum_{r < num_rel} aggr_{p in row i, t(p) == r}( w(p) x[s(p)] ) . W_rel[r] + bias )
