@@ -16,6 +16,7 @@ from .sampling import (  # noqa: F401
     block_rgcn_run, block_rgcn_supported, rgcn_prefers_fused,
     block_rgcn_basis_run, block_rgcn_basis_supported, rgcn_basis_prefers_fused,
     block_gin_run, block_gin_supported, gin_prefers_fused,
+    block_pna_run, block_pna_supported, pna_prefers_fused,
 )
 from . import graph  # noqa: F401
 from . import probe  # noqa: F401

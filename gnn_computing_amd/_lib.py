@@ -159,6 +159,10 @@ SIGNATURES = {
                                      c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_block_gin_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "gnnagg_block_gin_grid_cap": (c_int, [c_int, c_int, c_int, c_int]),
+    "gnnagg_block_pna_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int,
+                                     c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "gnnagg_block_pna_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "gnnagg_block_pna_grid_cap": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "gnnagg_block_rgcn_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                       ctypes.c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                       c_void_p]),

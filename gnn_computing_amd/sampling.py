@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .aggregator import (FEATURE_DTYPES, REDUCE, Aggregator_GAT, Aggregator_GCN, _bias_heads, _dev_ptr, _dev_ptr_rows, _edge_rows, _feat_dtype,
+from .aggregator import (AGGRS, FEATURE_DTYPES, REDUCE, SCALERS, Aggregator_GAT, Aggregator_GCN, _bias_heads, _dev_ptr, _dev_ptr_rows, _edge_rows, _feat_dtype,
                          matmul_NN)
 
 _U64 = (1 << 64) - 1
@@ -78,6 +78,23 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         Returns out."""
         return block_gin_run(self, x, w1, w2, b1=b1, b2=b2, eps=eps, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                              out_dtype=out_dtype, relu=relu, fused=fused)
+
+    def pna(self, x, w, w_self=None, bias=None, aggrs=("mean", "min", "max", "std"), scalers=("identity",), delta=None, val=None, val_full=False,
+            gathered=False, out=None, out_dtype=None, relu=False, fused=None):
+        """A PNA layer on this block -- PNAConv / MultiAggregation with a linear post-transform and a self term --
+        out = act(cat([x_dst, M], 1) @ cat([w_self, w], 0) + bias) in ONE launch on torch's current stream (gnnagg_block_pna_run), with
+        M [num_dst, S * A * F] what self.gcn(val).run_multi(x_src, M, aggrs, scalers, delta) gives: M is never stored, x_dst never copied.
+        x, val, val_full, gathered, bias, out, out_dtype, relu: as in sage().
+          aggrs, scalers   names as in run_multi ("sum", "mean", "min", "max", "var", "std"; "identity", "amplification", "attenuation"),
+                           distinct, in any order: the blocks of M (and the row slabs of w) lie scaler-major in the order of the library's bits
+          delta            pna_delta(ptr) of the training graph; needed by the two non-identity scalers
+          w, w_self        contiguous [S * A * F, n_out] and (or None: no self term) [F, n_out] tensors of x's dtype
+          fused            True: the kernel, ValueError where gnnagg_block_pna_supported says no.  False: the composition of existing calls
+                           (the gather, gcn(val).run_multi, cat, matmul_NN, bias, ReLU) -- for float32 the same bits on rows of at most
+                           128 edges.  None: the kernel where it is supported and was not measured slower (pna_prefers_fused).
+        Returns out."""
+        return block_pna_run(self, x, w, w_self=w_self, bias=bias, aggrs=aggrs, scalers=scalers, delta=delta, val=val, val_full=val_full,
+                             gathered=gathered, out=out, out_dtype=out_dtype, relu=relu, fused=fused)
 
     def rgcn(self, x, w_rel, etype, w_self=None, bias=None, reduce="mean", etype_full=False, val=None, val_full=False, gathered=False, out=None,
              out_dtype=None, relu=False, fused=None):
@@ -415,6 +432,128 @@ def block_gin_run(blk, x, w1, w2, b1=None, b2=None, eps=0.0, reduce="sum", val=N
                                      p_w1, p_b1, hidden, p_w2, p_b2, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None,
                                      FEATURE_DTYPES[out.dtype], REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def block_pna_supported(feat, n_out, n_aggr, n_scaler, dtype):
+    """gnnagg_block_pna_supported: does the fused kernel of Block.pna serve [feat] -> [n_out] with n_aggr aggregates x n_scaler scalers and
+    operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_pna_supported(int(feat), int(n_out), int(n_aggr), int(n_scaler),
+                                                                             FEATURE_DTYPES[dtype]))
+
+
+def pna_prefers_fused(num_dst, feat, n_out, n_aggr, n_scaler, dtype):
+    """The fused=None rule of Block.pna: the kernel wherever it is supported.  (profiles/block_pna/rule_measurements.txt: the shapes
+    measured and what each arm took.)"""
+    return block_pna_supported(feat, n_out, n_aggr, n_scaler, dtype)
+
+
+def block_pna_run(blk, x, w, w_self=None, bias=None, aggrs=("mean", "min", "max", "std"), scalers=("identity",), delta=None, val=None,
+                  val_full=False, gathered=False, out=None, out_dtype=None, relu=False, fused=None):
+    """Block.pna as a function (the thin form over gnnagg_block_pna_run); every dtype and shape refusal is raised before device work"""
+    aggrs = (aggrs,) if isinstance(aggrs, str) else tuple(aggrs)
+    scalers = (scalers,) if isinstance(scalers, str) else tuple(scalers)
+    for names, table, what in ((aggrs, AGGRS, "aggrs"), (scalers, SCALERS, "scalers")):   # run_multi's validation and mask order
+        if [n for n in names if n not in table] or not names or len(set(names)) != len(names):
+            raise ValueError("%s must be distinct names of %s, got %r" % (what, sorted(table, key=table.get), names))
+    amask, smask = sum(AGGRS[n] for n in aggrs), sum(SCALERS[n] for n in scalers)
+    if smask != _lib.SCALER_IDENTITY:
+        if delta is None:
+            raise ValueError("the amplification and attenuation scalers need delta (pna_delta(ptr))")
+        if not (math.isfinite(float(delta)) and float(delta) > 0.0):
+            raise ValueError("delta = %r must be finite and > 0" % (delta,))
+    mapped = blk.src_nodes is not None and not gathered
+    if val_full and blk.eid is None:
+        raise ValueError("val_full=True reads val through blk.eid: sample the block with return_eid=True")
+    if val_full and val is None:
+        raise ValueError("val_full=True needs val")
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = blk.num_src if not mapped else 0
+    if w_self is not None and not mapped:
+        need_rows = max(need_rows, blk.num_dst)
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    if val is not None:
+        if not isinstance(val, torch.Tensor) or val.dtype != torch.float32:
+            raise TypeError("val must be a torch.float32 tensor or None")
+        if val.dim() != 1 or (not val_full and int(val.numel()) != blk.num_edges):
+            raise ValueError("val must be 1-D%s, got %s" % ("" if val_full else " with one value per edge of the block: [%d]" % blk.num_edges,
+                                                             tuple(val.shape)))
+    k_m = len(scalers) * len(aggrs) * feat
+    for name, t, rows in (("w", w, k_m), ("w_self", w_self, feat)):
+        if t is None and name == "w_self":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != x.dtype:
+            raise TypeError("%s must be a tensor of x's dtype %s, got %s" % (name, x.dtype, getattr(t, "dtype", type(t).__name__)))
+        if t.dim() != 2 or int(t.shape[0]) != rows or int(t.shape[1]) < 1 or t.shape[1] != w.shape[1]:
+            raise ValueError("%s must be [%s = %d, n_out] with n_out >= 1%s, got %s" % (name, "S * A * F" if t is w else "F", rows,
+                                                                                      "" if t is w else " as w's", tuple(t.shape)))
+    n_out = int(w.shape[1])
+    shape = (blk.num_dst, n_out)
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a torch.float32 tensor or None")
+        if tuple(bias.shape) != (n_out,):
+            raise ValueError("bias must be [%d], got %s" % (n_out, tuple(bias.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_pna_supported(feat, n_out, len(aggrs), len(scalers), x.dtype):
+        raise ValueError("fused=True: gnnagg_block_pna_supported(feat=%d, n_out=%d, n_aggr=%d, n_scaler=%d, %s) says no"
+                         % (feat, n_out, len(aggrs), len(scalers), x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_eid = _dev_ptr(blk.eid, torch.int32, "blk.eid") if val_full else None
+    p_val = _dev_ptr(val, torch.float32, "val")
+    p_w, p_ws, p_b = _dev_ptr(w, x.dtype, "w"), _dev_ptr(w_self, x.dtype, "w_self"), _dev_ptr(bias, torch.float32, "bias")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("val", val), ("w", w), ("w_self", w_self), ("bias", bias), ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = pna_prefers_fused(blk.num_dst, feat, n_out, len(aggrs), len(scalers), x.dtype)
+    if not fused:   # the composition a caller writes with the existing calls
+        x_src = x[blk.src_nodes.long()] if mapped else x.contiguous()
+        m = torch.empty((blk.num_dst, k_m), dtype=x.dtype, device=x.device)
+        h = blk.gcn(val[blk.eid.long()] if val_full else val)
+        try:
+            h.run_multi(x_src, m, aggrs=aggrs, scalers=scalers, delta=delta)
+        finally:
+            h.close()
+        if w_self is not None:
+            res = matmul_NN(torch.cat([x_src[:blk.num_dst], m], 1), torch.cat([w_self, w], 0), out_dtype=torch.float32)
+        else:
+            res = matmul_NN(m, w, out_dtype=torch.float32)
+        if bias is not None:
+            res = res + bias
+        if relu:
+            res = res.clamp_min(0)
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    check(lib().gnnagg_block_pna_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, amask, smask,
+                                     ctypes.c_float(1.0 if delta is None else float(delta)), p_ws, p_w, p_b, n_out,
+                                     ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
+                                     _lib.FLAG_RELU if relu else 0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

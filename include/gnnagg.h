@@ -1079,6 +1079,61 @@ int gnnagg_block_gin_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst
 int gnnagg_block_gin_supported(int feat, int hidden, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_gin_grid_cap(int feat, int hidden, int n_out, int x_dtype);
 
+/* Block PNA layer: PyG's PNAConv / MultiAggregation with a linear post-transform and a self term -- DGL's PNAConv with one tower -- on one
+ * sampled block in one launch (csrc/agg_block_pna.hip).  With A = popcount(aggr_mask) aggregates and S = popcount(scaler_mask) scalers,
+ *   out[i] = act( cat[x_dst[i], M[i]] . cat[W_self; W] + bias ),   M [num_dst, S * A * feat]
+ * with no M in memory, no copy of x_dst, no concatenation and no GEMM launch.
+ *   messages     m_p = w(p) * x[s(p)] in fp32 (ONE multiply; widen(x) for bf16), s(p) and w(p) as in gnnagg_block_gcn_run (w = 1.0f
+ *                without d_val).
+ *   per row      M[i] is exactly what gnnagg_gcn_run_multi defines on the block's CSR over x[src_nodes]: S1 the plain add chain in CSR
+ *                order, S2 = fmaf(m, m, S2), min / max skipping NaN; sum = S1, mean = S1 / d, var = max(S2 / d - mean^2, 0) (a NaN
+ *                kept), std = sqrtf(var), min / max of NaN messages alone NaN; a row without edges is +0 in every block.  The scalers,
+ *                one fp32 scalar per row: identity, amplification logf(d + 1) / delta, attenuation delta / logf(d + 1); a row without
+ *                edges is multiplied by 0, never by delta / logf(1).
+ *   layout of W  [S * A * feat, n_out], row-major and dense: the slab of scaler s_pos and aggregate a_pos starts at row
+ *                (s_pos * A + a_pos) * feat, positions counted over the SET bits of the masks in ascending bit order (scaler-major: the
+ *                column order of gnnagg_gcn_run_multi's y).  W_self is [feat, n_out] or NULL (no self term).
+ *   order / bits ONE fp32 accumulator per element of out, k ascending over the self row and W_self, then over M and W; + bias[n] (d_bias
+ *                NULL adds nothing); ReLU with GNNAGG_FLAG_RELU, the only flag: a NaN stays a NaN.
+ *   types        x, W_self and W share x_dtype (GNNAGG_DTYPE_F32 or GNNAGG_DTYPE_BF16); bias is fp32; out is dense [num_dst, n_out]: fp32
+ *                for fp32 operands, fp32 or bf16 for bf16 operands (one round-to-nearest-even at the store).  out aliases no input.
+ *                d_x rows are x_pitch ELEMENTS apart.
+ *   fp32         v_mfma_f32_16x16x4_f32; the A operand of slab (s, a) is the unscaled aggregate times the row's scalar -- the one multiply
+ *                gnnagg_gcn_run_multi performs before its store -- so for rows of at most 128 edges out equals, bit for bit,
+ *                act(matmul_nn(cat[x_dst, M], cat[W_self; W]) + bias) with M of gnnagg_gcn_run_multi.  A longer row is walked by one lane
+ *                group here where the handle folds chunks: the same value inside gnnagg_gcn_run_multi's error bound.
+ *   error, bf16  the UNSCALED aggregates are rounded to bf16 once and multiplied on v_mfma_f32_16x16x32_bf16 with one fp32 accumulator
+ *                per scaler; the scalers are applied to the accumulators in fp32 and never rounded to bf16.  Against float64 over the
+ *                stored operands, with e_a the bound of gnnagg_gcn_run_multi for aggregate a (sum 1e-5 sum|m|, mean that / d, var
+ *                4e-5 S2 / d, std the square root of var's, min / max 0), u16 = 2^-8, T = |x_dst| |W_self| + sum_{s,a} scaler_s |a|
+ *                |W_{s,a}| and E = sum_{s,a} scaler_s (e_a + u16 (|a| + e_a)) |W_{s,a}|:
+ *                |out - out64| <= E + (gamma_n + 1e-5) (T + E), gamma_n = n u / (1 - n u), u = 2^-24, n = (1 + S A) Fp + 8, Fp = feat
+ *                rounded up to 32; a bf16 out adds its one rounding.
+ *   non-finite   +-Inf / NaN reach exactly the rows of out that hold them as a neighbour or as their self row.
+ *   determinism  the bits depend on the arguments only, never on alignment, pitch or lane geometry.  No atomics.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_dst = 0 is a valid call that launches nothing.  Rows of any length are walked by one lane group, as in
+ *                gnnagg_block_gcn_run.  Workgroups walk tiles of 16 rows; a launch holds at most gnnagg_block_pna_grid_cap workgroups.
+ *   range        gnnagg_block_pna_supported(feat, n_out, n_aggr = A, n_scaler = S, x_dtype) is the one place the rule lives:
+ *                1 <= feat, n_out <= 256, 1 <= A <= 6, 1 <= S <= 3 and [16 ints][16 x 2 floats][tile: 16 rows of 1 + A slots][bf16: the
+ *                image of all 1 + S A weight slabs] inside the 160 KB of LDS of a CU -- every fp32 shape (256 columns x 6 aggregates:
+ *                115 136 bytes); bf16 e.g. 128 -> 64 with 4 x 1 (103 872 bytes) and 64 -> 64 with 4 x 3 (118 208), not 128 -> 64 with
+ *                4 x 3.  gnnagg_block_pna_grid_cap: the workgroups a launch of that shape is capped at on the current device, 0 outside
+ *                the range.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; feat < 1; n_out < 1; x_pitch < feat;
+ *                an unknown x_dtype or out_dtype; fp32 operands with a bf16 out; an aggr_mask or scaler_mask that is 0 or holds unknown
+ *                bits; a non-identity scaler with a delta that is not finite or <= 0; any flag but GNNAGG_FLAG_RELU; d_eid without d_val;
+ *                a shape outside the supported range; a null d_blk_ptr, d_x, d_w or d_out with num_dst > 0.
+ * (tests/test_block_pna_host.py, tests/test_gpu_block_pna.py; DESIGN.md "Block PNA layer") */
+int gnnagg_block_pna_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const float *d_val,
+                         const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, int feat,
+                         int aggr_mask,                         /* GNNAGG_AGGR_* bits */
+                         int scaler_mask, float delta,          /* GNNAGG_SCALER_* bits; delta: read by the non-identity scalers only */
+                         const void *d_w_self, const void *d_w, const float *d_bias, int n_out, void *d_out, int out_dtype, int flags,
+                         void *hip_stream);
+int gnnagg_block_pna_supported(int feat, int n_out, int n_aggr, int n_scaler, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_pna_grid_cap(int feat, int n_out, int n_aggr, int n_scaler, int x_dtype);
+
 /* Block R-GCN layer: a relational (typed-edge) GCN layer -- PyG's RGCNConv, DGL's RelGraphConv without a weight decomposition -- on one
  * sampled block in one launch (csrc/agg_block_rgcn.hip).  With num_rel relations,
  *   out[i] = act( x_dst[i] . W_self + sum_{r < num_rel} aggr_{p in row i, t(p) == r}( w(p) x[s(p)] ) . W_rel[r] + bias )
