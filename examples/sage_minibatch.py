@@ -2,7 +2,7 @@
 """Mini-batch GraphSAGE forward (2 layers, mean aggregation) over sampled blocks: sample on the device (gnc.NeighborSampler), gather the
 input rows, and per layer h_dst' = relu(h_dst . W_self + mean_{kept neighbours}(h_src) . W_neigh) with the library's aggregation and GEMM.
 
-    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted] [--block-run] [--fused-layer]
+    python examples/sage_minibatch.py [--dataset arxiv] [--batch 1024] [--fanouts 15,10] [--batches 20] [--weighted] [--block-run] [--fused-layer] [--feat 128]
 
 --weighted draws the neighbours in proportion to a per-edge weight (NeighborSampler(prob=); a third of the edges have weight 0 and are never
 drawn) and aggregates the weighted sum with the kept edges' own weights, full_val[blk.eid].
@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--weighted", action="store_true", help="sample by a per-edge weight and aggregate with it")
     ap.add_argument("--block-run", action="store_true", help="aggregate each block with one Block.aggregate call: no handle, no gather")
     ap.add_argument("--fused-layer", action="store_true", help="run each layer as one Block.sage call (implies --block-run)")
+    ap.add_argument("--feat", type=int, default=DIMS[0], help="input features (past 256 Block.sage picks the chunked kernel or the composition)")
     args = ap.parse_args()
     args.block_run = args.block_run or args.fused_layer
     fanouts = tuple(int(f) for f in args.fanouts.split(","))
@@ -50,9 +51,10 @@ def main():
     ptrs, idxs = gnc.graph.dataset(args.dataset, device=dev)
     num_v = ptrs.numel() - 1
     gen = torch.Generator().manual_seed(123)
-    x = torch.randn(num_v, DIMS[0], generator=gen).to(dev)
-    w_self = [(torch.randn(DIMS[k], DIMS[k + 1], generator=gen) / DIMS[k] ** 0.5).to(dev) for k in range(2)]
-    w_neigh = [(torch.randn(DIMS[k], DIMS[k + 1], generator=gen) / DIMS[k] ** 0.5).to(dev) for k in range(2)]
+    dims = [args.feat] + DIMS[1:]
+    x = torch.randn(num_v, dims[0], generator=gen).to(dev)
+    w_self = [(torch.randn(dims[k], dims[k + 1], generator=gen) / dims[k] ** 0.5).to(dev) for k in range(2)]
+    w_neigh = [(torch.randn(dims[k], dims[k + 1], generator=gen) / dims[k] ** 0.5).to(dev) for k in range(2)]
     full_val = None
     if args.weighted:
         full_val = torch.exp2(12.0 * torch.rand(idxs.numel(), generator=gen) - 6.0)
@@ -86,7 +88,8 @@ def main():
         for k, blk in enumerate(blocks):
             if args.fused_layer:
                 kw = {"val": full_val, "val_full": True} if args.weighted else {}
-                h, dt = timed(lambda: blk.sage(h, w_neigh[k], w_self[k], reduce=reduce, relu=True, gathered=k > 0, fused=True, **kw))
+                one = True if gnc.block_sage_supported(h.shape[1], w_neigh[k].shape[1], h.dtype) else "wide"   # one launch either way
+                h, dt = timed(lambda: blk.sage(h, w_neigh[k], w_self[k], reduce=reduce, relu=True, gathered=k > 0, fused=one, **kw))
                 t_layer += dt
                 continue
 

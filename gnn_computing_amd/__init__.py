@@ -13,6 +13,7 @@ from .aggregator import (  # noqa: F401
 )
 from .sampling import (  # noqa: F401
     Block, NeighborSampler, block_attn_run, block_gcn_run, block_sage_run, block_sage_supported, sage_prefers_fused, sample_block_host,
+    block_sage_wide_supported, sage_prefers_wide,
     block_rgcn_run, block_rgcn_supported, rgcn_prefers_fused,
     block_rgcn_basis_run, block_rgcn_basis_supported, rgcn_basis_prefers_fused,
     block_gin_run, block_gin_supported, gin_prefers_fused,

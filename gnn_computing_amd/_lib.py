@@ -155,6 +155,11 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_block_sage_supported": (c_int, [c_int, c_int, c_int]),
     "gnnagg_block_sage_grid_cap": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_block_sage_wide_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_block_sage_wide_supported": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_block_sage_wide_grid_cap": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_block_sage_wide_chunk": (c_int, [c_int]),
     "gnnagg_block_gin_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int,
                                      c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_block_gin_supported": (c_int, [c_int, c_int, c_int, c_int]),

@@ -55,9 +55,12 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
           bias              None or float32 [n_out]
           out               None or a contiguous [num_dst, n_out] tensor: float32 for a float32 x, float32 or bfloat16 for a bfloat16 x;
                             out_dtype: the type of the out allocated here (x's by default)
-          fused             True: the kernel, ValueError where gnnagg_block_sage_supported says no.  False: the composition of existing
-                            calls (aggregate, cat, matmul_NN, bias, ReLU) -- for float32 the same bits.  None: the kernel where it is
-                            supported and was not measured slower (sage_prefers_fused).
+          fused             True: the kernel, ValueError where gnnagg_block_sage_supported says no (F, n_out <= 256).  "wide": the chunked
+                            kernel for rows up to 4096 features (gnnagg_block_sage_wide_run), ValueError where
+                            gnnagg_block_sage_wide_supported says no.  False: the composition of existing calls (aggregate, cat,
+                            matmul_NN, bias, ReLU) -- for float32 the same bits as either kernel.  None: the kernel where it is
+                            supported (sage_prefers_fused), else the chunked kernel where it was measured faster than the
+                            composition (sage_prefers_wide), else the composition.
         Returns out."""
         return block_sage_run(self, x, w_neigh, w_self=w_self, bias=bias, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                               out_dtype=out_dtype, relu=relu, fused=fused)
@@ -230,6 +233,25 @@ def sage_prefers_fused(num_dst, feat, n_out, dtype):
     return block_sage_supported(feat, n_out, dtype)
 
 
+def block_sage_wide_supported(feat, n_out, dtype):
+    """gnnagg_block_sage_wide_supported: does the chunked kernel of Block.sage (fused="wide") serve [feat] -> [n_out] with operands of `dtype`?"""
+    return dtype in FEATURE_DTYPES and bool(lib().gnnagg_block_sage_wide_supported(int(feat), int(n_out), FEATURE_DTYPES[dtype]))
+
+
+def sage_prefers_wide(num_dst, feat, n_out, dtype):
+    """The fused=None rule of Block.sage past the range of the narrow kernel: the chunked kernel only for shape classes where its slowest
+    round beat the composition's fastest round (profiles/block_sage_wide/rule_measurements.txt: every shape measured and what each arm
+    took).  That is one class: float32, feat a multiple of 4 in 260 .. 512, n_out in 64 .. 128 and at most 21 250 destination rows --
+    260 / 384 / 512 -> 128 and 512 -> 64 were measured on four blocks each and won on all sixteen (1.11 - 2.51 x); widths and n_out
+    between measured points are taken with them, nothing outside them.  21 250 rows is the largest measured block that won at all four
+    shapes; the next larger one measured (34 682 rows) lost at 512 -> 128, and nothing between the two was timed.  Larger float32
+    blocks, 602 -> 128 and 1024 -> 256 won on some shapes and lost on others, and bfloat16 lost or tied on every shape: those take the
+    composition.  Block.sage adds what only it knows: every measured x had 16-byte lanes (a pitch that is a multiple of 4 floats, a
+    16-byte aligned first row); an x without them takes the composition."""
+    return (dtype == torch.float32 and 260 <= feat <= 512 and feat % 4 == 0 and 64 <= n_out <= 128 and num_dst <= 21250
+            and block_sage_wide_supported(feat, n_out, dtype))
+
+
 def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None,
                    relu=False, fused=None):
     """Block.sage as a function (the thin form over gnnagg_block_sage_run); every dtype and shape refusal is raised before device work"""
@@ -281,8 +303,13 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
     odt = out.dtype if out is not None else (out_dtype or x.dtype)
     if x.dtype == torch.float32 and odt != torch.float32:
         raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
-    if fused and not block_sage_supported(feat, n_out, x.dtype):
+    wide = isinstance(fused, str) and fused == "wide"
+    if fused is not None and not wide:
+        fused = bool(fused)   # (1, 0 and numpy's bools mean True and False, as they always have)
+    if fused is True and not block_sage_supported(feat, n_out, x.dtype):
         raise ValueError("fused=True: gnnagg_block_sage_supported(feat=%d, n_out=%d, %s) says no" % (feat, n_out, x.dtype))
+    if wide and not block_sage_wide_supported(feat, n_out, x.dtype):
+        raise ValueError("fused=\"wide\": gnnagg_block_sage_wide_supported(feat=%d, n_out=%d, %s) says no" % (feat, n_out, x.dtype))
     # device tensors, contiguous where the call wants them dense
     px, pitch = _dev_ptr_rows(x, x.dtype, "x")
     p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
@@ -296,8 +323,9 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
         if t is not None and t.device != x.device:
             raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
     # ---- device work
-    if fused is None:
-        fused = sage_prefers_fused(blk.num_dst, feat, n_out, x.dtype)
+    if fused is None:   # the narrow kernel wherever it serves, else the chunked one where it was measured faster, else the composition
+        lanes16 = pitch % 4 == 0 and x.data_ptr() % 16 == 0   # (the lanes sage_prefers_wide was measured with)
+        fused = sage_prefers_fused(blk.num_dst, feat, n_out, x.dtype) or (lanes16 and sage_prefers_wide(blk.num_dst, feat, n_out, x.dtype) and "wide")
     if not fused:   # the composition a caller writes with the existing calls
         y = block_gcn_run(blk, x, reduce=reduce, val=val, val_full=val_full, gathered=gathered, return_dst=mapped and w_self is not None)
         if w_self is not None:
@@ -315,10 +343,10 @@ def block_sage_run(blk, x, w_neigh, w_self=None, bias=None, reduce="mean", val=N
         return out
     if out is None:
         out = torch.empty(shape, dtype=odt, device=x.device)
-    check(lib().gnnagg_block_sage_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, p_ws, p_wn,
-                                      p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
-                                      REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
-                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    run = lib().gnnagg_block_sage_wide_run if fused == "wide" else lib().gnnagg_block_sage_run
+    check(run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, p_val, p_eid, px, xdt, pitch, feat, p_ws, p_wn,
+              p_b, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype],
+              REDUCE[reduce], _lib.FLAG_RELU if relu else 0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

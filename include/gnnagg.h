@@ -1030,6 +1030,28 @@ int gnnagg_block_sage_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
 int gnnagg_block_sage_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
 int gnnagg_block_sage_grid_cap(int feat, int n_out, int x_dtype);
 
+/* Block SAGE layer, wide rows: the layer of gnnagg_block_sage_run for 1 <= feat <= 4096 and 1 <= n_out <= 256
+ * (csrc/agg_block_sage_wide.hip) -- the input layer of a mini-batch, where rows are widest (Pubmed 500, reddit 602, MAG 768, ...).
+ * The arguments, the aggregation, the self row, the combine and its k order, the types, the fp32 bits (those of gnnagg_matmul_nn over
+ * cat([x_dst, y]) and cat([W_self, W_neigh])), the bf16 bound, determinism, non-finite values, the refusals and their texts are those of
+ * gnnagg_block_sage_run; at a shape both serve, the two give the same bits.  What differs:
+ *   k chunks     the k dimension of [W_self; W_neigh] runs in chunks of KC = gnnagg_block_sage_wide_chunk(x_dtype) columns (128 fp32,
+ *                64 bf16) through a double-buffered LDS tile of rows x KC: first the chunks of the self half (plain copies of x_dst),
+ *                then those of the neighbour half (one walk of the row's edges per chunk), each ascending.  The accumulators of a tile
+ *                stay in registers across its chunks; the epilogue runs once.  bf16: the weight image is staged per chunk and serves
+ *                16 R rows (R = 4 for n_out <= 128, else 1).
+ *   range        gnnagg_block_sage_wide_supported(feat, n_out, x_dtype): 1 <= feat <= 4096, 1 <= n_out <= 256, fp32 or bf16.  The LDS of
+ *                a workgroup depends on KC and n_out, never on feat, and at least two workgroups fit a CU at every shape:
+ *                gnnagg_block_sage_wide_grid_cap (0 outside the range) is constant in feat.
+ * (tests/test_block_sage_wide_host.py, tests/test_gpu_block_sage_wide.py; DESIGN.md "Block SAGE layer") */
+int gnnagg_block_sage_wide_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes,
+                               const float *d_val, const int *d_eid, const void *d_x, int x_dtype, long long x_pitch, int feat,
+                               const void *d_w_self, const void *d_w_neigh, const float *d_bias, int n_out,
+                               void *d_out, int out_dtype, int reduce, int flags, void *hip_stream);
+int gnnagg_block_sage_wide_supported(int feat, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_sage_wide_grid_cap(int feat, int n_out, int x_dtype);
+int gnnagg_block_sage_wide_chunk(int x_dtype);                            /* KC; 0 for an unknown x_dtype */
+
 /* Block GIN layer: PyG's GINConv(nn = Sequential(Linear, ReLU, Linear), eps) / DGL's GINConv(apply_func = MLP, aggregator_type = sum |
  * mean | max) on one sampled block in one launch (csrc/agg_block_gin.hip) --
  *   h[i]   = self_scale * x_dst[i] + aggr_{p in row i}(val_p * x_src(p))       [feat]

@@ -4,11 +4,13 @@ batch of the arxiv- and products-shaped graphs, 1 024 / 8 192 seeds, fanout 10 /
 and bf16 -> bf16.  Arms:
 
     f   the fused call: one launch                                                           (blk.sage(..., fused=True))
+    w   the chunked kernel for wide rows: one launch                                         (blk.sage(..., fused="wide"))
     c   the composition: blk.aggregate(return_dst=True), two matmul_NN, add, bias, ReLU      (the yardstick)
 
 The block is sampled once outside the timing.  The arms alternate inside every round on a non-null stream; a round times `--calls`
 back-to-back calls of one arm (wall clock around a stream synchronisation); the figure of an arm is the median over `--rounds` rounds, with
-the minimum and maximum of a round.  (f) is checked against (c) on every shape: fp32 against the one-GEMM form of the composition bit for
+the minimum and maximum of a round.  (f) runs where F and n_out lie in its range (<= 256), (w) everywhere: --feat 512 / 602 / 1024 time
+(w) against (c), --feat 128 all three.  (f) and (w) are checked against (c) on every shape: fp32 against the one-GEMM form of the composition bit for
 bit, bf16 inside 2^-6 of the largest output (two roundings of y and of out apart).  One JSON line per (graph, batch, fanout, n_out,
 types); nothing is asserted about speed.
 
@@ -81,16 +83,24 @@ def main():
                             return torch.relu(gnc.matmul_NN(x_dst, ws, out_dtype=torch.float32) + gnc.matmul_NN(y, wn, out_dtype=torch.float32)
                                               + bias).to(dt)
 
+                        def arm_w():
+                            return blk.sage(x, wn, ws, bias, reduce="mean", relu=True, out=out, fused="wide")
+
+                        arms = {"f": arm_f} if gnc.block_sage_supported(F, n_out, dt) else {}
+                        arms.update(w=arm_w, c=arm_c)
                         with torch.cuda.stream(stream):
-                            got, want = arm_f().clone(), arm_c()
+                            want = arm_c()
                             one_gemm = blk.sage(x, wn, ws, bias, reduce="mean", relu=True, fused=False)
-                        stream.synchronize()
-                        if dt == torch.float32:
-                            assert torch.equal(got.view(torch.int32), one_gemm.view(torch.int32)), (name, batch, fanout, n_out)
-                        assert torch.isfinite(got).all().item() and torch.isfinite(want).all().item(), (name, batch, fanout, n_out, tag)
-                        worst = float((got.double() - want.double()).abs().max())
-                        assert worst <= 2.0 ** -6 * float(want.double().abs().max()), (name, batch, fanout, n_out, tag, worst)
-                        arms = {"f": arm_f, "c": arm_c}
+                        worst = {}
+                        for arm in [a for a in arms if a != "c"]:
+                            with torch.cuda.stream(stream):
+                                got = arms[arm]().clone()
+                            stream.synchronize()
+                            if dt == torch.float32:
+                                assert torch.equal(got.view(torch.int32), one_gemm.view(torch.int32)), (arm, name, batch, fanout, n_out)
+                            assert torch.isfinite(got).all().item() and torch.isfinite(want).all().item(), (arm, name, batch, fanout, n_out, tag)
+                            worst[arm] = float((got.double() - want.double()).abs().max())
+                            assert worst[arm] <= 2.0 ** -6 * float(want.double().abs().max()), (arm, name, batch, fanout, n_out, tag, worst[arm])
                         for fn in arms.values():
                             time_round(fn, 2)
                         times = {arm: [] for arm in arms}
@@ -100,8 +110,14 @@ def main():
                         med = {arm: statistics.median(t) for arm, t in times.items()}
                         rec = dict(input="%s-shaped input-layer block" % name, library=args.label, V=V, E=E, batch=n, fanout=fanout, types=tag, feat=F,
                                    n_out=n_out, rounds=args.rounds, calls=args.calls, num_dst=blk.num_dst, num_src=blk.num_src, edges=blk.num_edges,
-                                   c_over_f=med["c"] / med["f"], f_beats_c_by_more_than_the_spread=bool(max(times["f"]) < min(times["c"])),
-                                   c_beats_f_by_more_than_the_spread=bool(max(times["c"]) < min(times["f"])), worst_abs_diff_f_c=worst)
+                                   **{"worst_abs_diff_%s_c" % arm: w for arm, w in worst.items()})
+                        for arm in worst:   # an arm wins where its slowest round beat the other's fastest
+                            rec["c_over_" + arm] = med["c"] / med[arm]
+                            rec[arm + "_beats_c_by_more_than_the_spread"] = bool(max(times[arm]) < min(times["c"]))
+                            rec["c_beats_%s_by_more_than_the_spread" % arm] = bool(max(times["c"]) < min(times[arm]))
+                        # bytes the layer must move, compulsory: every edge's source row, the self rows, both weights once, out
+                        esz = 4 if dt == torch.float32 else 2
+                        rec["model_bytes"] = (blk.num_edges + blk.num_dst) * F * esz + 2 * F * n_out * esz + blk.num_dst * n_out * esz
                         for arm, t in times.items():
                             rec[arm + "_us"] = med[arm]
                             rec[arm + "_min_max_us"] = [min(t), max(t)]
