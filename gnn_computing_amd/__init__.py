@@ -19,6 +19,7 @@ from .sampling import (  # noqa: F401
     block_gin_run, block_gin_supported, gin_prefers_fused,
     block_pna_run, block_pna_supported, pna_prefers_fused,
 )
+from .scoring import pair_score, pair_score_supported, pair_score_prefers_fused  # noqa: F401
 from . import graph  # noqa: F401
 from . import probe  # noqa: F401
 # (gnn_computing_amd.extras -- torch.autograd wrappers over the backward entry points -- needs libgnnagg_extras.so: out of scope per

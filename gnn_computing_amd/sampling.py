@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import check, lib
 from .aggregator import (AGGRS, FEATURE_DTYPES, REDUCE, SCALERS, Aggregator_GAT, Aggregator_GCN, _bias_heads, _dev_ptr, _dev_ptr_rows, _edge_rows, _feat_dtype,
                          matmul_NN)
+from .scoring import pair_score
 
 _U64 = (1 << 64) - 1
 
@@ -153,6 +154,17 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         Rows without edges are +0.  Returns y."""
         return block_attn_run(self, q, k, v, kind=kind, a=a, heads=heads, scale=scale, slope=slope, bias=bias, bias_full=bias_full, edge=edge,
                               edge_full=edge_full, gathered=gathered, out=out, out_dtype=out_dtype)
+
+    def score(self, hd, hs=None, kind="dot", rel=None, etype=None, combine="mul", w1=None, w2=None, b1=None, b2=None, relu=False, gathered=False,
+              out=None, out_dtype=None, fused=None):
+        """One score (kind="mlp": one row of n_out values) per EDGE of this block in ONE launch on torch's current stream
+        (gnnagg_pair_score_run): pair_score over the block's own CSR -- edge p of destination row i scores (hd row of i, hs row of idx[p]);
+        the kernel finds i itself, no row array is built.  hs=None: hs = hd.  gathered=False on a relabelled block: hd and hs are
+        matrices of the graph the block was sampled from, read through src_nodes; gathered=True, or a block of global ids: the row
+        number and idx index them directly.  etype: one type per edge of the block.  Everything else as in pair_score().
+        Returns out, [num_edges] or [num_edges, n_out], in the block's edge order."""
+        return pair_score(hd, hd if hs is None else hs, ptr=self.ptr, idx=self.idx, src=None if gathered else self.src_nodes, kind=kind, rel=rel,
+                          etype=etype, combine=combine, w1=w1, w2=w2, b1=b1, b2=b2, relu=relu, out=out, out_dtype=out_dtype, fused=fused)
 
 
 def block_gcn_run(blk, x, reduce="mean", val=None, val_full=False, gathered=False, out=None, out_dtype=None, relu=False, return_dst=False):

@@ -1271,6 +1271,66 @@ int gnnagg_block_attn_run(const int *d_blk_ptr, const int *d_blk_idx, int num_ds
                           void *d_y, int y_dtype, int feat, int heads, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * G. Pair scoring: one value (or one row of n_out values) per node PAIR in one launch (csrc/agg_pair_score.hip) -- the decoders of
+ *    link prediction, edge classification and knowledge-graph completion over embeddings the layers above produced.  Everything before
+ *    this section writes one row per destination node.
+ * ------------------------------------------------------------------------------------------- */
+/*   pairs        exactly ONE of two forms.  COO: d_u [num_pairs], d_v [num_pairs] (positive and negative samples alike).  CSR: d_ptr
+ *                [num_rows + 1], d_idx [num_pairs]: v_p = d_idx[p] and u_p = the row r with d_ptr[r] <= p < d_ptr[r + 1], found on the
+ *                device by binary search (the largest r with d_ptr[r] <= p: empty rows, wherever they lie, are never an answer); no
+ *                expanded row array is built.  num_rows is read with d_ptr only.
+ *   rows         ru = d_src_nodes ? d_src_nodes[u_p] : u_p is the row of hu, rv = d_src_nodes ? d_src_nodes[v_p] : v_p the row of hv: the
+ *                map of a relabelled block, applied to BOTH ids.  Ids are not validated.
+ *   GNNAGG_PAIR_DOT   out[p] = sum_f hu[ru][f] * hv[rv][f], fp32 [num_pairs].  With d_rel (fp32 [num_rel, feat], dense) and d_etype
+ *                (int32 [num_pairs]) DistMult: out[p] = sum_f (hu[ru][f] * rel[t_p][f]) * hv[rv][f]; a pair whose type lies outside
+ *                [0, num_rel) scores +0 and reads no row.  Per lane c = fmaf(hu, hv, c) (DistMult: fmaf(fmul(hu, rel), hv, c)) over
+ *                the lane's columns in ascending f from +0, then a fixed xor butterfly over the lanes of the group: the result is a
+ *                function of the operands' values and of the lane geometry (feat, the pitches, the alignment of hu, hv and rel), never
+ *                of the pair form, of num_pairs or of the pairs around it.  No atomics, no LDS.  Against float64 over the stored
+ *                operands, A = sum_f |hu| |rel| |hv|: |out - out64| <= (gamma_n + 1e-5) A, n = feat rounded up to 32, + 8.
+ *                combine is GNNAGG_PAIR_MUL, out_dtype GNNAGG_DTYPE_F32, flags 0, every weight NULL.
+ *   GNNAGG_PAIR_MLP   out[p] = act( relu( m_p . W1 + b1 ) . W2 + b2 ), [num_pairs, n_out] dense.  GNNAGG_PAIR_MUL: m_p = hu[ru] (*) hv[rv]
+ *                -- ONE fp32 rounding per element; with bf16 operands the product is exact in fp32 and rounded to bf16 once -- and W1 is
+ *                [feat, hidden].  GNNAGG_PAIR_CAT: m_p = [hu[ru], hv[rv]] and W1 is [2 feat, hidden].  W2 is [hidden, n_out]; both
+ *                row-major, dense, of x_dtype; b1 [hidden], b2 [n_out] fp32 or NULL.  The hidden ReLU is always applied;
+ *                GNNAGG_FLAG_RELU is the activation of out and the only flag; a NaN stays a NaN.  With bf16 operands z is rounded to
+ *                bf16 once, after the ReLU; out is fp32 for fp32 operands, fp32 or bf16 (one rounding) for bf16 operands.  Neither m nor
+ *                z is ever in memory.
+ *     fp32       one fp32 accumulator per element, k ascending, on v_mfma_f32_16x16x4_f32: the fmaf chain of gnnagg_matmul_nn, so out
+ *                equals, bit for bit, act(matmul_nn(relu(matmul_nn(m, W1) + b1), W2) + b2) with m formed by one fp32 product or a copy.
+ *     bf16       v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  Against float64 over the stored operands, A_1 = |m| |W1| + |b1|,
+ *                A_2 = A_1 |W2| + |b2|, u16 = 2^-8: |out - out64| <= ((1 + gamma_n)(1 + u16)^2 - 1 + 1e-5) A_2, n = Kp + Hp + 8 (Kp, Hp: the
+ *                k of W1 and hidden rounded up to 32); a bf16 out adds its one rounding.
+ *     range      gnnagg_pair_score_supported(kind, combine, feat, hidden, n_out, x_dtype) is the one place the rule lives.  dot: feat >= 1.
+ *                mlp: 1 <= feat, hidden, n_out <= 256 and [m tile: 32 pairs][z tile: 32 pairs][bf16: the images of W1 and W2] inside
+ *                the 160 KB of LDS of a CU -- every fp32 shape (cat 256 -> 256: 99 328 bytes); bf16 e.g. mul 256 -> 128 -> 256 and cat
+ *                128 -> 128 -> 47 (106 240), not mul 256 -> 256 -> 1 (177 408) or cat 256 -> 256 (the image of W1 alone is 266 240).  Workgroups walk tiles of 32 pairs; an
+ *                mlp launch holds at most gnnagg_pair_score_grid_cap workgroups (0 outside the range; dot has no cap: INT_MAX).
+ *   types        hu, hv, W1, W2 share x_dtype (GNNAGG_DTYPE_F32 or GNNAGG_DTYPE_BF16); hu rows are hu_pitch ELEMENTS apart, hv rows
+ *                hv_pitch (each >= feat): column views serve.  hu and hv may be one matrix.  out aliases no input.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_pairs = 0 launches nothing and returns GNNAGG_OK -- after every check below that does not need a pointer.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: an unknown kind or combine; num_pairs < 0;
+ *                feat < 1; hu_pitch or hv_pitch below feat; an unknown x_dtype or out_dtype; fp32 operands with a bf16 out; any flag but
+ *                GNNAGG_FLAG_RELU; both pair forms, or half of one (d_u without d_v, d_ptr without d_idx, ...); d_ptr with
+ *                num_rows < 1; d_etype without d_rel or d_rel without d_etype; for dot: any of d_w1, d_w2, d_b1, d_b2, an out_dtype
+ *                other than fp32, a flag, GNNAGG_PAIR_CAT, d_rel with num_rel < 1; for mlp: d_rel, hidden < 1, n_out < 1, a shape
+ *                outside the supported range; with num_pairs > 0: neither pair form, a null d_hu, d_hv, d_out, (mlp) d_w1 or d_w2.
+ *   not here     no backward entry point; no heads; no sigmoid or loss epilogue; MLPs of other depths; feat > 256 for the mlp.
+ * (tests/test_pair_score_host.py, tests/test_gpu_pair_score.py; DESIGN.md "Pair scoring") */
+#define GNNAGG_PAIR_DOT 0
+#define GNNAGG_PAIR_MLP 1
+#define GNNAGG_PAIR_MUL 0
+#define GNNAGG_PAIR_CAT 1
+int gnnagg_pair_score_run(int kind, int combine, const int *d_u, const int *d_v, const int *d_ptr, const int *d_idx, int num_rows,
+                          int num_pairs, const int *d_src_nodes, const void *d_hu, long long hu_pitch, const void *d_hv,
+                          long long hv_pitch, int x_dtype, int feat, const float *d_rel, const int *d_etype, int num_rel,
+                          const void *d_w1, const float *d_b1, int hidden, const void *d_w2, const float *d_b2, int n_out, void *d_out,
+                          int out_dtype, int flags, void *hip_stream);
+int gnnagg_pair_score_supported(int kind, int combine, int feat, int hidden, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_pair_score_grid_cap(int kind, int combine, int feat, int hidden, int n_out, int x_dtype);
+
+/* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
  * ------------------------------------------------------------------------------------------- */
