@@ -18,6 +18,7 @@ from .sampling import (  # noqa: F401
     block_rgcn_basis_run, block_rgcn_basis_supported, rgcn_basis_prefers_fused,
     block_gin_run, block_gin_supported, gin_prefers_fused,
     block_pna_run, block_pna_supported, pna_prefers_fused,
+    block_edgeconv_run, block_edgeconv_supported, edgeconv_prefers_fused,
 )
 from .scoring import pair_score, pair_score_supported, pair_score_prefers_fused  # noqa: F401
 from . import graph  # noqa: F401

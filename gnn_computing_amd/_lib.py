@@ -19,6 +19,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 ATTN_DOT, ATTN_GATV2 = 0, 1   # gnnagg_block_attn_run
 PAIR_DOT, PAIR_MLP = 0, 1     # gnnagg_pair_score_run: kind
 PAIR_MUL, PAIR_CAT = 0, 1     # gnnagg_pair_score_run: combine
+EDGECONV_DIFF, EDGECONV_CAT = 0, 1   # gnnagg_block_edgeconv_run: combine
 AGGR_SUM, AGGR_MEAN, AGGR_MIN, AGGR_MAX, AGGR_VAR, AGGR_STD = 1, 2, 4, 8, 16, 32   # gnnagg_gcn_run_multi
 SCALER_IDENTITY, SCALER_AMPLIFICATION, SCALER_ATTENUATION = 1, 2, 4
 
@@ -189,6 +190,11 @@ SIGNATURES = {
                                       c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "gnnagg_pair_score_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "gnnagg_pair_score_grid_cap": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    # H: block EdgeConv layer
+    "gnnagg_block_edgeconv_run": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_int, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "gnnagg_block_edgeconv_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "gnnagg_block_edgeconv_grid_cap": (c_int, [c_int, c_int, c_int, c_int, c_int]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

@@ -83,6 +83,24 @@ class Block(collections.namedtuple("Block", "ptr idx src_nodes eid num_dst num_s
         return block_gin_run(self, x, w1, w2, b1=b1, b2=b2, eps=eps, reduce=reduce, val=val, val_full=val_full, gathered=gathered, out=out,
                              out_dtype=out_dtype, relu=relu, fused=fused)
 
+    def edgeconv(self, x, w1, w2, b1=None, b2=None, combine="diff", reduce="max", gathered=False, out=None, out_dtype=None, relu=False, fused=None):
+        """An edge-MLP layer on this block -- EdgeConv / DGCNN (combine="diff", reduce="max") or the MPNN / interaction-network message
+        (combine="cat") -- out[i] = act(reduce_p (relu(m_p @ w1 + b1) @ w2 + b2)) over the edges p of row i, with
+        m_p = cat(x_i, x_s - x_i) ("diff") or cat(x_i, x_s) ("cat"), x_i the destination's own row and x_s the row of idx[p], in ONE
+        launch on torch's current stream (gnnagg_block_edgeconv_run): no [E, 2 F] operand and no [E, n_out] message matrix is stored.
+        x, gathered, out, out_dtype: as in gin().
+          w1, w2       contiguous [2 F, hidden] and [hidden, n_out] tensors of x's dtype
+          b1, b2       None or float32 [hidden] / [n_out]
+          reduce       "sum", "mean" or "max"; a row without edges is +0 for each
+          relu         the activation of out, after the reduction; the hidden ReLU is always applied
+          fused        True: the kernel, ValueError where gnnagg_block_edgeconv_supported says no.  False: the composition of existing calls
+                       (the index of both row sets, a difference, cat, matmul_NN, bias, ReLU, matmul_NN, bias, then aggregate() over the
+                       [E, n_out] messages) -- for float32 the same bits.  None: the kernel where it was measured faster
+                       (edgeconv_prefers_fused).
+        Returns out."""
+        return block_edgeconv_run(self, x, w1, w2, b1=b1, b2=b2, combine=combine, reduce=reduce, gathered=gathered, out=out, out_dtype=out_dtype,
+                                  relu=relu, fused=fused)
+
     def pna(self, x, w, w_self=None, bias=None, aggrs=("mean", "min", "max", "std"), scalers=("identity",), delta=None, val=None, val_full=False,
             gathered=False, out=None, out_dtype=None, relu=False, fused=None):
         """A PNA layer on this block -- PNAConv / MultiAggregation with a linear post-transform and a self term --
@@ -472,6 +490,115 @@ def block_gin_run(blk, x, w1, w2, b1=None, b2=None, eps=0.0, reduce="sum", val=N
                                      p_w1, p_b1, hidden, p_w2, p_b2, n_out, ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None,
                                      FEATURE_DTYPES[out.dtype], REDUCE[reduce], _lib.FLAG_RELU if relu else 0,
                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+EDGECONV_COMBINES = {"diff": _lib.EDGECONV_DIFF, "cat": _lib.EDGECONV_CAT}
+
+
+def block_edgeconv_supported(combine, feat, hidden, n_out, dtype):
+    """gnnagg_block_edgeconv_supported: does the fused kernel of Block.edgeconv serve [2 feat] -> [hidden] -> [n_out] with operands of `dtype`?"""
+    return (combine in EDGECONV_COMBINES and dtype in FEATURE_DTYPES
+            and bool(lib().gnnagg_block_edgeconv_supported(EDGECONV_COMBINES[combine], int(feat), int(hidden), int(n_out), FEATURE_DTYPES[dtype])))
+
+
+def edgeconv_prefers_fused(num_dst, combine, feat, hidden, n_out, dtype):
+    """The fused=None rule of Block.edgeconv: the kernel wherever it is supported.  Its slowest round beat the composition's fastest
+    round at all 64 shapes timed (profiles/block_edgeconv/README.md: arxiv- and products-shaped input blocks of 1 024 / 8 192 seeds and
+    fanout 10 / 25, F = 3 and 64, hidden = n_out = 64, float32 and bfloat16, max and mean, combine="diff"; 1.33 - 4.58 x); no class
+    lost.  "cat" and other widths were not timed and are taken with the measured ones."""
+    return block_edgeconv_supported(combine, feat, hidden, n_out, dtype)
+
+
+def block_edgeconv_run(blk, x, w1, w2, b1=None, b2=None, combine="diff", reduce="max", gathered=False, out=None, out_dtype=None, relu=False,
+                       fused=None):
+    """Block.edgeconv as a function (the thin form over gnnagg_block_edgeconv_run); every dtype and shape refusal is raised before device work"""
+    if reduce not in REDUCE:
+        raise ValueError("reduce must be one of %s, got %r" % (sorted(REDUCE), reduce))
+    if combine not in EDGECONV_COMBINES:
+        raise ValueError("combine must be one of %s, got %r" % (sorted(EDGECONV_COMBINES), combine))
+    mapped = blk.src_nodes is not None and not gathered
+    if out_dtype is not None and out_dtype not in FEATURE_DTYPES:
+        raise TypeError("out_dtype must be torch.float32 or torch.bfloat16, got %s" % (out_dtype,))
+    # types and shapes
+    xdt = _feat_dtype(x, "x")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("x must be 2-D [rows, F] with F >= 1, got %s" % (tuple(x.shape),))
+    feat = int(x.shape[1])
+    need_rows = max(blk.num_src, blk.num_dst) if not mapped else 0
+    if int(x.shape[0]) < need_rows:
+        raise ValueError("x has %d rows, the block's ids index %d (gathered=%s)" % (x.shape[0], need_rows, bool(gathered)))
+    for name, w in (("w1", w1), ("w2", w2)):
+        if not isinstance(w, torch.Tensor) or w.dtype != x.dtype:
+            raise TypeError("%s must be a tensor of x's dtype %s, got %s" % (name, x.dtype, getattr(w, "dtype", type(w).__name__)))
+    if w1.dim() != 2 or int(w1.shape[0]) != 2 * feat or int(w1.shape[1]) < 1:
+        raise ValueError("w1 must be [%d, hidden] with hidden >= 1 (2 F rows: both halves of the message input), got %s" % (2 * feat, tuple(w1.shape)))
+    hidden = int(w1.shape[1])
+    if w2.dim() != 2 or int(w2.shape[0]) != hidden or int(w2.shape[1]) < 1:
+        raise ValueError("w2 must be [%d, n_out] with n_out >= 1, got %s" % (hidden, tuple(w2.shape)))
+    n_out = int(w2.shape[1])
+    shape = (blk.num_dst, n_out)
+    for name, b, n in (("b1", b1, hidden), ("b2", b2, n_out)):
+        if b is None:
+            continue
+        if not isinstance(b, torch.Tensor) or b.dtype != torch.float32:
+            raise TypeError("%s must be a torch.float32 tensor or None" % name)
+        if tuple(b.shape) != (n,):
+            raise ValueError("%s must be [%d], got %s" % (name, n, tuple(b.shape)))
+    if out is not None:
+        _feat_dtype(out, "out")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise TypeError("out is %s, out_dtype says %s" % (out.dtype, out_dtype))
+        if tuple(out.shape) != shape:
+            raise ValueError("out must be [%d, %d], got %s" % (shape + (tuple(out.shape),)))
+    odt = out.dtype if out is not None else (out_dtype or x.dtype)
+    if x.dtype == torch.float32 and odt != torch.float32:
+        raise TypeError("out_dtype: float32 operands give a float32 out, got %s" % (odt,))
+    if fused and not block_edgeconv_supported(combine, feat, hidden, n_out, x.dtype):
+        raise ValueError("fused=True: gnnagg_block_edgeconv_supported(%s, feat=%d, hidden=%d, n_out=%d, %s) says no"
+                         % (combine, feat, hidden, n_out, x.dtype))
+    # device tensors, contiguous where the call wants them dense
+    px, pitch = _dev_ptr_rows(x, x.dtype, "x")
+    p_ptr, p_idx = _dev_ptr(blk.ptr, torch.int32, "blk.ptr"), _dev_ptr(blk.idx, torch.int32, "blk.idx")
+    p_src = _dev_ptr(blk.src_nodes, torch.int32, "blk.src_nodes") if mapped else None
+    p_w1, p_w2 = _dev_ptr(w1, x.dtype, "w1"), _dev_ptr(w2, x.dtype, "w2")
+    p_b1, p_b2 = _dev_ptr(b1, torch.float32, "b1"), _dev_ptr(b2, torch.float32, "b2")
+    if out is not None:
+        _dev_ptr(out, out.dtype, "out")
+    for name, t in (("blk.ptr", blk.ptr), ("w1", w1), ("w2", w2), ("b1", b1), ("b2", b2), ("out", out)):
+        if t is not None and t.device != x.device:
+            raise ValueError("%s lives on %s, x on %s" % (name, t.device, x.device))
+    # ---- device work
+    if fused is None:
+        fused = edgeconv_prefers_fused(blk.num_dst, combine, feat, hidden, n_out, x.dtype)
+    if not fused:   # the composition a caller writes with the existing calls
+        E = blk.num_edges
+        if E:
+            rows = torch.searchsorted(blk.ptr[1:].long().contiguous(), torch.arange(E, device=x.device), right=True)
+            ri, rs = (blk.src_nodes[rows].long(), blk.src_nodes[blk.idx.long()].long()) if mapped else (rows, blk.idx.long())
+            xi, xs = x[ri], x[rs]
+            z = matmul_NN(torch.cat([xi, xs - xi if combine == "diff" else xs], 1), w1, out_dtype=torch.float32)
+            if b1 is not None:
+                z = z + b1
+            msg = matmul_NN(z.clamp_min(0).to(x.dtype), w2, out_dtype=torch.float32)
+            if b2 is not None:
+                msg = msg + b2
+            edges = Block(blk.ptr, torch.arange(E, device=x.device, dtype=torch.int32), None, None, blk.num_dst, E, E)
+            res = block_gcn_run(edges, msg, reduce=reduce, gathered=True)
+        else:
+            res = torch.zeros(shape, dtype=torch.float32, device=x.device)
+        if relu:
+            res = res.clamp_min(0)
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=x.device)
+    check(lib().gnnagg_block_edgeconv_run(p_ptr, p_idx if blk.num_edges else None, blk.num_dst, p_src, px, xdt, pitch, feat,
+                                          EDGECONV_COMBINES[combine], p_w1, p_b1, hidden, p_w2, p_b2, n_out,
+                                          ctypes.c_void_p(out.data_ptr()) if blk.num_dst else None, FEATURE_DTYPES[out.dtype], REDUCE[reduce],
+                                          _lib.FLAG_RELU if relu else 0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

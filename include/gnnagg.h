@@ -1331,6 +1331,47 @@ int gnnagg_pair_score_supported(int kind, int combine, int feat, int hidden, int
 int gnnagg_pair_score_grid_cap(int kind, int combine, int feat, int hidden, int n_out, int x_dtype);
 
 /* ---------------------------------------------------------------------------------------------
+ * H. Block EdgeConv layer: a two-layer MLP on every EDGE of one sampled block, reduced per destination row, in one launch
+ *    (csrc/agg_block_edgeconv.hip) -- EdgeConv / DGCNN (diff, max) and the MPNN / interaction-network message (cat, sum | mean).
+ *    Every layer of section F aggregates rows of x and transforms once per destination; here the non-linear function sits on the edge.
+ * ------------------------------------------------------------------------------------------- */
+/*   the block    d_blk_ptr [num_dst + 1], d_blk_idx, d_src_nodes (or NULL: ids index x directly) as in gnnagg_block_gcn_run.  Edge
+ *                position p of row i has s = d_blk_idx[p]; x_i is row d_src_nodes[i] (or i) of x, x_s row d_src_nodes[s] (or s).
+ *   the message  m_p = [x_i , x_s - x_i] (GNNAGG_EDGECONV_DIFF: one fp32 subtraction, with bf16 operands rounded to bf16 once) or
+ *                [x_i , x_s] (GNNAGG_EDGECONV_CAT);  msg_p = relu( m_p . W1 + b1 ) . W2 + b2 with W1 [2 feat, hidden], W2 [hidden, n_out]
+ *                row-major, dense, of x_dtype, b1 / b2 fp32 or NULL: the GNNAGG_PAIR_MLP contract of section G, chains and roundings
+ *                (bf16: z rounded once), with fp32 messages that are never in memory.
+ *   the row      out[i] = act( reduce_p msg_p ), [num_dst, n_out] dense.  GNNAGG_REDUCE_SUM / _MEAN: one fp32 chain per element in
+ *                ascending CSR order from +0, the mean divided by (float) degree; GNNAGG_REDUCE_MAX: v > run ? v : run from -inf, and a
+ *                NaN message makes the row's element NaN.  A row without edges is +0 for every reduce.  GNNAGG_FLAG_RELU is the
+ *                activation of out and the only flag.  out is fp32 for fp32 operands, fp32 or bf16 (one rounding) for bf16 operands.
+ *                A row is reduced by one workgroup: no atomics, and no bit of out depends on the grid.
+ *     fp32       bit for bit the composition: matmul_nn chains over the m rows of every edge, then gnnagg_block_gcn_run over the
+ *                [E, n_out] messages (finite messages; the composition's max drops a NaN).
+ *     bf16       per edge the bound of GNNAGG_PAIR_MLP with A_m = [|x_i|, |x_i| + |x_s|] (diff) and n grown by the row's length for
+ *                sum and mean; the row bound is the sum (mean: / degree; max: the largest) of its edges' bounds.
+ *   range        gnnagg_block_edgeconv_supported(combine, feat, hidden, n_out, x_dtype): 1 <= feat, hidden, n_out <= 256 and [384 bytes]
+ *                [accumulators 16 x (roundup16(n_out) + 4) fp32][m tile of k = 2 feat U message tile 32 x (roundup16(n_out) + 4) fp32]
+ *                [z tile][bf16: both weight images] inside the 160 KB of LDS of a CU: every fp32 shape; bf16 e.g. 64 -> 64 -> 128, not
+ *                128 -> 256 -> 256.  A launch holds at most gnnagg_block_edgeconv_grid_cap workgroups (0 outside the range).
+ *   types        x rows are x_pitch ELEMENTS apart (>= feat): column views serve.  out aliases no input.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, ONE launch on hip_stream, capturable into a HIP graph.
+ *                num_dst = 0 launches nothing and returns GNNAGG_OK -- after every check below that does not need a pointer.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: num_dst < 0; an unknown combine or reduce; feat,
+ *                hidden or n_out < 1; x_pitch below feat; an unknown x_dtype or out_dtype; fp32 operands with a bf16 out; any flag but
+ *                GNNAGG_FLAG_RELU; a shape outside the range; with num_dst > 0 a null d_blk_ptr, d_x, d_w1, d_w2 or d_out.
+ *   not here     edge weights, per-edge feature rows, min, MLPs of other depths, a backward pass; a hub row is walked by its one
+ *                workgroup.
+ * (tests/test_block_edgeconv_host.py, tests/test_gpu_block_edgeconv.py; DESIGN.md "Block EdgeConv") */
+#define GNNAGG_EDGECONV_DIFF 0
+#define GNNAGG_EDGECONV_CAT 1
+int gnnagg_block_edgeconv_run(const int *d_blk_ptr, const int *d_blk_idx, int num_dst, const int *d_src_nodes, const void *d_x, int x_dtype,
+                              long long x_pitch, int feat, int combine, const void *d_w1, const float *d_b1, int hidden, const void *d_w2,
+                              const float *d_b2, int n_out, void *d_out, int out_dtype, int reduce, int flags, void *hip_stream);
+int gnnagg_block_edgeconv_supported(int combine, int feat, int hidden, int n_out, int x_dtype);   /* 1: the kernel serves this shape */
+int gnnagg_block_edgeconv_grid_cap(int combine, int feat, int hidden, int n_out, int x_dtype);
+
+/* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
  * ------------------------------------------------------------------------------------------- */
