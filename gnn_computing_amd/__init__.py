@@ -21,6 +21,7 @@ from .sampling import (  # noqa: F401
     block_edgeconv_run, block_edgeconv_supported, edgeconv_prefers_fused,
 )
 from .scoring import pair_score, pair_score_supported, pair_score_prefers_fused  # noqa: F401
+from .knn import knn_graph, knn_run, knn_out_ptr, knn_supported, knn_prefers_fused, knn_work_bytes  # noqa: F401
 from . import graph  # noqa: F401
 from . import probe  # noqa: F401
 # (gnn_computing_amd.extras -- torch.autograd wrappers over the backward entry points -- needs libgnnagg_extras.so: out of scope per

@@ -195,6 +195,11 @@ SIGNATURES = {
                                           c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gnnagg_block_edgeconv_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "gnnagg_block_edgeconv_grid_cap": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    # I: kNN graph
+    "gnnagg_knn_run": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p]),
+    "gnnagg_knn_supported": (c_int, [c_int, c_int, c_int]),
+    "gnnagg_knn_work_bytes": (ctypes.c_longlong, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
 }
 
 # Section E of the header: only libgnnagg_extras.so (-DGNNAGG_EXTRAS; GNNAGG_LIB=.../libgnnagg_extras.so) exports these

@@ -272,6 +272,10 @@ int launch_gat_row_shift(const int *ptr, const int *idx, const float *att, float
 // slot < 0 = the row's only segment); rows of several segments leave one (m, den, acc) triple per segment in scratch, folded in ascending
 // order (mrow: int4 {row, first slot, end slot, -}).  feat <= kGatv2MaxFeat.
 constexpr int kGatv2Batch = 4, kGatv2LongEdges = 128, kGatv2SegEdges = 512, kGatv2MaxFeat = 1024;
+// kNN graph (agg_knn.hip, gnnagg_knn_run): the range, the candidate tile, a row's best list (one key per lane of a wavefront) and queue,
+// and the most shares a candidate range is split into
+constexpr int kKnnMaxFeat = 256, kKnnMaxK = 64, kKnnTile = 64, kKnnList = 64, kKnnQueue = 128, kKnnMaxSplits = 16;
+constexpr int kKnnLdsBytes = 160 * 1024;
 struct AttnLaunch {   // what GATv2 and dot-product attention launch alike (gatv2_shared.cuh: attn_fill_args)
     const int *ptr = nullptr, *idx = nullptr;
     const void *seg = nullptr, *mrow = nullptr;

@@ -1372,6 +1372,47 @@ int gnnagg_block_edgeconv_supported(int combine, int feat, int hidden, int n_out
 int gnnagg_block_edgeconv_grid_cap(int combine, int feat, int hidden, int n_out, int x_dtype);
 
 /* ---------------------------------------------------------------------------------------------
+ * I. k-nearest-neighbour graph: distances on the MFMA and a streaming top-k selection in one kernel (csrc/agg_knn.hip).  The [n, m]
+ *    distance matrix is never in memory; the result is the (ptr, idx) of a block of global ids, which every call of sections F - H takes.
+ * ------------------------------------------------------------------------------------------- */
+/*   the points   queries d_x [n, feat], candidates d_y [m, feat] of x_dtype (fp32 or bf16), rows x_pitch / y_pitch ELEMENTS apart
+ *                (>= feat: column views serve).  d_y = NULL: the candidates are the queries (m must equal n; y_pitch and d_y_ptr are not
+ *                read), and with loop = 0 the candidate j = i is excluded by index.  loop is read in that case only.
+ *   segments     d_x_ptr [num_seg + 1], d_y_ptr [num_seg + 1], int32, ascending, from 0 to n / m: query i of segment b (x_ptr[b] <= i <
+ *                x_ptr[b + 1], found by bisection) sees the candidates y_ptr[b] <= j < y_ptr[b + 1] only.  Both NULL (num_seg is then
+ *                not read): one segment.  The kernel clamps what it reads from them to [0, m]: pointers that break the contract give
+ *                rows of the wrong candidates, never an access outside y.
+ *   the order    per query the candidates of its segment ascending by the key (r_ij, j), r_ij = |y_j|^2 - 2 x_i . y_j in fp32 (the
+ *                products on the MFMA, bf16 rows widened exactly), compared as the monotone integer image of the float bits with every
+ *                NaN above +inf; ties go to the lower j.  The first count_i = min(k, segment size - excluded) are kept in that order.
+ *                The order is total, so the result is a function of the inputs alone: no bit depends on the grid, the tiling or splits.
+ *   the output   d_out_ptr [n + 1] is an INPUT: the running sum of count_i, a closed form of the segment sizes that the caller computes.
+ *                d_idx [out_ptr[n]] int32 ids into y; d_dist (or NULL) [out_ptr[n]] fp32 d_ij = max(|x_i|^2 + r_ij, 0).  One workgroup
+ *                (splits = 1) or one wavefront of the merge kernel owns a row of the output: no atomics on it.
+ *                The norm expansion cancels for points much closer than their norms (the error of d_ij is of the order 2^-24 (|x_i|^2 +
+ *                |y_j|^2), whatever d_ij is): centre a cloud that lies far from the origin.
+ *   splits       S > 1: workgroup (query tile, s) walks the s-th share of the tile's candidate range and leaves its best k keys in
+ *                d_work; a second kernel merges the S lists of a row by the same order.  0: the library picks S from the number of query
+ *                tiles and of CUs.  1 <= S <= 16.  gnnagg_knn_work_bytes(n, m, feat, k, x_dtype, num_seg, splits) is the size d_work must
+ *                have (0 where S resolves to 1; d_work may then be NULL).
+ *   range        gnnagg_knn_supported(feat, k, x_dtype): 1 <= feat <= 256, 1 <= k <= 64 and [query tile][1 or 2 candidate tiles of 64
+ *                rows][per query row: 64 best keys, a queue of 128 keys, 24 bytes] inside the 160 KB of LDS of a workgroup with a query
+ *                tile of 64 or 32 rows (the larger where it fits, two candidate tiles before one): every feat of the range fits.
+ *   the call     stateless: no handle, no allocation, no host synchronisation, one or two launches on hip_stream, capturable.
+ *                n = 0 launches nothing and returns GNNAGG_OK -- after every check below that does not need a pointer.
+ *   refusals     GNNAGG_ERR_ARG with a text naming the argument, before any HIP call: n or m < 0; feat outside 1..256; k outside 1..64;
+ *                an unknown x_dtype; a pitch below feat; d_y NULL with m != n; one of d_x_ptr / d_y_ptr NULL and the other not (d_y
+ *                given); num_seg < 1 with pointers; splits outside 0..16; with n > 0 a null d_x, d_out_ptr or d_idx; a d_work that is
+ *                NULL or smaller than gnnagg_knn_work_bytes where S > 1.
+ *   not here     cosine / inner-product metrics, k > 64, feat > 256, radius graphs, a direct-difference path for feat <= 4.
+ * (tests/test_knn_host.py, tests/test_gpu_knn.py; DESIGN.md "kNN graph") */
+int gnnagg_knn_run(const void *d_x, const void *d_y, int x_dtype, long long x_pitch, long long y_pitch, int n, int m, int feat, int k,
+                   const int *d_x_ptr, const int *d_y_ptr, int num_seg, int loop, const int *d_out_ptr, int *d_idx, float *d_dist,
+                   void *d_work, long long work_bytes, int splits, void *hip_stream);
+int gnnagg_knn_supported(int feat, int k, int x_dtype);   /* 1: the kernel serves this shape */
+long long gnnagg_knn_work_bytes(int n, int m, int feat, int k, int x_dtype, int num_seg, int splits);   /* -1: arguments out of range */
+
+/* ---------------------------------------------------------------------------------------------
  * E. Extras: libgnnagg_extras.so only (`make -C gnn_computing_amd/csrc extras`, -DGNNAGG_EXTRAS).  NOT in the shipped library:
  *    the reference is forward-only and SURVEY 2.2 marks its one backward kernel ("Experiment", no caller) out of scope.
  * ------------------------------------------------------------------------------------------- */
